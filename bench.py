@@ -19,11 +19,14 @@ searches in flight, separate HIP streams); value = 4N GiB / max-over-ranks time.
 states joined into an RCCL communicator (ncclCommInitAll), the collective search timed as `value` (main_multi_device); if the
 communicator cannot be set up the same shards are searched without it and the line says so (`collective_error`).
 
-Next to the contract's fields the N = 1 line carries `roofline`, `cpu_baseline` (the reference's natives, rows compared
-with the GPU stream before timing), `target_4gib` (the north-star size) and `configs` — the other BASELINE configs at 1 GiB
-and, for configs[1], `end_to_end` (the reference's call form on plain bytes: first / repeat / cache-off call, PCIe
-included, never `value`) and `file_api` (find_near_matches_in_file on the same GiB).  A failure in those secondary blocks
-is reported in the line (`extras_error`, `end_to_end_error`, `file_api.error`), never instead of it.
+A plain run does what the headline figure needs: it sets up, warms up, times exactly --steps steps, writes the last step's
+match stream if --dump-outputs is given, and prints the line; `roofline` then comes from the timed launches' own spans and
+the committed PMC profile.  With --full the N = 1 line also carries `value_sync` (one synchronous call at a time, and the
+roofline from those launches, HBM traffic measured in the run), `cpu_baseline` (the reference's natives, rows compared with
+the GPU stream before timing; every N), `target_4gib` (the north-star size), `regimes` and `configs` — the other BASELINE
+configs at 1 GiB and, for configs[1], `end_to_end` (the reference's call form on plain bytes: first / repeat / cache-off
+call, PCIe included, never `value`) and `file_api` (find_near_matches_in_file on the same GiB).  A failure in those
+secondary blocks is reported in the line (`extras_error`, `end_to_end_error`, `file_api.error`), never instead of it.
 
 Prints ONE JSON line on rank 0.
 """
@@ -65,6 +68,16 @@ def parse():
                     help="after the timed region, also time the two-deep pipeline with the younger scan on a second stream "
                          "(fz_set_streams(2)) and report it as `two_streams` beside `value`.  Not part of the default run: the "
                          "scans then overlap, and a kernel trace of the run would average overlapped launches of the headline kernel")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the CPU baseline (compared row by row "
+                         "with the GPU stream), and at N = 1 the synchronous-call latency (`value_sync`, the roofline from "
+                         "synchronous launches), the live HBM traffic, the 4 GiB target, the other BASELINE configs, the regimes "
+                         "and the end-to-end / file API calls.  Without it a run sets up, warms up, times --steps steps and prints "
+                         "its line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last step's ordered raw match stream (the rows the caller of the "
+                         "timed path receives) to DIR/<field>.npy, one float64 array per field (start, end, dist, block); "
+                         "beyond 64 MB in all a fixed, seeded sample of the rows")
     return ap.parse_args()
 
 
@@ -79,6 +92,27 @@ def _cpu_fn():
     except Exception as exc:                                        # pragma: no cover
         print("cpu_baseline: reference natives unusable (%r); timing the C port instead" % (exc,), file=sys.stderr)
     return oracle.lev_ngrams_raw, "port"
+
+
+MATCH_FIELDS = ("start", "end", "dist", "block")
+DUMP_LIMIT_BYTES = 64 * 10 ** 6 - (64 << 10)      # 64 MB in all, npy headers included
+
+
+def dump_outputs(dirname, rows):
+    """--dump-outputs: `rows` (the fz_match stream of the last timed step: a structured array, or an (n, 4) integer array
+    in MATCH_FIELDS order) -> DIR/<field>.npy as float64 (offsets < 2**53 are exact).  A stream too large for the limit is
+    cut to a sample of rows drawn with a fixed seed, kept in stream order."""
+    rows = np.asarray(rows)
+    cols = [rows[f] for f in MATCH_FIELDS] if rows.dtype.names else [rows.reshape(-1, len(MATCH_FIELDS))[:, i]
+                                                                     for i in range(len(MATCH_FIELDS))]
+    n = len(cols[0])
+    cap = DUMP_LIMIT_BYTES // (8 * len(cols))
+    if n > cap:
+        keep = np.sort(np.random.default_rng(20250925).choice(n, cap, replace=False))
+        cols = [c[keep] for c in cols]
+    os.makedirs(dirname, exist_ok=True)
+    for name, col in zip(MATCH_FIELDS, cols):
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(col, dtype=np.float64))
 
 
 _CPU_SHARD = {}
@@ -578,7 +612,7 @@ def main_multi_device(args):
     global_n = shard_bytes * N
 
     cpu = None
-    if not args.no_cpu_baseline:                                 # forks: before the HIP runtime exists in this process
+    if args.full and not args.no_cpu_baseline:                   # forks: before the HIP runtime exists in this process
         sample, _pat, _pl = workloads.cfg2(min(shard_bytes, 1 << 30), 1024)
         cpu = cpu_baseline(sample, pattern, k, args.cpu_sample_mib)
         cpu["sample"] += " (the first GiB of a shard's workload)"
@@ -699,6 +733,8 @@ def main_multi_device(args):
         collective = False
         rccl_ranks = 0
         first, matches, elapsed, per_dev, gather, st, sync_ms, settle = timed_phase(False)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, matches)
 
     # the same search without the collective (per-device records merged on the host), same run
     no_coll = None
@@ -919,6 +955,8 @@ def main_launcher_fallback(args, err):
         heads = [np.frombuffer(b[:24], dtype=np.float64) for b in blobs]
         streams = [np.frombuffer(b[24:], dtype=np.int64).reshape(-1, 4) for b in blobs]
         merged = fzd.merge_rank_streams(streams)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, merged)
         matches = [tuple(int(x) for x in r) for r in merged.tolist()]
         found = {(s_, e_, d_) for (s_, e_, d_, _g) in matches}
         missing = [q for q in edge_plants if (q, q + m, 0) not in found]
@@ -1009,7 +1047,7 @@ def main_rank(args):
         fill(rank, seq)
 
     cpu = None
-    if not args.no_cpu_baseline and rank == 0 and not use_torch:
+    if args.full and not args.no_cpu_baseline and rank == 0 and not use_torch:
         # forks: before the HIP runtime exists.  N > 1: rank 0 times the first GiB of its shard while the other ranks
         # wait for the communicator's unique id (the timed region starts behind a barrier)
         cpu = cpu_baseline(seq[:1 << 30] if world > 1 else seq, pattern, k, args.cpu_sample_mib)
@@ -1156,9 +1194,11 @@ def main_rank(args):
                             "same process and run" % args.mib}
         sync()
         engine.comm_set_collective(True)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, matches)
     sync_ms = None
     sync_spans = []
-    if not use_dist and not args.sync:
+    if not use_dist and not args.sync and args.full:
         # latency of one synchronous call (one search in flight), outside the timed region
         for _ in range(10):
             assert np.array_equal(step(), matches), "pipelined and synchronous searches returned different streams"
@@ -1202,7 +1242,7 @@ def main_rank(args):
         f_ms = float(np.mean(sync_spans)) if sync_spans else f_pipe   # spans of 200 synchronous launches: the kernel alone
         achieved = shard_bytes / (f_ms * 1e-3) / 1e9           # algorithmic bytes: N read once
         traffic_gb, traffic_src = (None, None)
-        if world == 1 and not use_dist and not args.no_live_traffic:
+        if world == 1 and not use_dist and args.full and not args.no_live_traffic:
             traffic_gb, traffic_src = live_traffic(args.mib)
         if traffic_gb is None:
             traffic_gb, traffic_src = measured_traffic(shard_bytes)
@@ -1272,7 +1312,7 @@ def main_rank(args):
                 ref1["x_vs_1gpu"] = round(value / ref1["value"], 3)
                 out["scaling_ref_1gpu"] = ref1
         out["cpu_baseline"] = cpu
-        if world == 1 and not use_dist and not args.no_extras:
+        if world == 1 and not use_dist and args.full and not args.no_extras:
             handle.release()
             del seq
             try:

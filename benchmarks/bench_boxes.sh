@@ -1,5 +1,5 @@
 #!/bin/bash
-# One box, one line of profiles/r06_bench_boxes.txt: the default `python bench.py` line's roofline figure (live hipEvent spans of
+# One box, one line of profiles/r06_bench_boxes.txt: the `python bench.py --full` line's roofline figure (live hipEvent spans of
 # synchronous launches) beside the rocprofv3 kernel-trace average of the same kernel on the same box, same code.
 # usage (GPU box): bash benchmarks/bench_boxes.sh <tag>   -> gpurun_out/boxes/<tag>.txt (+ the bench line itself)
 set -u
@@ -8,10 +8,10 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/boxes
 mkdir -p $OUT
 cd $ROOT
-python bench.py > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err; echo "bench rc=$?"
+python bench.py --full > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err; echo "bench rc=$?"
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/boxtrace
-timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/boxtrace -- python $ROOT/bench.py --no-cpu-baseline --no-live-traffic > $OUT/trace_$TAG.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/boxtrace -- python $ROOT/bench.py --full --no-cpu-baseline --no-live-traffic > $OUT/trace_$TAG.log 2>&1
 echo "trace rc=$?"
 cd $ROOT
 python - "$TAG" <<'EOF'

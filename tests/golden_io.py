@@ -1,6 +1,9 @@
-"""Reader for tests/golden/reference_calls.jsonl (written by tests/golden/gen_golden.py) and the
+"""Readers for tests/golden/reference_calls.jsonl (written by tests/golden/gen_golden.py) and
+tests/golden/reference_results.json.gz (written by tests/golden/gen_reference_results.py), and the
 tie-aware comparator of SURVEY.md §8(c)."""
 import base64
+import gzip
+import hashlib
 import json
 import os
 import zlib
@@ -8,6 +11,7 @@ import zlib
 import oracle
 
 FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_calls.jsonl")
+RESULTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_results.json.gz")
 
 
 class RefMatch(tuple):
@@ -71,6 +75,52 @@ def load(fn=None):
 
 def triples(matches):
     return [(m.start, m.end, m.dist) for m in matches]
+
+
+def inputs_digest(cases):
+    """sha256 over every input case, in order (byte strings as their bytes, everything else as its repr): the fixture's
+    results belong to exactly these inputs."""
+    h = hashlib.sha256()
+
+    def feed(x):
+        if isinstance(x, (tuple, list)):
+            h.update(b"(%d" % len(x))
+            for v in x:
+                feed(v)
+            h.update(b")")
+        elif isinstance(x, (bytes, bytearray)):
+            h.update(b"b%d:" % len(x) + bytes(x))
+        else:
+            h.update(repr(x).encode("ascii") + b";")
+    for case in cases:
+        feed(case)
+    return h.hexdigest()
+
+
+_results = None
+
+
+def recorded(name, cases):
+    """-> the reference's results for test `name`, recorded over `cases` (the test's own seeded inputs, list); fails when
+    the inputs are no longer the ones the fixture was written for."""
+    global _results
+    if _results is None:
+        with gzip.open(RESULTS, "rt") as f:
+            _results = json.load(f)
+    rec = _results[name]
+    assert rec["inputs"] == inputs_digest(cases), "%s: the inputs differ from the recorded ones: rerun gen_reference_results.py" % name
+    assert len(rec["results"]) == len(cases), name
+    return rec["results"]
+
+
+def as_triples(rows):
+    return [tuple(r) for r in rows]
+
+
+def rows_digest(rows):
+    """[number of rows, sha256 of their (start, end, dist)]: how the fixture stores long ordered match lists."""
+    rows = [[int(x) for x in r[:3]] for r in rows]
+    return [len(rows), hashlib.sha256(json.dumps(rows, separators=(",", ":")).encode("ascii")).hexdigest()]
 
 
 def equal_modulo_ties(got, expected, raw):

@@ -126,5 +126,33 @@ def test_round4_multi_device_lines():
 def test_bench_argument_surface():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup"):
+    for flag in ("--gpus", "--steps", "--warmup", "--full", "--dump-outputs"):
         assert flag in out.stdout
+
+
+def test_dump_outputs_files(tmp_path):
+    """--dump-outputs: one float64 array per fz_match field, exact for a stream within the limit; a larger stream is cut to
+    the same seeded sample of rows on every run, in stream order, and the files stay within 64 MB in all."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    dt = np.dtype([("start", "<i8"), ("end", "<i8"), ("dist", "<i4"), ("block", "<i4")])
+    rows = np.zeros(1000, dtype=dt)
+    rows["start"] = np.arange(1000) * 4099 + (5 << 30)
+    rows["end"], rows["dist"], rows["block"] = rows["start"] + 21, np.arange(1000) % 3, np.arange(1000) // 7
+    bench.dump_outputs(str(tmp_path / "small"), rows)
+    for f in bench.MATCH_FIELDS:
+        got = np.load(str(tmp_path / "small" / (f + ".npy")))
+        assert got.dtype == np.float64 and np.array_equal(got, rows[f])
+    n = bench.DUMP_LIMIT_BYTES // 32 + 12345
+    big = np.arange(4 * n, dtype=np.int64).reshape(n, 4)
+    samples = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        bench.dump_outputs(str(d), big)
+        assert sum(os.path.getsize(str(d / (f + ".npy"))) for f in bench.MATCH_FIELDS) <= 64 * 10 ** 6
+        cols = [np.load(str(d / (f + ".npy"))) for f in bench.MATCH_FIELDS]
+        assert len(cols[0]) < n and np.all(np.diff(cols[0]) > 0)
+        assert all(np.array_equal(c, cols[0] + i) for i, c in enumerate(cols))          # rows stay whole
+        samples.append(cols[0])
+    assert np.array_equal(samples[0], samples[1])
