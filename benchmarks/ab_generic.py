@@ -19,6 +19,6 @@ for _ in range(60):
     r = call()
     a, b, _d = eng.kernel_ms(); f.append(a); v.append(b); dv.append(_d)
 dt = (time.perf_counter() - t0) / 60
-print(json.dumps({"lib": os.path.basename(_native.LIB_PATH), "consolidated": cons, "grid_per_cu": os.environ.get("FZ_LP_GRID_PER_CU", "16"), "ms_per_call": round(dt * 1e3, 4),
+print(json.dumps({"lib": os.path.basename(_native.LIB_PATH), "consolidated": cons, "ms_per_call": round(dt * 1e3, 4),
                   "scan_ms": round(float(np.mean(f)), 4), "automaton_ms": round(float(np.mean(v)), 4), "device_ms": round(float(np.mean(dv)), 4),
-                  "order": "host" if os.environ.get("FZ_GEN_HOST_ORDER") else "device", "sha": __import__("hashlib").sha1(r.tobytes()).hexdigest()[:12], "raw": len(r)}), flush=True)
+                  "sha": __import__("hashlib").sha1(r.tobytes()).hexdigest()[:12], "raw": len(r)}), flush=True)

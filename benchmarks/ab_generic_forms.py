@@ -1,5 +1,5 @@
 """configs[3b] (1 GiB UTF-8 text, m = 64, limits (5, 2, 2, 5)): the generic search's C-ABI time and kernel spans for the
-automaton forms selected by the environment (FZ_GEN_LEGACY=1, FZ_GH_WAVES=4, FZ_GEN_NO_DEDUP=1, FZ_GH_GRID_PER_CU)."""
+automaton forms selected by the environment (FZ_GEN_LEGACY=1, FZ_GH_WAVES=4, FZ_GEN_NO_DEDUP=1)."""
 import hashlib, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np

@@ -4,7 +4,4 @@ import sys,json
 for l in sys.stdin:
     d=json.loads(l); print(d['m'],d['k'],'ms',d['ms'],'kernel',d['scan_kernel_ms'])"; }
 run A=1
-for t in 6 8 16 24; do run FZ_TILES_PER_WG=$t; done
-for r in 3 5 6 8; do run FZ_ROUNDS=$r; done
 run FZ_TAPER_STEPS=0
-run FZ_DUAL_STREAM=1

@@ -33,7 +33,6 @@
 #include <new>
 #include <string>
 #include <thread>
-#include <sys/stat.h>
 #include <unistd.h>
 #include <map>
 #include <mutex>
@@ -46,30 +45,25 @@
 namespace {
 
 // Every process-wide switch of the library: read from the environment ONCE, on first use, into this struct.  None of them is
-// needed to use the library; tests, A/B measurements and lab builds set them (INTEGRATION.md §5 describes each).  Results
-// never depend on a switch — the -m gpu suite runs the same cases under the ones marked (t) and compares with the oracle.
+// needed to use the library; tests and A/B measurements set them (INTEGRATION.md §5 describes each).  Results never depend
+// on a switch — the -m gpu suite runs the same cases under the ones marked (t) and compares with the oracle.
 struct Switches {
     // (t) alternative forms of the same computation
     bool no_direct = false;            // FZ_NO_DIRECT: records / counters through D2H copies, never the kernels' stores into pinned memory
     bool no_slot_and = false;          // FZ_NO_SLOT_AND: the filter's general slot form (shift + and) for every launch
     int max_blocks = 0;                // FZ_MAX_BLOCKS=n: at most n n-gram blocks per scan launch
     bool force_big_verify = false;     // FZ_FORCE_BIG_VERIFY: every stand-alone verification by fz_verify_big_kernel
-    bool no_wavefront = false;         // FZ_NO_WAVEFRONT: lane-per-candidate verification where lane-per-cell would run
     bool no_wf_fuse = false;           // FZ_NO_WF_FUSE: budgets 5 .. 15 verified by the stand-alone kernel, not inside the scan
     int wf32 = -1;                     // FZ_WF32=0 / 1: pin the fused lane-per-cell form off / on for budgets 8 .. 15 (default: by density)
     bool no_bits = false;              // FZ_NO_BITS: no bit-vector verification (Levenshtein budgets >= FZ_BITS_MIN_K take round 5's forms)
     int bits_min_k = 3;                // FZ_BITS_MIN_K=k: smallest Levenshtein budget always verified by bit-vector columns (below: the register
                                        // band unless the pattern lets expect dense candidates)
     int bits_qcap = 0;                 // FZ_BITS_QCAP=n: queue entries per wave of the bit-vector form (default: by LDS)
-    int bits_lds_kb = 0;               // FZ_BITS_LDS_KB: LDS per scan workgroup the bit-vector form may take (default 26)
     bool gen_legacy = false;           // FZ_GEN_LEGACY: the generic automaton as fz_lp_kernel (one wave per hit, round 3's form)
     bool gen_no_dedup = false;         // FZ_GEN_NO_DEDUP: no window table (every n-gram hit runs its automaton)
-    bool gen_direct = false;           // FZ_GEN_DIRECT: automaton records stored straight into pinned host memory (round 1)
-    bool gen_host_order = false;       // FZ_GEN_HOST_ORDER: the generic rows ordered by the host, not by fz_gen_order / scatter kernels
     int gh_waves = 0;                  // FZ_GH_WAVES=1 / 2 / 4: waves per hit of fz_gen_hit_kernel
     bool gh_no_bits = false;           // FZ_GH_NO_BITS: round 4's candidate step instead of the bit-parallel one
     int cand_lds_max = 0;              // FZ_CAND_LDS_MAX=n: candidate lists beyond n entries live in HBM
-    bool group_best_exact = false;     // FZ_GROUP_BEST_EXACT: fz_group_best by the exact walk only
     bool no_dev_threads = false;       // FZ_NO_DEV_THREADS: a multi-device context drives every device from the calling thread
     int taper_steps = 4;               // FZ_TAPER_STEPS (0: no regions), FZ_TAPER_MIN, FZ_TAPER_WG_PER_CU: the scan grid's last round
     double taper_min = 0.25;
@@ -77,21 +71,10 @@ struct Switches {
     bool no_rccl = false;              // FZ_NO_RCCL: behave like an install without librccl
     std::string rccl_lib;              // FZ_RCCL_LIB=path: the collective library to dlopen first (tests: tests/libmock_rccl.so)
     std::string rocm_path = "/opt/rocm";   // ROCM_PATH
-    // measurement / lab knobs (same results; they move work or change launch shapes)
-    bool trace = false;                // FZ_TRACE: per-phase host timings of a search on stderr
-    bool no_timing = false;            // FZ_NO_TIMING: contexts start without hipEvent timing of their kernels
-    bool dual_stream = false;          // FZ_DUAL_STREAM: contexts start with fz_set_streams(2)
-    bool no_ext_launch = false;        // FZ_NO_EXT_LAUNCH: events recorded behind the kernels instead of on their dispatch packets
-    bool gen_hi_stream = false;        // FZ_GEN_HI_STREAM: the generic automaton on a high-priority stream of its lane
-    bool no_spin = false;              // FZ_NO_SPIN: no hipDeviceScheduleSpin
-    bool stream_default_priority = false;   // FZ_STREAM_DEFAULT_PRIORITY: the scan streams at default instead of lowest priority
-    bool stream_nofill = false;        // FZ_STREAM_NOFILL: file streams without the reads (H2D + scan alone)
-    bool stream_trace = false;         // FZ_STREAM_TRACE: host time split of a file stream on stderr
-    long worker_spin_us = 1500;        // FZ_WORKER_SPIN_US: how long a device's worker thread spins before it sleeps
     long comm_timeout_ms = 60000;      // FZ_COMM_TIMEOUT_MS: deadline of every wait for a collective (then FZ_ETIMEOUT, not a hung job)
-    int fused_lds_kb = 0, fused_target_kb = 0, extra_lds_kb = 0;   // FZ_FUSED_LDS_KB, FZ_FUSED_TARGET_KB, FZ_EXTRA_LDS_KB: LDS shaping of the scan
-    int tiles_per_wg = 0, rounds = 0, wg_per_cu = 0;               // FZ_TILES_PER_WG, FZ_ROUNDS, FZ_WG_PER_CU: the scan grid
-    int lp_grid_per_cu = 24, gh_grid_per_cu = 0;                   // FZ_LP_GRID_PER_CU, FZ_GH_GRID_PER_CU: automaton grids
+    // diagnostics (print only)
+    bool trace = false;                // FZ_TRACE: per-phase host timings of a search on stderr
+    bool stream_trace = false;         // FZ_STREAM_TRACE: host time split of a file stream on stderr
 };
 
 Switches read_switches() {
@@ -99,26 +82,17 @@ Switches read_switches() {
         auto flag = [](const char *n) { return getenv(n) != nullptr; };
         auto num = [](const char *n, int dflt) { const char *e = getenv(n); return e ? atoi(e) : dflt; };
         v.no_direct = flag("FZ_NO_DIRECT"); v.no_slot_and = flag("FZ_NO_SLOT_AND"); v.max_blocks = num("FZ_MAX_BLOCKS", 0);
-        v.force_big_verify = flag("FZ_FORCE_BIG_VERIFY"); v.no_wavefront = flag("FZ_NO_WAVEFRONT"); v.no_wf_fuse = flag("FZ_NO_WF_FUSE");
+        v.force_big_verify = flag("FZ_FORCE_BIG_VERIFY"); v.no_wf_fuse = flag("FZ_NO_WF_FUSE");
         v.no_bits = flag("FZ_NO_BITS"); v.bits_min_k = num("FZ_BITS_MIN_K", 3); v.bits_qcap = num("FZ_BITS_QCAP", 0);
-        v.bits_lds_kb = num("FZ_BITS_LDS_KB", 0);
         v.wf32 = num("FZ_WF32", -1); v.gen_legacy = flag("FZ_GEN_LEGACY"); v.gen_no_dedup = flag("FZ_GEN_NO_DEDUP");
-        v.gen_direct = flag("FZ_GEN_DIRECT"); v.gen_host_order = flag("FZ_GEN_HOST_ORDER"); v.gh_waves = num("FZ_GH_WAVES", 0);
-        v.gh_no_bits = flag("FZ_GH_NO_BITS"); v.cand_lds_max = num("FZ_CAND_LDS_MAX", 0); v.group_best_exact = flag("FZ_GROUP_BEST_EXACT");
+        v.gh_waves = num("FZ_GH_WAVES", 0); v.gh_no_bits = flag("FZ_GH_NO_BITS"); v.cand_lds_max = num("FZ_CAND_LDS_MAX", 0);
         v.no_dev_threads = flag("FZ_NO_DEV_THREADS"); v.taper_steps = num("FZ_TAPER_STEPS", 4);
         if (const char *e = getenv("FZ_TAPER_MIN")) v.taper_min = atof(e);
         v.taper_wg_per_cu = num("FZ_TAPER_WG_PER_CU", 7); v.no_rccl = flag("FZ_NO_RCCL");
         if (const char *e = getenv("FZ_RCCL_LIB")) v.rccl_lib = e;
         if (const char *e = getenv("ROCM_PATH")) v.rocm_path = e;
-        v.trace = flag("FZ_TRACE"); v.no_timing = flag("FZ_NO_TIMING"); v.dual_stream = num("FZ_DUAL_STREAM", 0) != 0;
-        v.no_ext_launch = flag("FZ_NO_EXT_LAUNCH"); v.gen_hi_stream = flag("FZ_GEN_HI_STREAM"); v.no_spin = flag("FZ_NO_SPIN");
-        v.stream_default_priority = flag("FZ_STREAM_DEFAULT_PRIORITY"); v.stream_nofill = flag("FZ_STREAM_NOFILL");
-        v.stream_trace = flag("FZ_STREAM_TRACE");
-        if (const char *e = getenv("FZ_WORKER_SPIN_US")) v.worker_spin_us = atol(e);
         if (const char *e = getenv("FZ_COMM_TIMEOUT_MS")) v.comm_timeout_ms = std::max(1L, atol(e));
-        v.fused_lds_kb = num("FZ_FUSED_LDS_KB", 0); v.fused_target_kb = num("FZ_FUSED_TARGET_KB", 0); v.extra_lds_kb = num("FZ_EXTRA_LDS_KB", 0);
-        v.tiles_per_wg = num("FZ_TILES_PER_WG", 0); v.rounds = num("FZ_ROUNDS", 0); v.wg_per_cu = num("FZ_WG_PER_CU", 0);
-        v.lp_grid_per_cu = num("FZ_LP_GRID_PER_CU", 24); v.gh_grid_per_cu = num("FZ_GH_GRID_PER_CU", 0);
+        v.trace = flag("FZ_TRACE"); v.stream_trace = flag("FZ_STREAM_TRACE");
         return v;
 }
 
@@ -198,7 +172,7 @@ struct DevState {
     bool dedup_used = false;                     // the search being collected ran with it (row count = counters[FZ_HDR_GEN_ROWS])
     bool gen_multi_used = false;                 // ... and its automaton as fz_gen_hit_kernel (counters[FZ_HDR_GEN_FAIL]: hits it gave up on)
     uint64_t gen_rows_cap = 0;                   // rows
-    uint8_t *h_big = nullptr, *h_big_dev = nullptr;
+    uint8_t *h_big = nullptr;
     uint64_t big_cap = 0;                        // records
     // one recycled sequence allocation (chunked file reads upload / release 1 MiB buffers in a loop;
     // hipMalloc + hipFree per chunk would dominate)
@@ -219,21 +193,18 @@ struct DevState {
     uint64_t hit_cap_used = 0, rec_cap_used = 0;
     bool fused_used = false;
     uint32_t form_used = 0;                      // FZ_FORM_* of the last enqueue
-    bool wf32_candidate = false;                 // the search in this slot could have verified inside the scan with 32 lanes per candidate
     bool timed = true;                           // the search being collected recorded its start event
     double last_filter_ms = 0;                   // scan span of the search collected last on this device (fz_device_ms)
     uint64_t fold_guess = 8192, fold_copied = 0; // folded generic search: pairs fetched with the counters
     bool fold_direct = true;                     // ... or written straight into h_stage by the automaton kernel (while they fit)
     bool fold_was_direct = false;                // mode of the folded search being collected
     int lp_end_event = 2;                        // which event marks the end of the last automaton kernel (2, or 3 = the completion)
-    hipStream_t stream_hi = nullptr;             // generic searches in flight: the automaton and what follows it (high priority)
-    hipEvent_t ev_scan_done = nullptr;
     uint8_t *d_pat = nullptr;                    // pattern in HBM (subsequences longer than FZ_MAX_M, fz_verify_big_kernel)
     uint64_t pat_cap = 0;
     int slot_id = 0;                             // which of the two result slots is the current one
     uint32_t launches_used = 0;                  // scan launches of the last enqueue on this device
     // Two fused searches in flight (result slot 1): the younger one's scan on a stream and a counter block of its own, so
-    // that it starts while the older scan drains instead of behind it (FZ_DUAL_STREAM=0: one stream, as before)
+    // that it starts while the older scan drains instead of behind it (fz_set_streams(ctx, 2); default: one stream)
     hipStream_t stream_alt = nullptr;
     uint8_t *d_hdr_alt = nullptr;
     // RCCL (fz_comm_*): this device state is rank comm_rank of a communicator.  A search of such a context leaves
@@ -253,7 +224,7 @@ struct DevState {
     struct Slot {
         hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
         uint8_t *h_stage = nullptr, *h_stage_dev = nullptr;
-        bool last_direct = false, verify_launched = false, fused_used = false, timed = true, wf32_candidate = false;
+        bool last_direct = false, verify_launched = false, fused_used = false, timed = true;
         int scan_end_event = 1, verify_end_event = 2;
         uint64_t hit_cap_used = 0, rec_cap_used = 0;
         int slot_id = 1;
@@ -267,7 +238,6 @@ struct DevState {
         std::swap(verify_launched, other.verify_launched);
         std::swap(timed, other.timed);
         std::swap(fused_used, other.fused_used);
-        std::swap(wf32_candidate, other.wf32_candidate);
         std::swap(scan_end_event, other.scan_end_event);
         std::swap(verify_end_event, other.verify_end_event);
         std::swap(hit_cap_used, other.hit_cap_used);
@@ -305,10 +275,9 @@ struct DevWorkers {
         bool stop = false;
     };
     std::vector<W *> ws;
-    long spin_us = 1500;
+    static constexpr long kSpinUs = 1500;
 
     explicit DevWorkers(size_t n) {
-        spin_us = sw().worker_spin_us;
         for (size_t i = 0; i < n; ++i) {
             W *w = new W();
             ws.push_back(w);
@@ -330,7 +299,7 @@ struct DevWorkers {
             unsigned spins = 0;
             while (w->posted.load(std::memory_order_acquire) == seen) {
                 if ((++spins & 255u) == 0 &&
-                    std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() > spin_us) {
+                    std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() > kSpinUs) {
                     std::unique_lock<std::mutex> lk(w->mu);
                     w->cv.wait(lk, [&]() { return w->stop || w->posted.load(std::memory_order_acquire) != seen; });
                     if (w->stop) return;
@@ -391,7 +360,6 @@ struct ShardOut {
 struct fz_ctx {
     std::vector<DevState> devs;
     fz_stats_t stats{};
-    bool last_fused = false;
     // Candidate slots per list of the per-hit automaton kernel.  Small lists let every wave of the launch
     // be resident at once (256 slots: 8 KB of LDS per wave, 19 waves per CU; 1024: 7 per CU); a search
     // that overflows them re-runs with 4x the slots and the context remembers.
@@ -441,7 +409,7 @@ struct fz_ctx {
     std::vector<uint32_t> seg_order;
     // hipEvent timing of the kernels (fz_stats: filter_ms / verify_ms / device_ms).  One event record is one more packet
     // in front of the kernel and two hipEventElapsedTime calls behind it: fz_set_timing(ctx, 0) drops them.
-    bool timing = !sw().no_timing;
+    bool timing = true;
     // The spans are read from the events only when somebody asks (fz_stats / fz_device_ms): a hipEventElapsedTime call
     // costs ~5 us of host time, two or three of them sat between the completion of every search and its result.  The
     // references die with the next launch of the context (whose enqueue re-records the events).
@@ -452,8 +420,8 @@ struct fz_ctx {
     bool comm_broken = false;                    // a collective ran into its deadline: the communicator is abandoned (no further
                                                  // collective is started, its streams and buffers are not waited for or freed)
     uint64_t gcap = 4096;                        // records per rank the all-gather carries (follows the counts, on all ranks alike)
-    // fz_set_streams: 2 = the younger of two fused searches in flight scans on a stream of its own (FZ_DUAL_STREAM=1 presets it)
-    int streams = sw().dual_stream ? 2 : 1;
+    // fz_set_streams: 2 = the younger of two fused searches in flight scans on a stream of its own
+    int streams = 1;
     double last_gather_ms = 0;                   // host time of the last search's exchange step (all-gather + D2H + parse)
     // multi-device contexts: one host thread per device (enqueue, wait, collect and order its shard), and what the
     // shards of the search being collected left (rows_ready: every shard's rows are ordered, emit_matches only merges)
@@ -533,7 +501,6 @@ int ensure_big(DevState &d, uint64_t cap) {
     HIP_TRY(hipSetDevice(d.device));
     if (d.h_big) { HIP_TRY(hipStreamSynchronize(d.stream)); HIP_TRY(hipHostFree(d.h_big)); d.h_big = nullptr; d.big_cap = 0; }
     HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&d.h_big), cap * sizeof(FzRec), hipHostMallocMapped));
-    HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&d.h_big_dev), d.h_big, 0));
     d.big_cap = cap;
     return FZ_OK;
 }
@@ -745,8 +712,17 @@ struct Search {
     uint64_t part_lo = 0, part_hi = ~0ull;
 };
 
-// dynamic LDS per scan workgroup when verification is fused (a function of the switches: fz_debug_reload_switches reaches it)
-#define kFusedLdsBudget ((uint32_t)(sw().fused_lds_kb > 0 ? sw().fused_lds_kb : 64) * 1024u)
+// dynamic LDS per scan workgroup when verification is fused
+constexpr uint32_t kFusedLdsBudget = 64u * 1024u;
+
+// One kernel launch.  Its start / stop events (either may be null) ride on the kernel's own dispatch packet when there are
+// any: no event packets of their own around it.
+template <typename... KArgs, typename... Args>
+void launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, uint32_t lds, hipStream_t st, hipEvent_t ev_start,
+            hipEvent_t ev_stop, Args... args) {
+    if (ev_start || ev_stop) hipExtLaunchKernelGGL(kernel, grid, block, lds, st, ev_start, ev_stop, 0u, args...);
+    else hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
+}
 
 // Fields of FzScanArgs that every kernel of a search shares.
 void fill_common_args(FzScanArgs &fa, const Shard &sh, const Search &q) {
@@ -798,7 +774,6 @@ struct VerifyPlan {
 
 VerifyPlan plan_verify(const Search &q) {
     const bool force_big = sw().force_big_verify;                               // test knob: every stand-alone verification by fz_verify_big_kernel
-    const bool no_wf = sw().no_wavefront;
     VerifyPlan v;
     const uint32_t mpad = (q.m + 15u) & ~15u;
     const uint32_t win_dwords = (q.m + 2 * q.k + 6) / 4 + 1;
@@ -808,7 +783,7 @@ VerifyPlan plan_verify(const Search &q) {
     v.wf_lds = 16 + mpad + 16 + 16 * (size_t)wf_per_wave;                       // 16 waves per workgroup
     while (v.waves > 1 && mpad + v.waves * (size_t)fz_wave_lds_bytes(win_dwords, band_w, 64, false) > 64 * 1024) v.waves >>= 1;
     v.ring_lds = mpad + (size_t)v.waves * fz_wave_lds_bytes(win_dwords, band_w, 64, false);
-    v.want_wf = q.mode == FZ_MODE_LEV && q.k >= 5 && q.k <= 31 && !no_wf;
+    v.want_wf = q.mode == FZ_MODE_LEV && q.k >= 5 && q.k <= 31;
     v.big = force_big || q.m > FZ_MAX_M || q.k > FZ_MAX_K || (v.want_wf ? v.wf_lds > 64 * 1024 : v.ring_lds > 160 * 1024);
     return v;
 }
@@ -856,28 +831,29 @@ void plan_scan_regions(FzScanArgs &fa, uint64_t ntiles, uint64_t grid, uint32_t 
     plan_scan_regions(fa, ntiles, grid, n_cus, steps, fmin, t_per_cu);
 }
 
-// Enqueue scan (+ separate verify when it cannot be fused) for one shard on its device stream.
-// No host synchronisation.
-int enqueue_shard(fz_ctx *ctx, const Shard &sh, const Search &q, bool with_verify, bool copy_back = true) {
-    DevState &d = lane_dev(ctx, sh.dev);
-    HIP_TRY(hipSetDevice(d.device));
-    unsigned long long *counters = reinterpret_cast<unsigned long long *>(d.d_out);
-    FzRec *recs = reinterpret_cast<FzRec *>(d.d_out + kHeaderBytes);
-    const bool no_direct = env_no_direct();
-    // direct mode needs a kernel to publish the counters: an empty buffer launches none
-    const bool snapshot = copy_back && with_verify && q.collective;      // collective search: records stay on the device
-    const bool direct = copy_back && d.direct && !no_direct && !snapshot && sh.geom.buf_len > 0 && !q.plan.s.empty();
-    if (direct && with_verify) recs = reinterpret_cast<FzRec *>(d.h_stage_dev + kHeaderBytes);
-    d.last_direct = direct;
-    d.timed = ctx->timing;
+// What one scan of a shard runs: the grid, the verification form and the sizes that go with them.  The shape fields of
+// FzScanArgs (regions, fused, vlanes, qcap, win_pieces, win_dwords, band_w) are written into the scan's arguments.
+struct ScanPlan {
+    uint64_t ntiles = 0;         // tiles this call scans
+    uint32_t grid = 1;           // workgroups of every scan launch
+    int wfg = 0;                 // the scan kernel's WFG argument (scan_kernel: wf_gw)
+    uint32_t form = FZ_FORM_NONE;   // fz_stats' verify_form
+    uint32_t lds = 0;            // dynamic LDS of a scan workgroup
+    VerifyPlan vp;               // the stand-alone verification (with_verify and not fused)
+};
 
+// Everything that decides what a scan of the shard with geometry `geom` runs: a function of the search, the geometry, the
+// device's CU count and the switches, no device state.
+ScanPlan plan_scan(const Search &q, const FzGeom &geom, uint32_t n_cus, bool with_verify, FzScanArgs &fa) {
+    ScanPlan sp;
     const uint32_t L = q.plan.L;
     const uint32_t G = (uint32_t)q.plan.s.size();
-    const uint64_t ntiles_all = (sh.geom.buf_len + FZ_TILE_BYTES - 1) / FZ_TILE_BYTES;
+    const bool in_memory = geom.seg_stride == 0;
+    const uint64_t ntiles_all = (geom.buf_len + FZ_TILE_BYTES - 1) / FZ_TILE_BYTES;
     const uint64_t tile_lo = std::min<uint64_t>(ntiles_all, q.part_lo / FZ_TILE_BYTES);
     const uint64_t tile_hi = q.part_hi == ~0ull ? ntiles_all : std::min<uint64_t>(ntiles_all, (q.part_hi + FZ_TILE_BYTES - 1) / FZ_TILE_BYTES);
     const bool partial = tile_lo != 0 || tile_hi != ntiles_all;
-    const uint64_t ntiles = tile_hi > tile_lo ? tile_hi - tile_lo : 0;          // tiles this call scans
+    const uint64_t ntiles = sp.ntiles = tile_hi > tile_lo ? tile_hi - tile_lo : 0;
     // Grid: every workgroup strides over ~16 tiles (256 KiB).  Measured on MI355X at 1 GiB: 6 / 8 /
     // 12 / 16 / 20 / 32 / 64 workgroups per CU -> 0.302 / 0.302 / 0.276 / 0.267 / 0.265 / 0.280 /
     // 0.333 ms: several rounds of short workgroups overlap one workgroup's end-of-life verification
@@ -897,11 +873,10 @@ int enqueue_shard(fz_ctx *ctx, const Shard &sh, const Search &q, bool with_verif
     // 3 rounds 0.2062, 6 rounds 0.2074, 8 rounds 0.2104 against 0.2121-0.2146 for 12 tiles (3.56 rounds); 2 GiB, 9 rounds
     // 0.3887 against 0.3989; 512 MiB, 2 rounds 0.1165 against 0.1182.  Long inputs keep 12 tiles per workgroup (4 GiB:
     // 0.7743 against 0.7791-0.7855 for 14-18 whole rounds and 0.802 for 8 tiles: the per-workgroup cost wins there).
-    const int tiles_per_wg_env = sw().tiles_per_wg > 0 ? sw().tiles_per_wg : 0;
-    const int tiles_per_wg = tiles_per_wg_env ? tiles_per_wg_env : 12;
-    const uint64_t resident = (uint64_t)d.n_cus * 6;
-    uint64_t max_grid = std::max<uint64_t>(resident, ntiles / tiles_per_wg);
-    if (!tiles_per_wg_env && ntiles < resident * 120) {
+    constexpr uint64_t kTilesPerWg = 12;
+    const uint64_t resident = (uint64_t)n_cus * 6;
+    uint64_t max_grid = std::max<uint64_t>(resident, ntiles / kTilesPerWg);
+    if (ntiles < resident * 120) {
         const uint64_t rounds = std::max<uint64_t>(1, (2 * ntiles + resident * 19 / 2) / (resident * 19));   // round(ntiles / (9.5 resident))
         max_grid = resident * rounds;
     }
@@ -912,52 +887,34 @@ int enqueue_shard(fz_ctx *ctx, const Shard &sh, const Search &q, bool with_verif
     //  the scan's loop (cannot shorten what the tickets bound); workgroups of 6 tiles (0.31 ms: twice the tickets); the shard
     //  words spread over four lines of the header (every scan slower — 1 GiB exact search 0.188-0.193 -> 0.197 ms, same
     //  box: those lines also hold the statistics words).)
-    {   // lab knobs: FZ_ROUNDS=r -> a grid of r x (FZ_WG_PER_CU workgroups per CU): whole rounds of resident workgroups
-        const int rounds = sw().rounds;
-        const int per_cu = sw().wg_per_cu > 0 ? sw().wg_per_cu : 6;
-        if (rounds > 0) max_grid = (uint64_t)d.n_cus * per_cu * rounds;
-    }
     // the queue codes carry a bounded per-workgroup tile iteration
     const uint64_t min_grid = (ntiles + FZ_TITER_MAX - 1) / FZ_TITER_MAX;
-    dim3 grid((unsigned)std::max<uint64_t>(std::max<uint64_t>(1, min_grid), std::min<uint64_t>(ntiles, max_grid)));
-
-    FzScanArgs fa;
-    fill_common_args(fa, sh, q);
+    sp.grid = (uint32_t)std::max<uint64_t>(std::max<uint64_t>(1, min_grid), std::min<uint64_t>(ntiles, max_grid));
     // Tapered last round: workgroups start in blockIdx order, so the last resident round of a launch starts while the
     // machine is still full and — with equal shares — ends one workgroup life (~60 us) after the grid ran dry, the chip
     // draining all the while (device stamps of every workgroup, benchmarks/lab_scan_phases.py: residency falls linearly from
     // 1 792 to 0 over the last 60 us of a 1 GiB launch).  The last `resident` workgroups therefore take shrinking shares
     // (kTaperSteps groups, down to kTaperMin of a full share) of their own tile range at the end of the buffer, the others
     // correspondingly more.
-    plan_scan_regions(fa, ntiles, grid.x, (uint32_t)d.n_cus);
+    plan_scan_regions(fa, ntiles, sp.grid, n_cus);
     if (partial) {                                               // one region: the call's tiles, no taper
         fa.nreg = 1;
-        fa.reg_wg0[0] = 0; fa.reg_nwg[0] = grid.x; fa.reg_tile0[0] = tile_lo; fa.reg_end[0] = tile_hi;
+        fa.reg_wg0[0] = 0; fa.reg_nwg[0] = sp.grid; fa.reg_tile0[0] = tile_lo; fa.reg_end[0] = tile_hi;
     }
-    if (q.mode == FZ_MODE_GENERIC && !with_verify) fa.gen_dedup = d.gen_dedup_arg;      // the scan fills the window table (run_generic)
+
     const bool force_big = sw().force_big_verify;
-    const VerifyPlan vp = plan_verify(q);
-    {
-        int rc = stage_pattern(d, fa, q.p, q.m, with_verify && vp.big);
-        if (rc) return rc;
-    }
-    const HashGeom hgeom(L);
-    const int nwin = hgeom.nwin, dh = hgeom.dh;
-    fa.d2 = nwin == 2 ? std::min<uint32_t>(L, 8) - 4 : 0;
-    fa.mask1 = hgeom.mask1;
-    fa.mask2 = 0xffffffffu;
+    sp.vp = plan_verify(q);
+    const VerifyPlan &vp = sp.vp;
     fa.band_w = q.mode == FZ_MODE_LEV ? 2 * q.k + 2 : 0;
     fa.win_dwords = (q.m + 2 * q.k + 6) / 4 + 1;
-    fa.hit_cap = d.hit_cap;
-    fa.rec_cap = direct ? kHostRecs : d.rec_cap;
     const uint32_t mpad = (q.m + 15u) & ~15u;
     // Lanes that verify at once: all 64 while the staged windows stay small; fewer for long patterns
     // so that the scan keeps ~8 workgroups per CU resident (measured at m = 64, k = 5 on 1 GiB of text:
     // 64 lanes -> 31.6 KB LDS, 5 workgroups/CU, scan 0.540 ms; candidates are rare there anyway).
-    const uint32_t target = (uint32_t)(sw().fused_target_kb > 0 ? sw().fused_target_kb : 18) * 1024u;
+    constexpr uint32_t target = 18u * 1024u;
     fa.vlanes = 64;
     uint32_t fused_lds;
-    if (sh.geom.seg_stride == 0) {
+    if (in_memory) {
         // in-memory search: the windows of queued candidates are prefetched by LDS-DMA, 16-byte pieces, one slot
         // per queue entry (fz_prefetch_windows); the queue shrinks for long patterns (a tile that outgrows it is
         // re-scanned by enumeration, 64 entries at a time: 64 is the floor)
@@ -999,12 +956,15 @@ int enqueue_shard(fz_ctx *ctx, const Shard &sh, const Search &q, bool with_verif
     // queue discipline takes (more than ~16 candidates per tile and wave: short DNA patterns), the headline workload
     // (k = 2, 3 per tile) keeps the band.
     const bool bits_budget = q.k >= (uint32_t)sw().bits_min_k || per_tile > 16.0;
-    if (q.mode == FZ_MODE_LEV && with_verify && !force_big && !sw().no_bits && sh.geom.seg_stride == 0 && bits_budget &&
+    // fz_verify_lev_bits packs its running minimum as (score << 8) | columns_left: windows of at most 255 columns.  The gate's
+    // whole-piece bound win_pieces * 16 + 16 <= FZ_PAD_BACK (with m <= 128) keeps every window at m + 2k + 3 <= 240 columns.
+    static_assert(FZ_PAD_BACK - 16 <= 255, "fz_verify_lev_bits: window columns in 8 bits");
+    if (q.mode == FZ_MODE_LEV && with_verify && !force_big && !sw().no_bits && in_memory && bits_budget &&
         q.m <= FZ_BITS_MAX_M(2) && q.k <= FZ_MAX_K && fa.win_pieces * 16u + 16u <= FZ_PAD_BACK) {
         bits_nw = q.m <= FZ_BITS_MAX_M(4) ? 4 : q.m <= FZ_BITS_MAX_M(1) ? 1 : 2;      // 32-, 64-, 128-bit columns
         // (26 KB: six workgroups per CU.  Measured on 1 GiB of DNA, m = 54, k = 8, 2.4e6 candidates: 64 / 96 / 128 / 160 entries
         //  per wave = 26 / 37 / 47 / 58 KB -> 0.463 / 0.517 / 0.656 / 0.830 ms: fuller passes do not pay for the lost waves)
-        const uint32_t budget = (uint32_t)(sw().bits_lds_kb > 0 ? sw().bits_lds_kb : 26) * 1024u;
+        constexpr uint32_t budget = 26u * 1024u;
         const uint32_t fixed = mpad + FZ_TABLE_BYTES + FZ_PEQ_BYTES(bits_nw);
         // Queue entries per wave: one full pass (64) + twice the expected candidates per tile, within the LDS budget.
         uint32_t qc = sw().bits_qcap > 0 ? (uint32_t)sw().bits_qcap
@@ -1019,7 +979,7 @@ int enqueue_shard(fz_ctx *ctx, const Shard &sh, const Search &q, bool with_verif
     // taken in block-range passes — instead of round 1's (half-full queues; a tile that overflows is enumerated: DNA, m = 20,
     // 4 substitutions: 14 ms per GiB; m = 12, 3: 45 ms).
     bool adapt_plain = false;
-    if (!bits_nw && fa.fused && sh.geom.seg_stride == 0 && with_verify && !sw().no_bits && per_tile > 16.0 && q.mode == FZ_MODE_SUBS) {
+    if (!bits_nw && fa.fused && in_memory && with_verify && !sw().no_bits && per_tile > 16.0 && q.mode == FZ_MODE_SUBS) {
         const uint32_t fixed = mpad + FZ_TABLE_BYTES;
         uint32_t qc = sw().bits_qcap > 0 ? (uint32_t)sw().bits_qcap : (uint32_t)std::min(512.0, 64.0 + 32.0 * std::ceil(2.0 * per_tile / 32.0));
         while (qc > 64u && fixed + FZ_WAVES_PER_BLOCK * fz_wave_lds_pref_bytes(qc, fa.win_pieces) > target + 4096) qc -= 32u;
@@ -1037,16 +997,56 @@ int enqueue_shard(fz_ctx *ctx, const Shard &sh, const Search &q, bool with_verif
     // are not (DNA, m = 100, k = 10, 4.5e4 candidates: 0.551 against 0.687 ms; m = 54, k = 8, 2.4e6: 2.70 against 20.7 ms —
     // the hit list outgrows its buffer and the search runs twice).  FZ_WF32=0 / 1 pins the choice.
     const int wf32_env = sw().wf32;
-    const bool wf_candidate = !bits_nw && !fa.fused && sh.geom.seg_stride == 0 && with_verify && !force_big && !no_wf_fuse && vp.want_wf && !vp.big && vp.gw <= 32 &&
+    const bool wf_candidate = !bits_nw && !fa.fused && in_memory && with_verify && !force_big && !no_wf_fuse && vp.want_wf && !vp.big && vp.gw <= 32 &&
                               q.m <= FZ_MAX_M && wf_fused_lds <= target + 4096;
-    d.wf32_candidate = wf_candidate && vp.gw == 32;
     // (round 6: patterns up to 128 characters never get here — bit-vector columns; for the longer ones the choice follows the
     //  expected density per_tile above, a function of the pattern — the measured crossover, 1.5e4 .. 4.5e4 candidates per GiB, is
     //  ~0.1 per tile and wave — not, as in rounds 4 and 5, what the context's previous search saw)
     const bool wf_fused = wf_candidate && (vp.gw == 16 || (wf32_env >= 0 ? wf32_env != 0 : per_tile > 0.1));
     if (wf_fused) { fa.fused = 1u; fused_lds = wf_fused_lds; fa.vlanes = 64; }
+    sp.wfg = bits_nw ? bits_nw : adapt_plain ? 3 : wf_fused ? vp.gw : 0;
+    sp.form = !with_verify ? FZ_FORM_NONE : bits_nw == 4 ? FZ_FORM_FUSED_BITS32 : bits_nw == 1 ? FZ_FORM_FUSED_BITS1 : bits_nw == 2 ? FZ_FORM_FUSED_BITS2
+              : wf_fused ? FZ_FORM_FUSED_CELLS : fa.fused ? FZ_FORM_FUSED_BAND : FZ_FORM_KERNEL;
     // (the hit-emitting form keeps no pattern in LDS: fz_confirm reads it from the argument block / HBM)
-    const uint32_t scan_lds = fa.fused ? fused_lds : FZ_TABLE_BYTES + FZ_WAVES_PER_BLOCK * fz_wave_lds_bytes(0, 0, 64, true);
+    sp.lds = fa.fused ? fused_lds : FZ_TABLE_BYTES + FZ_WAVES_PER_BLOCK * fz_wave_lds_bytes(0, 0, 64, true);
+    return sp;
+}
+
+// Enqueue scan (+ separate verify when it cannot be fused) for one shard on its device stream, as plan_scan decided.
+// No host synchronisation.
+int enqueue_shard(fz_ctx *ctx, const Shard &sh, const Search &q, bool with_verify, bool copy_back = true) {
+    DevState &d = lane_dev(ctx, sh.dev);
+    HIP_TRY(hipSetDevice(d.device));
+    unsigned long long *counters = reinterpret_cast<unsigned long long *>(d.d_out);
+    FzRec *recs = reinterpret_cast<FzRec *>(d.d_out + kHeaderBytes);
+    const bool no_direct = env_no_direct();
+    // direct mode needs a kernel to publish the counters: an empty buffer launches none
+    const bool snapshot = copy_back && with_verify && q.collective;      // collective search: records stay on the device
+    const bool direct = copy_back && d.direct && !no_direct && !snapshot && sh.geom.buf_len > 0 && !q.plan.s.empty();
+    if (direct && with_verify) recs = reinterpret_cast<FzRec *>(d.h_stage_dev + kHeaderBytes);
+    d.last_direct = direct;
+    d.timed = ctx->timing;
+
+    FzScanArgs fa;
+    fill_common_args(fa, sh, q);
+    const ScanPlan sp = plan_scan(q, sh.geom, (uint32_t)d.n_cus, with_verify, fa);
+    const VerifyPlan &vp = sp.vp;
+    const uint32_t L = q.plan.L;
+    const uint32_t G = (uint32_t)q.plan.s.size();
+    const uint64_t ntiles = sp.ntiles;
+    const dim3 grid(sp.grid);
+    if (q.mode == FZ_MODE_GENERIC && !with_verify) fa.gen_dedup = d.gen_dedup_arg;      // the scan fills the window table (run_generic)
+    {
+        int rc = stage_pattern(d, fa, q.p, q.m, with_verify && vp.big);
+        if (rc) return rc;
+    }
+    const HashGeom hgeom(L);
+    const int nwin = hgeom.nwin, dh = hgeom.dh;
+    fa.d2 = nwin == 2 ? std::min<uint32_t>(L, 8) - 4 : 0;
+    fa.mask1 = hgeom.mask1;
+    fa.mask2 = 0xffffffffu;
+    fa.hit_cap = d.hit_cap;
+    fa.rec_cap = direct ? kHostRecs : d.rec_cap;
     // the stream and the counter block of this search (see DevState::stream_alt)
     const bool alt = ctx->streams == 2 && d.slot_id == 1 && fa.fused && direct && copy_back && !fa.pat_g && sh.geom.seg_stride == 0;
     const hipStream_t st = alt ? d.stream_alt : d.stream;
@@ -1057,14 +1057,13 @@ int enqueue_shard(fz_ctx *ctx, const Shard &sh, const Search &q, bool with_verif
     }
 
     // When the scan's last launch is also the search's last kernel (fused verification, results written straight to
-    // the host), the start / completion events ride on the kernels' own dispatch packets (hipExtLaunchKernelGGL)
+    // the host), the start / completion events ride on the kernels' own dispatch packets (launch)
     // instead of two extra packets around them: fewer packets on the critical path of a synchronous call, and
     // filter_ms becomes the kernels' own span.
-    const bool no_ext = sw().no_ext_launch;
-    const bool ext_events = !no_ext && copy_back && direct && !(with_verify && !fa.fused) && ntiles > 0 && G > 0;
+    const bool ext_events = copy_back && direct && !(with_verify && !fa.fused) && ntiles > 0 && G > 0;
     // ... and whenever the scan launches a kernel at all, its start / end events (ev[0], ev[1]: fz_stats' filter_ms) ride
     // on the first / last launch as well instead of two packets of their own in front of and behind the scan
-    const bool attach = !no_ext && ntiles > 0 && G > 0;
+    const bool attach = ntiles > 0 && G > 0;
     if (ctx->timing && !attach) HIP_TRY(hipEventRecord(d.ev[0], st));
     uint32_t launches = 0;
     for (uint32_t g0 = 0; g0 < G && ntiles > 0;) {
@@ -1093,17 +1092,11 @@ int enqueue_shard(fz_ctx *ctx, const Shard &sh, const Search &q, bool with_verif
         for (uint32_t b = 1; b < nblk; ++b)
             for (uint32_t c = 0; c < b; ++c)
                 if (fa.H[b] == fa.H[c]) fa.flags |= FZ_FLAG_DUP_HASHES;
-        ScanKernel kern = scan_kernel(nwin, dh, fa.fused != 0, sh.geom.seg_stride != 0, fa.lut_shift == 2, bits_nw ? bits_nw : adapt_plain ? 3 : wf_fused ? vp.gw : 0);
+        ScanKernel kern = scan_kernel(nwin, dh, fa.fused != 0, sh.geom.seg_stride != 0, fa.lut_shift == 2, sp.wfg);
         if (!kern) return fail(FZ_EUNSUPPORTED, "this (lab) build carries no scan kernel for nwin=%d dh=%d", nwin, dh);
-        const uint32_t extra_lds = (uint32_t)sw().extra_lds_kb * 1024u;
         hipEvent_t ev_start = (attach && ctx->timing && g0 == 0) ? d.ev[0] : nullptr;
         hipEvent_t ev_stop = g0 + nblk >= G ? (ext_events ? d.ev[3] : (attach && ctx->timing) ? d.ev[1] : nullptr) : nullptr;
-        if (ev_start || ev_stop)
-            hipExtLaunchKernelGGL(kern, grid, dim3(FZ_FILTER_THREADS), scan_lds + extra_lds, st, ev_start, ev_stop, 0u, sh.d_buf, fa,
-                                  ntiles, d.d_hits, recs, counters);
-        else
-            hipLaunchKernelGGL(kern, grid, dim3(FZ_FILTER_THREADS), scan_lds + extra_lds, st, sh.d_buf, fa, ntiles, d.d_hits, recs,
-                               counters);
+        launch(kern, grid, dim3(FZ_FILTER_THREADS), sp.lds, st, ev_start, ev_stop, sh.d_buf, fa, ntiles, d.d_hits, recs, counters);
         HIP_TRY(hipGetLastError());
         ++launches;
         g0 += nblk;
@@ -1116,51 +1109,46 @@ int enqueue_shard(fz_ctx *ctx, const Shard &sh, const Search &q, bool with_verif
     d.verify_end_event = 2;
     // the verification kernel is the search's last one when its records go straight to the host: then the completion
     // event rides on its launch (no ev[2] / ev[3] packets behind it; the verify span is ev[1] .. ev[3])
-    hipEvent_t v_stop = (!no_ext && copy_back && direct && !snapshot) ? d.ev[3] : nullptr;
-#define FZ_LAUNCH_VERIFY(kernel, grid_, block_, lds_)                                                                      \
-    do {                                                                                                                   \
-        if (v_stop) hipExtLaunchKernelGGL(kernel, grid_, block_, lds_, d.stream, nullptr, v_stop, 0u, sh.d_buf, fa, d.d_hits, recs, counters); \
-        else hipLaunchKernelGGL(kernel, grid_, block_, lds_, d.stream, sh.d_buf, fa, d.d_hits, recs, counters);            \
-    } while (0)
+    hipEvent_t v_stop = (copy_back && direct && !snapshot) ? d.ev[3] : nullptr;
     if (with_verify && !fa.fused && ntiles > 0 && G > 0) {
         d.verify_launched = true;
         if (v_stop) d.verify_end_event = 3;
         fa.nblk = 0;
         fa.g0 = 0;
         fa.host_hdr = direct ? reinterpret_cast<uint64_t>(d.h_stage_dev) : 0;
-        const int gw = vp.gw;
-        const size_t wf_lds = vp.wf_lds, ring_lds = vp.ring_lds;
-        const unsigned waves = vp.waves;
-        const bool want_wf = vp.want_wf, big = vp.big;
-        if (big) {
+        using VerifyKernel = void (*)(const uint8_t *, const FzScanArgs, const uint64_t *, FzRec *, unsigned long long *);
+        VerifyKernel vk;
+        dim3 vgrid, vblock;
+        size_t vlds;
+        if (vp.big) {
             if (!fa.pat_g) return fail(FZ_EDEVICE, "internal: the pattern was not staged for the big verification");
             const uint32_t cells = q.mode == FZ_MODE_LEV ? 2 * q.k + 1 : 1;
-            const dim3 bgrid(d.n_cus * 32), bblock(64);
-            if (cells <= 64) FZ_LAUNCH_VERIFY(fz_verify_big_kernel<1>, bgrid, bblock, 0);
-            else if (cells <= 128) FZ_LAUNCH_VERIFY(fz_verify_big_kernel<2>, bgrid, bblock, 0);
-            else if (cells <= 256) FZ_LAUNCH_VERIFY(fz_verify_big_kernel<4>, bgrid, bblock, 0);
-            else if (cells <= 512) FZ_LAUNCH_VERIFY(fz_verify_big_kernel<8>, bgrid, bblock, 0);
-            else if (cells <= 1024) FZ_LAUNCH_VERIFY(fz_verify_big_kernel<16>, bgrid, bblock, 0);
-            else FZ_LAUNCH_VERIFY(fz_verify_big_kernel<32>, bgrid, bblock, 0);
-        } else if (want_wf) {
+            if (cells <= 64) vk = fz_verify_big_kernel<1>;
+            else if (cells <= 128) vk = fz_verify_big_kernel<2>;
+            else if (cells <= 256) vk = fz_verify_big_kernel<4>;
+            else if (cells <= 512) vk = fz_verify_big_kernel<8>;
+            else if (cells <= 1024) vk = fz_verify_big_kernel<16>;
+            else vk = fz_verify_big_kernel<32>;
+            vgrid = dim3(d.n_cus * 32); vblock = dim3(64); vlds = 0;
+        } else if (vp.want_wf) {
             // lane-per-cell: 64 / gw candidates per wave, one contiguous byte window per candidate
-            fa.gw = (uint32_t)gw;
+            fa.gw = (uint32_t)vp.gw;
+            if (vp.gw == 16) vk = fz_verify_wf_kernel<16>;
+            else if (vp.gw == 32) vk = fz_verify_wf_kernel<32>;
+            else vk = fz_verify_wf_kernel<64>;
             // 16 waves per workgroup: few workgroups = few finish tickets (every ticket is an atomic on one word)
-            const dim3 vgrid(d.n_cus * 2), vblock(1024);
-            if (gw == 16) FZ_LAUNCH_VERIFY(fz_verify_wf_kernel<16>, vgrid, vblock, wf_lds);
-            else if (gw == 32) FZ_LAUNCH_VERIFY(fz_verify_wf_kernel<32>, vgrid, vblock, wf_lds);
-            else FZ_LAUNCH_VERIFY(fz_verify_wf_kernel<64>, vgrid, vblock, wf_lds);
+            vgrid = dim3(d.n_cus * 2); vblock = dim3(1024); vlds = vp.wf_lds;
         } else {
             // LDS: pattern + per-wave window and score ring; the block was shrunk until it fits.
             fa.vlanes = 64;
-            if (ring_lds > 64 * 1024)
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(fz_verify_kernel),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)ring_lds));
-            FZ_LAUNCH_VERIFY(fz_verify_kernel, dim3(d.n_cus * 4), dim3(64 * waves), ring_lds);
+            vk = fz_verify_kernel;
+            if (vp.ring_lds > 64 * 1024)
+                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(vk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)vp.ring_lds));
+            vgrid = dim3(d.n_cus * 4); vblock = dim3(64 * vp.waves); vlds = vp.ring_lds;
         }
+        launch(vk, vgrid, vblock, (uint32_t)vlds, d.stream, nullptr, v_stop, sh.d_buf, fa, d.d_hits, recs, counters);
         HIP_TRY(hipGetLastError());
     }
-#undef FZ_LAUNCH_VERIFY
     const bool completion_attached = ext_events || (d.verify_launched && v_stop);
     if (copy_back) {
         if (d.verify_launched && ctx->timing && d.verify_end_event == 2) HIP_TRY(hipEventRecord(d.ev[2], d.stream));
@@ -1185,8 +1173,7 @@ int enqueue_shard(fz_ctx *ctx, const Shard &sh, const Search &q, bool with_verif
     }
     d.launches_used = launches;                  // (summed by search_enqueue: this may run on the device's worker thread)
     d.fused_used = fa.fused != 0;
-    d.form_used = !with_verify ? FZ_FORM_NONE : bits_nw == 4 ? FZ_FORM_FUSED_BITS32 : bits_nw == 1 ? FZ_FORM_FUSED_BITS1 : bits_nw == 2 ? FZ_FORM_FUSED_BITS2
-                  : wf_fused ? FZ_FORM_FUSED_CELLS : fa.fused ? FZ_FORM_FUSED_BAND : FZ_FORM_KERNEL;
+    d.form_used = sp.form;
     d.hit_cap_used = d.hit_cap;
     d.rec_cap_used = d.rec_cap;
     return FZ_OK;
@@ -1499,7 +1486,6 @@ int search_enqueue(fz_ctx *ctx, fz_seq *seq, const Search &q, bool with_verify) 
         const DevState &d = lane_dev(ctx, sh.dev);
         ctx->stats.filter_launches += d.launches_used;
         ctx->stats.verify_form = d.form_used;
-        ctx->last_fused = d.fused_used;
     }
     return FZ_OK;
 }
@@ -1592,6 +1578,42 @@ int run_search(fz_ctx *ctx, fz_seq *seq, const Search &q, bool with_verify, std:
     return search_collect(ctx, seq, q, with_verify, recs, hits);
 }
 
+// fz_gen_hit_kernel's form for a generic search with `cand_cap` candidate slots per list.
+using GhKernel = void (*)(const uint8_t *, const FzScanArgs, const uint64_t *, FzGenRec *, unsigned long long *);
+struct GenHitPlan {
+    GhKernel kernel;
+    bool bits;                   // the bit-parallel form
+    uint32_t waves;              // waves per hit
+    uint32_t capw;               // slots per list of one wave
+    size_t lds;
+};
+
+GenHitPlan plan_gen_hit(const Search &q, uint32_t cand_cap) {
+    GenHitPlan g;
+    const uint32_t mpad = (q.m + 15u) & ~15u, wpad = (q.m + 2 * q.k + 15u) & ~15u;
+    // the bit-parallel form (fz_gen_hit_kernel<W, true>: 64-bit equality words, flags as words, unconditional stores):
+    // patterns of at most 64 characters and budgets of at most 32.  FZ_GH_NO_BITS=1: the round-4 step (A/B, tests);
+    // FZ_GH_WAVES=1 / 2 / 4: waves per hit.  Default with the bit-parallel form: ONE — measured in round 5 (profiles/
+    // r05_generic_kernels.txt): a hit's time is ~1 500 cycles per window character that has candidates, whatever the
+    // number of waves or of slices per trip (the big tree of a true occurrence belongs to one start, and the per-character
+    // cost is the dependent chain of one trip), so more waves per hit only cost residency; 2 otherwise (round 4)
+    // fz_gen_hit_kernel<W, true>'s implicit bounds, held HERE: one 64-bit equality word per window character (m <= 64),
+    // the equality words of a window in two register pairs (m + 2k <= 128), skip counts in 32 bits (k <= 32), counters
+    // below 2^31 (limits <= FZ_MAX_K = 255); anything else takes round 4's step
+    static_assert(FZ_MAX_K < (1u << 31), "fz_b_lt / fz_b_eq operands");
+    g.bits = q.m <= 64u && q.k <= 32u && q.m >= 1u && q.m + 2u * q.k <= 128u &&
+             std::max(std::max(q.max_subs, q.max_ins), std::max(q.max_dels, q.k)) <= FZ_MAX_K && !sw().gh_no_bits;
+    const uint32_t env = (uint32_t)sw().gh_waves;
+    g.waves = env == 4u || env == 2u || (env == 1u && g.bits) ? env : g.bits ? 1u : 2u;
+    g.capw = g.waves == 1u ? std::max<uint32_t>(64u, cand_cap) : std::max<uint32_t>(64u, cand_cap / 2u);
+    g.lds = (size_t)mpad + wpad + FZ_GH_CTL_BYTES + (size_t)g.waves * 2u * g.capw * sizeof(FzGCand) +
+            (size_t)g.waves * FZ_GH_MCAP_W(g.waves) * 8u +
+            (g.bits ? (size_t)FZ_GH_PT_BYTES + (size_t)wpad * 8u + (size_t)64u * g.waves * 8u : 0u);
+    g.kernel = g.bits ? (g.waves == 1u ? fz_gen_hit_kernel<1, true> : g.waves == 2u ? fz_gen_hit_kernel<2, true> : fz_gen_hit_kernel<4, true>)
+                      : (g.waves == 4u ? fz_gen_hit_kernel<4, false> : fz_gen_hit_kernel<2, false>);
+    return g;
+}
+
 // Generic search: scan (emit exact hits) -> fz_generic_kernel (one wave per hit) -> records.
 // Re-runs with larger buffers on overflow: hit list, record list, then candidate lists.
 // `phase`: 0 = the whole search; 1 = launch only (fz_generic_ngrams_begin: the kernels of the first attempt are enqueued on
@@ -1626,11 +1648,11 @@ int run_generic(fz_ctx *ctx, fz_seq *seq, const Search &q, std::vector<FzGenRec>
             // once per window (fz_device.h: FzGenDedup; the scan fills the table as it lists the hits).  Where the rows are
             // finished on the device, where only (hull, best) pairs leave it, and for the flag-only search;
             // FZ_GEN_NO_DEDUP=1: every hit on its own (A/B, tests).
-            const bool no_dedup = sw().gen_no_dedup;
-            const bool gen_direct0 = sw().gen_direct, host_order0 = sw().gen_host_order;
-            const bool dev_order0 = !gen_direct0 && !host_order0 && !q.any && !q.fold && seq->shards.size() == 1 && sh.geom.seg_stride == 0 &&
-                                    !comm_multi_process(ctx);
-            const bool dedup = !no_dedup && sh.geom.seg_stride == 0 && (dev_order0 || q.fold || q.any);
+            // One shard, no segments: the rows are ordered and finished on the device (fz_gen_order_kernel,
+            // fz_gen_scatter_kernel) and cross PCIe once, straight into the caller's buffer; the host's run ordering
+            // (emit_generic) serves searches with more than FZ_GEN_ORDER_MAX hits, several shards and the file API's segments.
+            const bool dev_order = !q.any && !q.fold && seq->shards.size() == 1 && sh.geom.seg_stride == 0 && !comm_multi_process(ctx);
+            const bool dedup = !sw().gen_no_dedup && sh.geom.seg_stride == 0 && (dev_order || q.fold || q.any);
             d.dedup_used = dedup;
             d.gen_dedup_arg = 0;
             if (dedup) {
@@ -1661,17 +1683,6 @@ int run_generic(fz_ctx *ctx, fz_seq *seq, const Search &q, std::vector<FzGenRec>
             rc = ensure_big(d, 1u << 16);
             if (rc) return rc;
             fa.hit_cap = d.hit_cap;
-            // Records of the automaton: into the device buffer, fetched with ONE copy once the count is known.
-            // (Round 1 let the kernel store them straight into pinned host memory: 2.1e5 scattered 24-byte stores
-            // cross PCIe at ~10 GB/s and the kernel cannot finish before they have drained — 0.49 ms for a kernel
-            // whose work takes a fraction of that; FZ_GEN_DIRECT=1 restores that path.)
-            const bool gen_direct = sw().gen_direct;
-            // One shard, no segments: the rows are ordered and finished on the device (fz_gen_order_kernel,
-            // fz_gen_scatter_kernel) and cross PCIe once, straight into the caller's buffer; FZ_GEN_HOST_ORDER=1
-            // keeps the host's run ordering (emit_generic), which also serves searches with more than
-            // FZ_GEN_ORDER_MAX hits, several shards and the file API's segments.
-            const bool host_order = sw().gen_host_order;
-            const bool dev_order = !gen_direct && !host_order && !q.any && !q.fold && seq->shards.size() == 1 && sh.geom.seg_stride == 0 && !comm_multi_process(ctx);
             if (dev_order) {
                 rc = ensure_gen_rows(d);
                 if (rc) return rc;
@@ -1679,116 +1690,72 @@ int run_generic(fz_ctx *ctx, fz_seq *seq, const Search &q, std::vector<FzGenRec>
                 fa.rows_cap = d.gen_rows_cap;
             }
             fa.gen_dedup = d.gen_dedup_arg;
+            // Records of the automaton: into the device buffer, fetched with ONE copy once the count is known.
+            // (Round 1 let the kernel store them straight into pinned host memory: 2.1e5 scattered 24-byte stores
+            // cross PCIe at ~10 GB/s and the kernel cannot finish before they have drained — 0.49 ms for a kernel
+            // whose work takes a fraction of that.)
             // Folded search (a few thousand pairs): the automaton kernel writes them straight into the pinned staging
             // buffer and its last workgroup publishes the counters there, as the fused scan does for its records — no
             // copy command between the kernel and the host (FZ_NO_DIRECT=1, or more pairs than the buffer holds: the copy).
-            const bool no_direct = env_no_direct();
-            const bool fold_direct = q.fold && !gen_direct && !no_direct && d.fold_direct && seq->shards.size() == 1;
+            const bool fold_direct = q.fold && !env_no_direct() && d.fold_direct && seq->shards.size() == 1;
             d.fold_was_direct = fold_direct;
-            fa.rec_cap = gen_direct ? d.big_cap : fold_direct ? kHostRecs : d.rec_cap;
+            fa.rec_cap = fold_direct ? kHostRecs : d.rec_cap;
             if (fold_direct) fa.host_hdr = reinterpret_cast<uint64_t>(d.h_stage_dev);
             unsigned long long *counters = reinterpret_cast<unsigned long long *>(d.d_out);
-            FzGenRec *recs = gen_direct ? reinterpret_cast<FzGenRec *>(d.h_big_dev)
-                           : fold_direct ? reinterpret_cast<FzGenRec *>(d.h_stage_dev + kHeaderBytes)
-                                         : reinterpret_cast<FzGenRec *>(d.d_out + kHeaderBytes);
+            FzGenRec *recs = reinterpret_cast<FzGenRec *>((fold_direct ? d.h_stage_dev : d.d_out) + kHeaderBytes);
             static_assert(sizeof(FzGenRec) == sizeof(FzRec), "the generic records share the record buffer");
-            // fz_gen_hit_kernel: four waves per hit, every wave a quarter of the list (in-memory searches with the lists in LDS)
-            const uint32_t gh_waves_env = (uint32_t)sw().gh_waves;
-            const bool gh_no_bits = sw().gh_no_bits;
-            // the bit-parallel form (fz_gen_hit_kernel<W, true>: 64-bit equality words, flags as words, unconditional stores):
-            // patterns of at most 64 characters and budgets of at most 32.  FZ_GH_NO_BITS=1: the round-4 step (A/B, tests);
-            // FZ_GH_WAVES=1 / 2 / 4: waves per hit.  Default with the bit-parallel form: ONE — measured in round 5 (profiles/
-            // r05_generic_kernels.txt): a hit's time is ~1 500 cycles per window character that has candidates, whatever the
-            // number of waves or of slices per trip (the big tree of a true occurrence belongs to one start, and the per-character
-            // cost is the dependent chain of one trip), so more waves per hit only cost residency; 2 otherwise (round 4)
-            // fz_gen_hit_kernel<W, true>'s implicit bounds, held HERE: one 64-bit equality word per window character (m <= 64),
-            // the equality words of a window in two register pairs (m + 2k <= 128), skip counts in 32 bits (k <= 32), counters
-            // below 2^31 (limits <= FZ_MAX_K = 255); anything else takes round 4's step
-            static_assert(FZ_MAX_K < (1u << 31), "fz_b_lt / fz_b_eq operands");
-            const bool gh_bits = q.m <= 64u && q.k <= 32u && q.m >= 1u && q.m + 2u * q.k <= 128u &&
-                                 std::max(std::max(q.max_subs, q.max_ins), std::max(q.max_dels, q.k)) <= FZ_MAX_K && !gh_no_bits;
-            const uint32_t gh_waves = gh_waves_env == 4u || gh_waves_env == 2u || (gh_waves_env == 1u && gh_bits) ? gh_waves_env : gh_bits ? 1u : 2u;
-            const uint32_t capw = gh_waves == 1u ? std::max<uint32_t>(64u, cand_cap) : std::max<uint32_t>(64u, cand_cap / 2u);   // slots per list of one wave
-            const size_t lds_multi = (size_t)mpad + wpad + FZ_GH_CTL_BYTES + (size_t)gh_waves * 2u * capw * sizeof(FzGCand) +
-                                     (size_t)gh_waves * FZ_GH_MCAP_W(gh_waves) * 8u +
-                                     (gh_bits ? (size_t)FZ_GH_PT_BYTES + (size_t)wpad * 8u + (size_t)64u * gh_waves * 8u : 0u);
-            using GhKernel = void (*)(const uint8_t *, const FzScanArgs, const uint64_t *, FzGenRec *, unsigned long long *);
-            const GhKernel gh = gh_bits ? (gh_waves == 1u ? fz_gen_hit_kernel<1, true> : gh_waves == 2u ? fz_gen_hit_kernel<2, true> : fz_gen_hit_kernel<4, true>)
-                                        : (gh_waves == 4u ? fz_gen_hit_kernel<4, false> : fz_gen_hit_kernel<2, false>);
-            const bool multi = ctx->gen_multi && !legacy_now && scratch == 0 && sh.geom.seg_stride == 0 && lds_multi <= 160 * 1024;
+            const GenHitPlan gp = plan_gen_hit(q, cand_cap);
+            const bool multi = ctx->gen_multi && !legacy_now && scratch == 0 && sh.geom.seg_stride == 0 && gp.lds <= 160 * 1024;
             d.gen_multi_used = multi;
             if (multi) {
-                fa.cand_cap = capw;
-                if (lds_multi > 64 * 1024)
-                    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(gh), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_multi));
+                fa.cand_cap = gp.capw;
+                if (gp.lds > 64 * 1024)
+                    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(gp.kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gp.lds));
             }
+            const LpKernel lp = lp_kernel(FZ_LP_GENERIC_HIT, scratch != 0);
             if (lds > 64 * 1024)
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(lp_kernel(FZ_LP_GENERIC_HIT, scratch != 0)),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            const unsigned grid_per_cu = (unsigned)sw().lp_grid_per_cu;   // lab knob
+                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(lp), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             // (measured on configs[3b], 6144 hits: 16 / 24 / 32 workgroups per CU with 512-entry match buffers 0.325 /
             //  0.310 / 0.310 ms, with 128-entry ones 0.325 / 0.303 / 0.304 ms — once every hit is resident the kernel
             //  takes as long as its slowest hit)
-            // (Lab knob FZ_GEN_HI_STREAM=1, measured and NOT the default: for a search in flight next to another one,
-            // everything behind the scan on a HIGH-priority stream of the lane, so that the automaton's waves take the
-            // slots the other lane's scan frees instead of waiting behind its grid.  configs[3b], two in flight: 0.364 ms
-            // per search against 0.310 ms with the automaton on the lane's own low-priority stream — the automaton's
-            // 4 171 waves then hold their CUs' registers for 160 us and the scan, which is what bounds the pair, starves.)
-            const bool use_hi = sw().gen_hi_stream;
-            hipStream_t st2 = d.stream;
-            if (phase == 1 && use_hi) {
-                if (!d.stream_hi) {
-                    int prio_least = 0, prio_greatest = 0;
-                    HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-                    HIP_TRY(hipStreamCreateWithPriority(&d.stream_hi, hipStreamNonBlocking, prio_greatest));
-                    HIP_TRY(hipEventCreateWithFlags(&d.ev_scan_done, hipEventDisableTiming));
-                }
-                HIP_TRY(hipEventRecord(d.ev_scan_done, d.stream));
-                HIP_TRY(hipStreamWaitEvent(d.stream_hi, d.ev_scan_done, 0));
-                st2 = d.stream_hi;
-            }
+            constexpr unsigned kLpGridPerCu = 24;
+            // (configs[3b]: 16 -> 0.130 ms, 32 -> 0.104: every hit of the search needs a workgroup of its own)
+            constexpr unsigned kGenHitGridPerCu = 32;
+            // (Measured and NOT kept: for a search in flight next to another one, everything behind the scan on a HIGH-priority
+            // stream of the lane, so that the automaton's waves take the slots the other lane's scan frees instead of waiting
+            // behind its grid.  configs[3b], two in flight: 0.364 ms per search against 0.310 ms with the automaton on the
+            // lane's own low-priority stream — the automaton's 4 171 waves then hold their CUs' registers for 160 us and the
+            // scan, which is what bounds the pair, starves.)
             // the automaton's end event rides on its own launch; for a folded search in direct mode that event is also
             // the search's completion (ev[3]): no event packet of its own anywhere in such a search
-            const bool no_ext = sw().no_ext_launch;
-            hipEvent_t lp_stop = no_ext ? nullptr : fold_direct ? d.ev[3] : ctx->timing ? d.ev[2] : nullptr;
+            hipEvent_t lp_stop = fold_direct ? d.ev[3] : ctx->timing ? d.ev[2] : nullptr;
             d.lp_end_event = fold_direct ? 3 : 2;
-            const unsigned multi_per_cu_env = (unsigned)sw().gh_grid_per_cu;
-            const unsigned multi_per_cu = multi_per_cu_env ? multi_per_cu_env : 32u;   // lab knob (configs[3b]: 16 -> 0.130 ms, 32 -> 0.104: every hit of the search needs a workgroup of its own)
-            if (multi && lp_stop)
-                hipExtLaunchKernelGGL(gh, dim3(d.n_cus * multi_per_cu), dim3(64 * gh_waves), lds_multi, st2, nullptr, lp_stop, 0u,
-                                      sh.d_buf, fa, d.d_hits, recs, counters);
-            else if (multi)
-                hipLaunchKernelGGL(gh, dim3(d.n_cus * multi_per_cu), dim3(64 * gh_waves), lds_multi, st2, sh.d_buf, fa, d.d_hits,
-                                   recs, counters);
-            else if (lp_stop)
-                hipExtLaunchKernelGGL(lp_kernel(FZ_LP_GENERIC_HIT, scratch != 0), dim3(scratch ? kCandScratchGrid : d.n_cus * grid_per_cu),
-                                      dim3(64), lds, st2, nullptr, lp_stop, 0u, sh.d_buf, fa, d.d_hits, (uint64_t)0, recs, counters);
+            if (multi)
+                launch(gp.kernel, dim3(d.n_cus * kGenHitGridPerCu), dim3(64 * gp.waves), (uint32_t)gp.lds, d.stream, nullptr, lp_stop,
+                       sh.d_buf, fa, d.d_hits, recs, counters);
             else
-                hipLaunchKernelGGL(lp_kernel(FZ_LP_GENERIC_HIT, scratch != 0), dim3(scratch ? kCandScratchGrid : d.n_cus * grid_per_cu), dim3(64),
-                                   lds, st2, sh.d_buf, fa, d.d_hits, (uint64_t)0, recs, counters);
+                launch(lp, dim3(scratch ? kCandScratchGrid : d.n_cus * kLpGridPerCu), dim3(64), (uint32_t)lds, d.stream, nullptr, lp_stop,
+                       sh.d_buf, fa, d.d_hits, (uint64_t)0, recs, counters);
             HIP_TRY(hipGetLastError());
-            if (ctx->timing && !lp_stop && !fold_direct) HIP_TRY(hipEventRecord(d.ev[2], st2));
+            if (ctx->timing && !lp_stop && !fold_direct) HIP_TRY(hipEventRecord(d.ev[2], d.stream));
             if (dev_order) {
-                hipLaunchKernelGGL(fz_gen_order_kernel, dim3(d.n_cus * 8), dim3(256), 0, st2, d.d_hits, fa, counters);
-                hipLaunchKernelGGL(fz_gen_scatter_kernel, dim3(d.n_cus * 8), dim3(256), 0, st2, d.d_hits, fa, recs,
+                hipLaunchKernelGGL(fz_gen_order_kernel, dim3(d.n_cus * 8), dim3(256), 0, d.stream, d.d_hits, fa, counters);
+                hipLaunchKernelGGL(fz_gen_scatter_kernel, dim3(d.n_cus * 8), dim3(256), 0, d.stream, d.d_hits, fa, recs,
                                    reinterpret_cast<FzOutRow *>(d.d_gen_rows), counters);
                 HIP_TRY(hipGetLastError());
             }
             // folded search: the (few) pairs come back with the counters in ONE copy — as many as the previous search had
             d.fold_copied = fold_direct ? kHostRecs : q.fold ? std::min<uint64_t>(std::min<uint64_t>(d.fold_guess, kHostRecs), d.rec_cap) : 0;
             if (!fold_direct) {
-                HIP_TRY(hipMemcpyAsync(d.h_stage, d.d_out, kHeaderBytes + d.fold_copied * sizeof(FzGenRec), hipMemcpyDeviceToHost, st2));
-                HIP_TRY(hipEventRecord(d.ev[3], st2));
+                HIP_TRY(hipMemcpyAsync(d.h_stage, d.d_out, kHeaderBytes + d.fold_copied * sizeof(FzGenRec), hipMemcpyDeviceToHost, d.stream));
+                HIP_TRY(hipEventRecord(d.ev[3], d.stream));
                 // the counters are zeroed for the next search now, behind the copy (not in front of that search's scan)
-                if (st2 == d.stream) {
-                    HIP_TRY(hipMemsetAsync(d.d_out, 0, kHeaderBytes, st2));
-                    d.header_zeroed = true;
-                }
+                HIP_TRY(hipMemsetAsync(d.d_out, 0, kHeaderBytes, d.stream));
             } else {
-                if (!lp_stop) HIP_TRY(hipEventRecord(d.ev[3], st2));
-                d.header_zeroed = true;                       // by the publishing workgroup
+                if (!lp_stop) HIP_TRY(hipEventRecord(d.ev[3], d.stream));
             }
-            if (d.dedup_used && st2 == d.stream) {            // the window table is cleared for the next search, behind this one
+            d.header_zeroed = true;                           // (direct: by the publishing workgroup)
+            if (d.dedup_used) {                               // the window table is cleared for the next search, behind this one
                 HIP_TRY(hipMemsetAsync(d.d_gen_dedup, 0, FZ_GEN_DEDUP_ZERO_BYTES, d.stream));
                 d.dedup_zeroed = true;
             }
@@ -1823,15 +1790,13 @@ int run_generic(fz_ctx *ctx, fz_seq *seq, const Search &q, std::vector<FzGenRec>
                 ctx->stats.ngram_hits += nh;
                 continue;
             }
-            const bool gen_direct2 = sw().gen_direct;
             if (nh > d.hit_cap) { int rc = ensure_hits(d, nh + nh / 8 + 1024); if (rc) return rc; rerun = true; }
-            if (nr > d.big_cap) { int rc = ensure_big(d, nr + nr / 8 + 1024); if (rc) return rc; if (gen_direct2) rerun = true; }
+            if (nr > d.big_cap) { int rc = ensure_big(d, nr + nr / 8 + 1024); if (rc) return rc; }
             if (d.fold_was_direct) {                          // pairs beyond the staging buffer were dropped: again, through d_out
                 if (nr > kHostRecs) { d.fold_direct = false; rerun = true; }
             } else if (q.fold && nr * 4 < kHostRecs) d.fold_direct = true;
-            if (!gen_direct2 && !d.fold_was_direct && std::max(nr, nrows) > d.rec_cap) { int rc = ensure_recs(d, std::max(nr, nrows) + nrows / 8 + 1024); if (rc) return rc; rerun = true; }
-            const bool host_order2 = sw().gen_host_order;
-            const bool rows_ready = !gen_direct2 && !host_order2 && !q.fold && seq->shards.size() == 1 && sh.geom.seg_stride == 0 &&
+            if (!d.fold_was_direct && std::max(nr, nrows) > d.rec_cap) { int rc = ensure_recs(d, std::max(nr, nrows) + nrows / 8 + 1024); if (rc) return rc; rerun = true; }
+            const bool rows_ready = !q.fold && seq->shards.size() == 1 && sh.geom.seg_stride == 0 &&
                                     nh <= FZ_GEN_ORDER_MAX && nrows <= d.gen_rows_cap && !comm_multi_process(ctx);
             // Window table + device ordering: only the windows' LEADERS left automaton records, the members' rows exist on the
             // device-ordered path alone.  If that path cannot be taken for this attempt (the row buffer is smaller than the row
@@ -1845,7 +1810,7 @@ int run_generic(fz_ctx *ctx, fz_seq *seq, const Search &q, std::vector<FzGenRec>
             }
             const bool in_stage = q.fold && nr <= d.fold_copied && seq->shards.size() == 1;   // the pairs are in h_stage already
             if (q.fold) d.fold_guess = std::max<uint64_t>(4096, nr + nr / 4 + 256);
-            if (!gen_direct2 && !rerun && !novf && nr && !rows_ready && !in_stage)
+            if (!rerun && !novf && nr && !rows_ready && !in_stage)
                 HIP_TRY(hipMemcpy(d.h_big, d.d_out + kHeaderBytes, nr * sizeof(FzGenRec), hipMemcpyDeviceToHost));
             if (novf) { lists_overflowed = true; rerun = true; }
             if (rerun) continue;
@@ -2218,7 +2183,7 @@ static int devstate_init(DevState &d) {
     HIP_TRY(hipSetDevice(d.device));
     // a search call is ~0.3 ms: spin instead of sleeping on the completion interrupt — on EVERY device of the context
     // (the flag is per device; refused with hipErrorSetOnActiveProcess once a device is in use: then it stays as it is)
-    if (!sw().no_spin) (void)hipSetDeviceFlags(hipDeviceScheduleSpin);
+    (void)hipSetDeviceFlags(hipDeviceScheduleSpin);
     (void)hipGetLastError();
     // Lowest priority: a different hardware queue than the default-priority streams of the rest of
     // the process, and the dispatcher prefers their workgroups.  Measured with RCCL on torch's
@@ -2226,9 +2191,8 @@ static int devstate_init(DevState &d) {
     // after it (250 us); the scan alone is not slower at low priority.
     int prio_least = 0, prio_greatest = 0;
     HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-    const bool default_prio = sw().stream_default_priority;
-    HIP_TRY(hipStreamCreateWithPriority(&d.stream, hipStreamNonBlocking, default_prio ? 0 : prio_least));
-    HIP_TRY(hipStreamCreateWithPriority(&d.stream_alt, hipStreamNonBlocking, default_prio ? 0 : prio_least));
+    HIP_TRY(hipStreamCreateWithPriority(&d.stream, hipStreamNonBlocking, prio_least));
+    HIP_TRY(hipStreamCreateWithPriority(&d.stream_alt, hipStreamNonBlocking, prio_least));
     HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d.d_hdr_alt), kHeaderBytes));
     HIP_TRY(hipMemset(d.d_hdr_alt, 0, kHeaderBytes));
     for (auto &ev : d.ev) HIP_TRY(hipEventCreate(&ev));
@@ -2247,7 +2211,6 @@ static void devstate_destroy(DevState &d) {
     if (d.stream) (void)hipStreamSynchronize(d.stream);
     if (d.stream_alt) { (void)hipStreamSynchronize(d.stream_alt); (void)hipStreamDestroy(d.stream_alt); }
     if (d.d_hdr_alt) (void)hipFree(d.d_hdr_alt);
-    if (d.stream_hi) (void)hipStreamSynchronize(d.stream_hi);
     if (d.d_hits) (void)hipFree(d.d_hits);
     if (d.d_out) (void)hipFree(d.d_out);
     if (d.spare_alloc) (void)hipFree(d.spare_alloc);
@@ -2263,8 +2226,6 @@ static void devstate_destroy(DevState &d) {
     for (int i = 0; i < 2; ++i) if (d.stream_h[i]) (void)hipHostFree(d.stream_h[i]);
     if (d.stream_d) (void)hipFree(d.stream_d);
     for (auto &ev : d.ev) if (ev) (void)hipEventDestroy(ev);
-    if (d.ev_scan_done) (void)hipEventDestroy(d.ev_scan_done);
-    if (d.stream_hi) { (void)hipStreamSynchronize(d.stream_hi); (void)hipStreamDestroy(d.stream_hi); }
     if (d.stream) (void)hipStreamDestroy(d.stream);
 }
 
@@ -2303,7 +2264,7 @@ int fz_create(const int *device_ids, int n_devices, fz_ctx **out) {
         return fail(FZ_EDEVICE, "no HIP device available (%s)", e == hipSuccess ? "count = 0" : hipGetErrorString(e));
     // a search call is ~0.3 ms: spin instead of sleeping on the completion interrupt (ignored if the
     // runtime was already initialised with other flags, e.g. by torch in a distributed job)
-    if (!sw().no_spin) (void)hipSetDeviceFlags(hipDeviceScheduleSpin);
+    (void)hipSetDeviceFlags(hipDeviceScheduleSpin);
     (void)hipGetLastError();
     std::vector<int> ids;
     if (!device_ids || n_devices <= 0) ids.push_back(0);
@@ -3952,16 +3913,7 @@ int fz_stream_read_fd(fz_stream *st, int fd, int64_t offset, int threads, uint64
         uint64_t n = 0;
         bool short_read = false;
         const auto tf = std::chrono::steady_clock::now();
-        const bool nofill = sw().stream_nofill;     // lab: the H2D + scan pipeline alone
-        if (nofill) {
-            struct stat sb;
-            if (fstat(fd, &sb) != 0) return fail(FZ_EDEVICE, "fstat failed");
-            const uint64_t left = (uint64_t)sb.st_size > pos ? (uint64_t)sb.st_size - pos : 0;
-            n = std::min(room, left);
-            short_read = n < room;
-        } else {
-            rc = pool.fill(fd, dst, room, pos, n, short_read);
-        }
+        rc = pool.fill(fd, dst, room, pos, n, short_read);
         if (rc) return rc;
         st->t_fill += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tf).count();
         rc = fz_stream_submit(st, n, short_read ? 1 : 0);
@@ -4365,8 +4317,7 @@ static int group_best_exact(const fz_match *in, uint64_t n, fz_match **out, uint
 int fz_group_best(const fz_match *in, uint64_t n, fz_match **out, uint64_t *n_out) {
     if (!out || !n_out || (!in && n)) return fail(FZ_EINVAL, "null argument");
     *out = nullptr; *n_out = 0;
-    const bool no_fast = sw().group_best_exact;                                // test knob
-    if (n < 32 || n > 0x7fffffffull || no_fast) return group_best_exact(in, n, out, n_out);
+    if (n < 32 || n > 0x7fffffffull) return group_best_exact(in, n, out, n_out);
     auto better = [](const fz_match &a, const fz_match &b) {
         const int64_t la = a.end - a.start, lb = b.end - b.start;
         return a.dist < b.dist || (a.dist == b.dist && (la > lb || (la == lb && a.start < b.start)));
