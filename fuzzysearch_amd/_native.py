@@ -26,6 +26,7 @@ EXPORTED_SYMBOLS = (
     "fz_consolidate", "fz_group_best", "fz_merge_ranks", "fz_wire_pack", "fz_wire_merge", "fz_debug_launch_plan", "fz_debug_order_records", "fz_debug_order_records_bounded", "fz_debug_order_segments", "fz_stats", "fz_mem_info", "fz_set_timing", "fz_set_streams", "fz_device_ms", "fz_free",
     "fz_comm_unique_id", "fz_comm_init_rank", "fz_comm_init_all", "fz_comm_info", "fz_comm_set_collective",
     "fz_comm_allgather", "fz_comm_max_f64", "fz_comm_barrier", "fz_comm_destroy", "fz_comm_gather_ms", "fz_comm_backend", "fz_debug_reload_switches", "fz_debug_gather_merge", "fz_debug_scan_regions",
+    "fz_debug_scan_plan",
 )
 
 
@@ -119,6 +120,10 @@ def load_library():
         L.fz_comm_gather_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
         L.fz_debug_scan_regions.restype = ci
         L.fz_debug_scan_regions.argtypes = [u64, u64, u32, ci, ctypes.c_double, ci, ctypes.POINTER(u32), ctypes.c_void_p]
+        if hasattr(L, "fz_debug_scan_plan"):
+            L.fz_debug_scan_plan.restype = ci
+            L.fz_debug_scan_plan.argtypes = [ctypes.c_char_p, u32, u32, u64, u32, ci, ctypes.POINTER(u32), ctypes.POINTER(u32),
+                                             ctypes.POINTER(ci), ctypes.POINTER(u32), ctypes.c_void_p]
         L.fz_debug_gather_merge.restype = ci
         L.fz_debug_gather_merge.argtypes = [ctypes.c_void_p, u32, u64, ctypes.c_void_p, u32, mpp, u64p, u64p]
         L.fz_seq_len.restype = u64
@@ -765,7 +770,7 @@ class Engine(object):
             _check(self._lib.fz_set_timing(self._h, 1 if on else 0))
 
     def set_streams(self, n):
-        """1 (default) or 2 streams for the two-deep pipeline of fused searches (fz_set_streams)."""
+        """2 (default with one device) or 1 stream per device for the two-deep pipeline of fused searches (fz_set_streams)."""
         with self._lock:
             _check(self._lib.fz_set_streams(self._h, n))
 

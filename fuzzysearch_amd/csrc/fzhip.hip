@@ -203,10 +203,12 @@ struct DevState {
     uint64_t pat_cap = 0;
     int slot_id = 0;                             // which of the two result slots is the current one
     uint32_t launches_used = 0;                  // scan launches of the last enqueue on this device
-    // Two fused searches in flight (result slot 1): the younger one's scan on a stream and a counter block of its own, so
-    // that it starts while the older scan drains instead of behind it (fz_set_streams(ctx, 2); default: one stream)
+    // Two fused searches in flight: the younger one's scan on the stream the older one does not use, so that it starts
+    // while the older scan drains instead of behind it (fz_ctx::streams; enqueue_shard states why the two may share the
+    // device).  stream_alt has a counter block of its own; on_alt: the search of this result slot scans there.
     hipStream_t stream_alt = nullptr;
     uint8_t *d_hdr_alt = nullptr;
+    bool on_alt = false;
     // RCCL (fz_comm_*): this device state is rank comm_rank of a communicator.  A search of such a context leaves
     // its counters + records in d_out; a device-to-device snapshot (d_send[slot], taken on the scan stream right
     // behind the kernels, so a younger search may reuse d_out) is what the all-gather sends.
@@ -224,7 +226,7 @@ struct DevState {
     struct Slot {
         hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
         uint8_t *h_stage = nullptr, *h_stage_dev = nullptr;
-        bool last_direct = false, verify_launched = false, fused_used = false, timed = true;
+        bool last_direct = false, verify_launched = false, fused_used = false, timed = true, on_alt = false;
         int scan_end_event = 1, verify_end_event = 2;
         uint64_t hit_cap_used = 0, rec_cap_used = 0;
         int slot_id = 1;
@@ -238,6 +240,7 @@ struct DevState {
         std::swap(verify_launched, other.verify_launched);
         std::swap(timed, other.timed);
         std::swap(fused_used, other.fused_used);
+        std::swap(on_alt, other.on_alt);
         std::swap(scan_end_event, other.scan_end_event);
         std::swap(verify_end_event, other.verify_end_event);
         std::swap(hit_cap_used, other.hit_cap_used);
@@ -420,7 +423,8 @@ struct fz_ctx {
     bool comm_broken = false;                    // a collective ran into its deadline: the communicator is abandoned (no further
                                                  // collective is started, its streams and buffers are not waited for or freed)
     uint64_t gcap = 4096;                        // records per rank the all-gather carries (follows the counts, on all ranks alike)
-    // fz_set_streams: 2 = the younger of two fused searches in flight scans on a stream of its own
+    // fz_set_streams: 2 = the younger of two fused searches in flight scans on the other stream of its device, next to the
+    // older one; 1 = behind it on the same stream.  fz_create sets the default (2 for a context of one device state).
     int streams = 1;
     double last_gather_ms = 0;                   // host time of the last search's exchange step (all-gather + D2H + parse)
     // multi-device contexts: one host thread per device (enqueue, wait, collect and order its shard), and what the
@@ -840,11 +844,14 @@ struct ScanPlan {
     uint32_t form = FZ_FORM_NONE;   // fz_stats' verify_form
     uint32_t lds = 0;            // dynamic LDS of a scan workgroup
     VerifyPlan vp;               // the stand-alone verification (with_verify and not fused)
+    bool overlapped = false;     // the launch runs next to the scan of the search in flight before it (enqueue_shard)
 };
 
 // Everything that decides what a scan of the shard with geometry `geom` runs: a function of the search, the geometry, the
-// device's CU count and the switches, no device state.
-ScanPlan plan_scan(const Search &q, const FzGeom &geom, uint32_t n_cus, bool with_verify, FzScanArgs &fa) {
+// device's CU count, the switches and `shares_chip` (another search of the context is in flight on the device and this one
+// writes its records straight to the host), no device state.  A fused in-memory scan that shares the chip is planned as
+// one that runs next to its predecessor (sp.overlapped); every other plan is the same with or without `shares_chip`.
+ScanPlan plan_scan(const Search &q, const FzGeom &geom, uint32_t n_cus, bool with_verify, bool shares_chip, FzScanArgs &fa) {
     ScanPlan sp;
     const uint32_t L = q.plan.L;
     const uint32_t G = (uint32_t)q.plan.s.size();
@@ -854,54 +861,6 @@ ScanPlan plan_scan(const Search &q, const FzGeom &geom, uint32_t n_cus, bool wit
     const uint64_t tile_hi = q.part_hi == ~0ull ? ntiles_all : std::min<uint64_t>(ntiles_all, (q.part_hi + FZ_TILE_BYTES - 1) / FZ_TILE_BYTES);
     const bool partial = tile_lo != 0 || tile_hi != ntiles_all;
     const uint64_t ntiles = sp.ntiles = tile_hi > tile_lo ? tile_hi - tile_lo : 0;
-    // Grid: every workgroup strides over ~16 tiles (256 KiB).  Measured on MI355X at 1 GiB: 6 / 8 /
-    // 12 / 16 / 20 / 32 / 64 workgroups per CU -> 0.302 / 0.302 / 0.276 / 0.267 / 0.265 / 0.280 /
-    // 0.333 ms: several rounds of short workgroups overlap one workgroup's end-of-life verification
-    // (latency-bound) with the others' streaming; too many pay the per-workgroup fixed cost.  At least
-    // 6 per CU (the co-resident count at this kernel's SGPR use) so small inputs still fill the chip.
-    // (Round 2 measured the alternative — a persistent grid whose waves draw 4 KiB chunks from ticket
-    // counters so that all finish together: same time without candidates, 0.04 ms slower on DNA,
-    // because every wave then runs its verification at the same moment, at the end.)
-    // (re-measured with the software-pipelined loop of round 2, 1 GiB: 8 / 10 / 12 / 14 / 16 / 20 / 24 / 32 tiles ->
-    //  DNA k = 2: 0.232 / 0.223 / 0.222 / 0.222 / 0.224 / 0.240 / 0.244 / 0.260 ms; exact search: 0.191 / 0.182 /
-    //  0.187 / 0.193 / 0.199 / 0.201 / 0.196 / 0.205 ms)
-    // Round 3 (two-level finish tickets in place, `profiles/r03_lab_ab.txt`): what matters below ~10 rounds of resident
-    // workgroups is that the grid is a WHOLE number of rounds of 6 workgroups per CU (round 4's device stamps show SEVEN
-    // resident per CU — amdgpu_waves_per_eu(7, 7) — so these are not rounds of residents; the multiples of 6 per CU
-    // stay because they measured best, with and without the tapered last round below; a last round that is
-    // 56 % full costs 1 GiB 8 us) of ~9.5 tiles per workgroup: 1 GiB, 4 rounds (10.7 tiles) 0.2046 ms, 5 rounds 0.2048,
-    // 3 rounds 0.2062, 6 rounds 0.2074, 8 rounds 0.2104 against 0.2121-0.2146 for 12 tiles (3.56 rounds); 2 GiB, 9 rounds
-    // 0.3887 against 0.3989; 512 MiB, 2 rounds 0.1165 against 0.1182.  Long inputs keep 12 tiles per workgroup (4 GiB:
-    // 0.7743 against 0.7791-0.7855 for 14-18 whole rounds and 0.802 for 8 tiles: the per-workgroup cost wins there).
-    constexpr uint64_t kTilesPerWg = 12;
-    const uint64_t resident = (uint64_t)n_cus * 6;
-    uint64_t max_grid = std::max<uint64_t>(resident, ntiles / kTilesPerWg);
-    if (ntiles < resident * 120) {
-        const uint64_t rounds = std::max<uint64_t>(1, (2 * ntiles + resident * 19 / 2) / (resident * 19));   // round(ntiles / (9.5 resident))
-        max_grid = resident * rounds;
-    }
-    // (has_near_match_*, measured in round 5 on 4 GiB with a match in the first MiB: 0.21 ms against 0.84 ms for the full
-    //  scan.  What is left is NOT the running workgroups finishing their tiles but the ~21 800 workgroups that start after
-    //  the first record, skip their tiles and still take their finish tickets: ~100 agent-scope atomics per microsecond on
-    //  the sixteen shard words, which share one cache line.  Tried and dropped: a check of the record counter per tile in
-    //  the scan's loop (cannot shorten what the tickets bound); workgroups of 6 tiles (0.31 ms: twice the tickets); the shard
-    //  words spread over four lines of the header (every scan slower — 1 GiB exact search 0.188-0.193 -> 0.197 ms, same
-    //  box: those lines also hold the statistics words).)
-    // the queue codes carry a bounded per-workgroup tile iteration
-    const uint64_t min_grid = (ntiles + FZ_TITER_MAX - 1) / FZ_TITER_MAX;
-    sp.grid = (uint32_t)std::max<uint64_t>(std::max<uint64_t>(1, min_grid), std::min<uint64_t>(ntiles, max_grid));
-    // Tapered last round: workgroups start in blockIdx order, so the last resident round of a launch starts while the
-    // machine is still full and — with equal shares — ends one workgroup life (~60 us) after the grid ran dry, the chip
-    // draining all the while (device stamps of every workgroup, benchmarks/lab_scan_phases.py: residency falls linearly from
-    // 1 792 to 0 over the last 60 us of a 1 GiB launch).  The last `resident` workgroups therefore take shrinking shares
-    // (kTaperSteps groups, down to kTaperMin of a full share) of their own tile range at the end of the buffer, the others
-    // correspondingly more.
-    plan_scan_regions(fa, ntiles, sp.grid, n_cus);
-    if (partial) {                                               // one region: the call's tiles, no taper
-        fa.nreg = 1;
-        fa.reg_wg0[0] = 0; fa.reg_nwg[0] = sp.grid; fa.reg_tile0[0] = tile_lo; fa.reg_end[0] = tile_hi;
-    }
-
     const bool force_big = sw().force_big_verify;
     sp.vp = plan_verify(q);
     const VerifyPlan &vp = sp.vp;
@@ -1009,12 +968,74 @@ ScanPlan plan_scan(const Search &q, const FzGeom &geom, uint32_t n_cus, bool wit
               : wf_fused ? FZ_FORM_FUSED_CELLS : fa.fused ? FZ_FORM_FUSED_BAND : FZ_FORM_KERNEL;
     // (the hit-emitting form keeps no pattern in LDS: fz_confirm reads it from the argument block / HBM)
     sp.lds = fa.fused ? fused_lds : FZ_TABLE_BYTES + FZ_WAVES_PER_BLOCK * fz_wave_lds_bytes(0, 0, 64, true);
+    // Next to the predecessor: fused (no hit list), in memory, the pattern in the argument block (stage_pattern leaves the
+    // HBM copy alone), whole-buffer scans (has_near_match_* never pipelines)
+    sp.overlapped = shares_chip && fa.fused && in_memory && !partial && q.m <= FZ_MAX_M && !vp.big;
+
+    // Grid: every workgroup strides over ~16 tiles (256 KiB).  Measured on MI355X at 1 GiB: 6 / 8 /
+    // 12 / 16 / 20 / 32 / 64 workgroups per CU -> 0.302 / 0.302 / 0.276 / 0.267 / 0.265 / 0.280 /
+    // 0.333 ms: several rounds of short workgroups overlap one workgroup's end-of-life verification
+    // (latency-bound) with the others' streaming; too many pay the per-workgroup fixed cost.  At least
+    // 6 per CU (the co-resident count at this kernel's SGPR use) so small inputs still fill the chip.
+    // (Round 2 measured the alternative — a persistent grid whose waves draw 4 KiB chunks from ticket
+    // counters so that all finish together: same time without candidates, 0.04 ms slower on DNA,
+    // because every wave then runs its verification at the same moment, at the end.)
+    // (re-measured with the software-pipelined loop of round 2, 1 GiB: 8 / 10 / 12 / 14 / 16 / 20 / 24 / 32 tiles ->
+    //  DNA k = 2: 0.232 / 0.223 / 0.222 / 0.222 / 0.224 / 0.240 / 0.244 / 0.260 ms; exact search: 0.191 / 0.182 /
+    //  0.187 / 0.193 / 0.199 / 0.201 / 0.196 / 0.205 ms)
+    // Round 3 (two-level finish tickets in place, `profiles/r03_lab_ab.txt`): what matters below ~10 rounds of resident
+    // workgroups is that the grid is a WHOLE number of rounds of 6 workgroups per CU (round 4's device stamps show SEVEN
+    // resident per CU — amdgpu_waves_per_eu(7, 7) — so these are not rounds of residents; the multiples of 6 per CU
+    // stay because they measured best, with and without the tapered last round below; a last round that is
+    // 56 % full costs 1 GiB 8 us) of ~9.5 tiles per workgroup: 1 GiB, 4 rounds (10.7 tiles) 0.2046 ms, 5 rounds 0.2048,
+    // 3 rounds 0.2062, 6 rounds 0.2074, 8 rounds 0.2104 against 0.2121-0.2146 for 12 tiles (3.56 rounds); 2 GiB, 9 rounds
+    // 0.3887 against 0.3989; 512 MiB, 2 rounds 0.1165 against 0.1182.  Long inputs keep 12 tiles per workgroup (4 GiB:
+    // 0.7743 against 0.7791-0.7855 for 14-18 whole rounds and 0.802 for 8 tiles: the per-workgroup cost wins there).
+    constexpr uint64_t kTilesPerWg = 12;
+    const uint64_t resident = (uint64_t)n_cus * 6;
+    uint64_t max_grid = std::max<uint64_t>(resident, ntiles / kTilesPerWg);
+    if (ntiles < resident * 120) {
+        const uint64_t rounds = std::max<uint64_t>(1, (2 * ntiles + resident * 19 / 2) / (resident * 19));   // round(ntiles / (9.5 resident))
+        max_grid = resident * rounds;
+    }
+    // A scan that runs next to its predecessor (sp.overlapped): 16 tiles per workgroup, no tapered last round.  The
+    // older scan's drain is what the younger one fills, so neither the whole-rounds rule nor the taper has a drain of its
+    // own to shorten; fewer, longer workgroups pay fewer per-workgroup costs.  Measured on MI355X, two searches in flight,
+    // median ms per step (`profiles/r07_overlap.txt`), 1 GiB / 4 GiB: the plan of a scan alone 0.208-0.209 / 0.825-0.826;
+    // taper off 0.205 / 0.819-0.820; 12 tiles 0.207 / 0.821-0.824; 16 tiles 0.205 / 0.808-0.809; 16 tiles, taper off
+    // 0.201 / 0.804-0.805 (same box; on another 0.198 / 0.793, against 20 tiles 0.199 / 0.798, 24 tiles 0.203 / 0.811,
+    // 32 tiles 0.200 / 0.801).
+    constexpr uint64_t kTilesPerWgOverlapped = 16;
+    constexpr bool kTaperOverlapped = false;
+    if (sp.overlapped) max_grid = std::max<uint64_t>(resident, ntiles / kTilesPerWgOverlapped);
+    // (has_near_match_*, measured in round 5 on 4 GiB with a match in the first MiB: 0.21 ms against 0.84 ms for the full
+    //  scan.  What is left is NOT the running workgroups finishing their tiles but the ~21 800 workgroups that start after
+    //  the first record, skip their tiles and still take their finish tickets: ~100 agent-scope atomics per microsecond on
+    //  the sixteen shard words, which share one cache line.  Tried and dropped: a check of the record counter per tile in
+    //  the scan's loop (cannot shorten what the tickets bound); workgroups of 6 tiles (0.31 ms: twice the tickets); the shard
+    //  words spread over four lines of the header (every scan slower — 1 GiB exact search 0.188-0.193 -> 0.197 ms, same
+    //  box: those lines also hold the statistics words).)
+    // the queue codes carry a bounded per-workgroup tile iteration
+    const uint64_t min_grid = (ntiles + FZ_TITER_MAX - 1) / FZ_TITER_MAX;
+    sp.grid = (uint32_t)std::max<uint64_t>(std::max<uint64_t>(1, min_grid), std::min<uint64_t>(ntiles, max_grid));
+    // Tapered last round: workgroups start in blockIdx order, so the last resident round of a launch starts while the
+    // machine is still full and — with equal shares — ends one workgroup life (~60 us) after the grid ran dry, the chip
+    // draining all the while (device stamps of every workgroup, benchmarks/lab_scan_phases.py: residency falls linearly from
+    // 1 792 to 0 over the last 60 us of a 1 GiB launch).  The last `resident` workgroups therefore take shrinking shares
+    // (kTaperSteps groups, down to kTaperMin of a full share) of their own tile range at the end of the buffer, the others
+    // correspondingly more.
+    if (!sp.overlapped || kTaperOverlapped) plan_scan_regions(fa, ntiles, sp.grid, n_cus);
+    else fa.nreg = 0;
+    if (partial) {                                               // one region: the call's tiles, no taper
+        fa.nreg = 1;
+        fa.reg_wg0[0] = 0; fa.reg_nwg[0] = sp.grid; fa.reg_tile0[0] = tile_lo; fa.reg_end[0] = tile_hi;
+    }
     return sp;
 }
 
 // Enqueue scan (+ separate verify when it cannot be fused) for one shard on its device stream, as plan_scan decided.
-// No host synchronisation.
-int enqueue_shard(fz_ctx *ctx, const Shard &sh, const Search &q, bool with_verify, bool copy_back = true) {
+// No host synchronisation.  `behind`: another search of the context is in flight (fz_*_begin with one search pending).
+int enqueue_shard(fz_ctx *ctx, const Shard &sh, const Search &q, bool with_verify, bool copy_back = true, bool behind = false) {
     DevState &d = lane_dev(ctx, sh.dev);
     HIP_TRY(hipSetDevice(d.device));
     unsigned long long *counters = reinterpret_cast<unsigned long long *>(d.d_out);
@@ -1029,7 +1050,7 @@ int enqueue_shard(fz_ctx *ctx, const Shard &sh, const Search &q, bool with_verif
 
     FzScanArgs fa;
     fill_common_args(fa, sh, q);
-    const ScanPlan sp = plan_scan(q, sh.geom, (uint32_t)d.n_cus, with_verify, fa);
+    const ScanPlan sp = plan_scan(q, sh.geom, (uint32_t)d.n_cus, with_verify, behind && ctx->streams == 2 && direct, fa);
     const VerifyPlan &vp = sp.vp;
     const uint32_t L = q.plan.L;
     const uint32_t G = (uint32_t)q.plan.s.size();
@@ -1047,8 +1068,28 @@ int enqueue_shard(fz_ctx *ctx, const Shard &sh, const Search &q, bool with_verif
     fa.mask2 = 0xffffffffu;
     fa.hit_cap = d.hit_cap;
     fa.rec_cap = direct ? kHostRecs : d.rec_cap;
-    // the stream and the counter block of this search (see DevState::stream_alt)
-    const bool alt = ctx->streams == 2 && d.slot_id == 1 && fa.fused && direct && copy_back && !fa.pat_g && sh.geom.seg_stride == 0;
+    // The stream and the counter block of this search.  An overlapped scan (plan_scan: fused, direct, in memory, the pattern
+    // in the argument block) takes the stream its predecessor — the search in the device's other result slot — does not
+    // use; so do the counters: stream_alt has d_hdr_alt, d.stream the header of d_out.  Two scans may then run at once
+    // because nothing one of them writes is read or written by the other:
+    //  - d_hits: only the hit-list forms write it, never a fused scan; a predecessor that is not fused may use it, its
+    //    overlapped successor does not.
+    //  - d_out: an overlapped scan on d.stream uses its header as counters (zeroed in stream order by the memset below or
+    //    by the publishing workgroup of the last search on d.stream) and writes no records there: direct mode puts them in
+    //    the pinned slot.  The scan on stream_alt never touches d_out.
+    //  - the pinned slots: every search writes the records and the published counters of its own result slot (h_stage_dev
+    //    of the slot enqueue runs in; pending_begin swaps the slots around the launch).
+    //  - d_hdr_alt: one search at a time on stream_alt (the two in flight are on different streams); its publishing
+    //    workgroup zeroes it for the next one, which is ordered behind it on that stream.
+    //  - pattern staging (d_pat): an overlapped scan reads the pattern from its argument block; a predecessor staged on
+    //    d.stream keeps the buffer to itself.
+    //  - fallback: a result set beyond the pinned slot (collect_shard) synchronises both streams before it grows d_out /
+    //    d_hits and re-runs the search on d.stream in copy mode; while a device is out of direct mode a second search is not
+    //    launched before the first is collected (pending_begin), so nothing overlaps until direct mode returns.
+    // Synchronous calls, the first search of a pipeline and everything not overlapped stay on d.stream.
+    if (sp.overlapped && fa.pat_g) return fail(FZ_EDEVICE, "internal: an overlapped scan with the pattern staged in HBM");
+    const bool alt = sp.overlapped && !d.other.on_alt;
+    d.on_alt = alt;
     const hipStream_t st = alt ? d.stream_alt : d.stream;
     if (alt) counters = reinterpret_cast<unsigned long long *>(d.d_hdr_alt);
     else {
@@ -1472,7 +1513,7 @@ int gather_records(fz_ctx *ctx, fz_seq *seq, std::vector<FzRec> &recs) {
 }
 
 // Launch a search on every shard (no host synchronisation).
-int search_enqueue(fz_ctx *ctx, fz_seq *seq, const Search &q, bool with_verify) {
+int search_enqueue(fz_ctx *ctx, fz_seq *seq, const Search &q, bool with_verify, bool behind = false) {
     ctx->view = nullptr;
     ctx->view_n = 0;
     ctx->rows_ready = false;
@@ -1480,7 +1521,9 @@ int search_enqueue(fz_ctx *ctx, fz_seq *seq, const Search &q, bool with_verify) 
     ctx->stats.bytes_scanned = ctx->stats.ngram_hits = ctx->stats.raw_matches = 0;
     ctx->stats.filter_ms = ctx->stats.verify_ms = ctx->stats.device_ms = 0;
     ctx->tref.clear();
-    int rc = for_each_shard(ctx, seq, [ctx, seq, &q, with_verify](size_t si) { return enqueue_shard(ctx, seq->shards[si], q, with_verify); });
+    int rc = for_each_shard(ctx, seq, [ctx, seq, &q, with_verify, behind](size_t si) {
+        return enqueue_shard(ctx, seq->shards[si], q, with_verify, true, behind);
+    });
     if (rc) return rc;
     for (const Shard &sh : seq->shards) {
         const DevState &d = lane_dev(ctx, sh.dev);
@@ -2286,6 +2329,11 @@ int fz_create(const int *device_ids, int n_devices, fz_ctx **out) {
         int rc = devstate_init(d);
         if (rc) { fz_destroy(ctx); return rc; }
     }
+    // Overlapped pipelines by default where they were measured: one device state.  Several device states of one context
+    // may share a GPU (FZ_DEVICES=0,0); each brings two low-priority streams, and a process gets 4 hardware queues by
+    // default, so their streams would share queues and the overlap is not what was measured.  They keep one stream per
+    // device unless fz_set_streams(ctx, 2) asks for more.
+    ctx->streams = ctx->devs.size() == 1 ? 2 : 1;
     if (ctx->devs.size() > 1 && !sw().no_dev_threads) {
         ctx->workers = new (std::nothrow) DevWorkers(ctx->devs.size());
         if (!ctx->workers) { fz_destroy(ctx); return fail(FZ_ENOMEM, "out of memory"); }
@@ -2673,7 +2721,7 @@ static int pending_begin(fz_ctx *ctx, fz_seq *seq, const uint8_t *p, uint32_t m,
         if (second && !ctx->snapshot) for (const DevState &d : ctx->devs) if (!d.direct || env_no_direct()) pd.launched = false;
         if (pd.launched) {
             if (second) for (DevState &d : ctx->devs) d.swap_slot();
-            rc = search_enqueue(ctx, seq, q, true);
+            rc = search_enqueue(ctx, seq, q, true, /*behind=*/second);
             if (second) for (DevState &d : ctx->devs) d.swap_slot();
             if (rc) return rc;
         }
@@ -3231,6 +3279,31 @@ int fz_debug_scan_regions(uint64_t ntiles, uint64_t grid, uint32_t n_cus, int st
     static std::mutex mu;
     std::lock_guard<std::mutex> lk(mu);
     plan_scan_regions(fa, ntiles, grid, n_cus, steps, fmin, wg_per_cu);
+    *n_regions = fa.nreg;
+    for (uint32_t r = 0; r < fa.nreg; ++r) {
+        table[4 * r] = fa.reg_wg0[r]; table[4 * r + 1] = fa.reg_nwg[r]; table[4 * r + 2] = fa.reg_tile0[r]; table[4 * r + 3] = fa.reg_end[r];
+    }
+    return FZ_OK;
+}
+
+int fz_debug_scan_plan(const uint8_t *p, uint32_t m, uint32_t k, uint64_t buf_len, uint32_t n_cus, int shares_chip, uint32_t *grid,
+                       uint32_t *form, int *overlapped, uint32_t *n_regions, uint64_t *table) {
+    if (!p || !grid || !form || !overlapped || !n_regions || !table || m == 0 || m / (k + 1) == 0 || n_cus == 0)
+        return fail(FZ_EINVAL, "bad argument");
+    Search q;                                               // what lev_plan makes of the search, without a context
+    q.mode = FZ_MODE_LEV; q.m = m; q.k = k; q.p = p;
+    q.plan.L = m / (k + 1);
+    for (uint32_t s = 0; s + q.plan.L <= m; s += q.plan.L) q.plan.s.push_back(s);
+    FzGeom geom{};
+    geom.buf_len = buf_len;
+    static FzScanArgs fa;
+    static std::mutex mu;
+    std::lock_guard<std::mutex> lk(mu);
+    memset(&fa, 0, sizeof fa);
+    const ScanPlan sp = plan_scan(q, geom, n_cus, true, shares_chip != 0, fa);
+    *grid = sp.grid;
+    *form = sp.form;
+    *overlapped = sp.overlapped ? 1 : 0;
     *n_regions = fa.nreg;
     for (uint32_t r = 0; r < fa.nreg; ++r) {
         table[4 * r] = fa.reg_wg0[r]; table[4 * r + 1] = fa.reg_nwg[r]; table[4 * r + 2] = fa.reg_tile0[r]; table[4 * r + 3] = fa.reg_end[r];

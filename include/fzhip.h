@@ -326,6 +326,14 @@ int fz_debug_order_segments(const void *recs, const uint64_t *seg_ends, uint32_t
 int fz_debug_scan_regions(uint64_t ntiles, uint64_t grid, uint32_t n_cus, int steps, double fmin, int wg_per_cu, uint32_t *n_regions,
                           uint64_t *table);
 
+/* Test hook, no device needed: the plan of the scan launches of a Levenshtein n-gram search (pattern p of m characters,
+ * budget k) over an in-memory shard of `buf_len` bytes on a GPU with `n_cus` compute units (fzhip.hip: plan_scan).
+ * shares_chip != 0: the search is launched while another one of the context is in flight and writes its records straight
+ * to the host.  *grid = workgroups per launch, *form = FZ_FORM_* of fz_stats' verify_form, *overlapped = the launch runs
+ * next to its predecessor (on the device's other stream), regions as in fz_debug_scan_regions (table: at most 8 rows). */
+int fz_debug_scan_plan(const uint8_t *p, uint32_t m, uint32_t k, uint64_t buf_len, uint32_t n_cus, int shares_chip, uint32_t *grid,
+                       uint32_t *form, int *overlapped, uint32_t *n_regions, uint64_t *table);
+
 /* Test hook (no device needed): the host half of the exchange step of a collective search (what follows the
  * ncclAllGather).  `blocks` = `world` blocks of 1024 + cap * 24 bytes, block r = what rank r contributed: 128 64-bit
  * counters (word 1 = records the rank produced) followed by min(count, cap) device records (see fz_debug_order_records);
@@ -347,11 +355,13 @@ int  fz_mem_info(fz_ctx *ctx, uint64_t *free_bytes, uint64_t *total_bytes);
 /* hipEvent timing of the kernels (filter_ms / verify_ms / device_ms of fz_stats, fz_device_ms): on by default.
  * Off, no events are recorded around the kernels and the *_ms fields read 0. */
 int  fz_set_timing(fz_ctx *ctx, int on);
-/* Streams the two-deep pipeline (fz_lev_ngrams_begin / fz_subs_ngrams_begin) uses per device: 1 (default) = both searches in
- * flight on one stream, the younger scan starts when the older one has finished; 2 = the younger scan — when it is fused
- * and writes its records straight to the host — runs on a stream and a counter block of its own and starts while the older
- * one drains (headline workload: 0.222 -> 0.205 ms per search; a kernel's own hipEvent span then includes the time it
- * shares the device, so filter_ms no longer measures the kernel alone). */
+/* Streams the two-deep pipeline (fz_lev_ngrams_begin / fz_subs_ngrams_begin) uses per device.  2 (the default of a context
+ * of one device state) = a search launched while another one is in flight — when its scan is fused, in memory, and writes
+ * its records straight to the host — runs on the device's other stream with a counter block of its own and starts while
+ * the older one drains; consecutive searches of a pipeline alternate between the two streams.  1 (the default of a
+ * context of several device states) = both searches in flight on one stream, the younger scan starts when the older one
+ * has finished.  Synchronous calls always run on the first stream.  Under overlap a kernel's own hipEvent span (filter_ms,
+ * fz_device_ms) includes the time it shares the device with its neighbour, so it no longer measures the kernel alone. */
 int  fz_set_streams(fz_ctx *ctx, int n);
 /* hipEvent span of the filter kernel(s) of the search collected last, per device of the ctx (at most `cap` values
  * are written); returns the number of devices, or a negative FZ_E* code. */
