@@ -1,6 +1,8 @@
 """Random GPU-vs-oracle cases that also run in a SUBPROCESS (`python -m tests.gpu_cases <what> ...`): several switches
 of the library are process-wide statics read from the environment (FZ_FORCE_BIG_VERIFY, FZ_NO_SLOT_AND,
-FZ_MAX_BLOCKS, FZ_NO_DIRECT), so a test that wants them set starts a fresh interpreter.  Prints "OK <n cases> <n records>"."""
+FZ_MAX_BLOCKS, FZ_NO_DIRECT), so a test that wants them set starts a fresh interpreter.  Prints "OK <n cases> <n records>".
+The seam sweeps of tests/seam_case.py run through here as well (`seams <route> <CUs>`: the route's small texts, then the
+text with several tiles per workgroup; in-process from tests/test_gpu_scan_seams.py for the routes that need no switch)."""
 import os
 import random
 import sys
@@ -142,9 +144,124 @@ def run_generic_windows(engine, rnd, n_cases):
     return cases, n_rec
 
 
+def seam_search(engine, h, kind, p, k):
+    """The raw stream of one search of a seam case (tests/seam_case.py), as the oracle states it."""
+    if kind == "lev":
+        return engine.lev_ngrams(h, p, k)
+    if kind == "subs":
+        return engine.subs_ngrams(h, p, k)
+    if kind == "exact":
+        return engine.search_exact(h, p)
+    return engine.generic_ngrams(h, p, kind[1], kind[2], kind[3], k)
+
+
+def check_seam_case(engine, route, case, want, what):
+    """Upload, search, the full ordered raw stream against `want`, the form the route is there for; generic searches: the
+    consolidated rows and the flag as well."""
+    import oracle
+    p, k = case.pattern, case.k
+    h = engine.upload(case.text)
+    try:
+        got = seam_search(engine, h, route.kind, p, k)
+        form = engine.stats()["verify_form"]
+        if got != want:
+            bad = next((i for i, (a, b) in enumerate(zip(got, want)) if a != b), min(len(got), len(want)))
+            raise AssertionError("%s %s: %d rows against %d expected, first difference at row %d: %r / %r" % (
+                route.name, what, len(got), len(want), bad, got[bad:bad + 2], want[bad:bad + 2]))
+        assert form == route.form, (route.name, what, "verify_form", form)
+        if route.kind[0] == "generic":
+            cons = engine.generic_ngrams_consolidated(h, p, route.kind[1], route.kind[2], route.kind[3], k)
+            assert [r[:3] for r in cons] == oracle.consolidate(want), (route.name, what, "consolidated")
+            assert engine.generic_ngrams_any(h, p, route.kind[1], route.kind[2], route.kind[3], k) == (len(want) > 0)
+    finally:
+        h.release()
+    return len(got)
+
+
+def run_seam_route(engine, route, n_cus):
+    """One route of tests/seam_case.py in the regime of one tile per workgroup: the wave / row / tile sweep on the quiet and
+    on the noisy background, the first-tile / start / end sweeps on their small texts (every tail), patterns with NUL bytes
+    at either end.  -> (coverage line, searches, rows)."""
+    from tests import seam_case as sc
+    p = sc.route_pattern(route)
+    args = dict(pattern_alphabet=route.alpha, **sc.route_args(route))
+    n_search = n_rows = 0
+    ntiles = (route.n + sc.TILE - 1) // sc.TILE
+    covers = []
+    for background in ("quiet", "noisy") if route.noisy else ("quiet",):
+        case = sc.build(p, route.k, route.n, n_cus, background, **args)
+        want = sc.sparse_expected(route.kind, case) if background == "quiet" else sc.expected(route.kind, case)
+        sc.check_exact_copies_found(route.kind, case, want)
+        sc.check_coverage(case.coverage, route.m, route.k, route.classes, case.plan, ntiles, edited=route.copies == 2)
+        n_rows += check_seam_case(engine, route, case, want, background)
+        n_search += 1
+        covers.append(case.coverage)
+        edge = []
+        for case in sc.edge_cases(route, n_cus, background=background):
+            want = sc.sparse_expected(route.kind, case) if background == "quiet" else sc.expected(route.kind, case)
+            n_rows += check_seam_case(engine, route, case, want, "%s edge n = %d" % (background, len(case.text)))
+            n_search += 1
+            edge.append(case.coverage)
+        sc.check_coverage(sc.merge_coverage(edge), route.m, route.k, ("first", "start", "end"))
+        covers += edge
+    if route.m <= 64:                                           # the end class once more for every short last tile
+        for tail in sc.EDGE_TAILS[1:]:
+            edge = []
+            for case in sc.edge_cases(route, n_cus, classes=("end",), tail=tail):
+                n_rows += check_seam_case(engine, route, case, sc.sparse_expected(route.kind, case), "tail %d" % tail)
+                n_search += 1
+                edge.append(case.coverage)
+            sc.check_coverage(sc.merge_coverage(edge), route.m, route.k, ("end",))
+    if route.kind in ("lev", "subs") and route.form != sc.FORM_KERNEL:      # every form that fuses
+        for nul in ("head", "tail"):
+            p_nul = sc.route_pattern(route, nul)
+            for case in sc.edge_cases(route, n_cus, p=p_nul, classes=("start", "end")):
+                # (the two NUL bytes change the pattern's alphabet, which a short pattern's form depends on: the form the plan
+                #  hook names for this pattern, a fused one)
+                form = sc.scan_plan(p_nul, route.k, len(case.text), n_cus)[1] if route.kind == "lev" else route.form
+                assert form not in (sc.FORM_NONE, sc.FORM_KERNEL)
+                n_rows += check_seam_case(engine, route._replace(form=form), case, sc.sparse_expected(route.kind, case), "NUL %s" % nul)
+                n_search += 1
+    return sc.coverage_line(route.name, sc.merge_coverage(covers), route.form), n_search, n_rows
+
+
+def run_seam_route_iterations(engine, route, n_cus, text=None, bg=None):
+    """One route in the regime of several tiles per workgroup (64 MiB on 256 CUs: tile iterations 0 .. 2, the next tile's
+    rows 0-1 loaded while rows 2-3 are tested; the size comes from the plan hook): the wave / row / tile sweep on the quiet
+    background.  `text` / `bg`: the quiet text of an earlier route, its plants restored.  -> (line, rows, text, bg)."""
+    from tests import seam_case as sc
+    n = sc.size_with_iterations(n_cus, 3, (64 << 20) + 4099)
+    case = sc.build(sc.route_pattern(route), route.k, n, n_cus, "quiet", text=text, bg=bg, seed=2, pattern_alphabet=route.alpha,
+                    **sc.route_args(route))
+    try:
+        ntiles = (n + sc.TILE - 1) // sc.TILE
+        sc.check_coverage(case.coverage, route.m, route.k, route.classes, case.plan, ntiles, edited=route.copies == 2)
+        assert max(o[1] for o in case.coverage["tile"]["tiles"]) >= 2
+        want = sc.sparse_expected(route.kind, case)
+        sc.check_exact_copies_found(route.kind, case, want)
+        rows = check_seam_case(engine, route, case, want, "quiet, %d MiB" % (n >> 20))
+    finally:
+        case.bg.restore(case.text, case.plants)
+    return "%s | grid %d, %d MiB" % (sc.coverage_line(route.name, case.coverage, route.form), case.plan[0], n >> 20), rows, case.text, case.bg
+
+
 def main(argv):
     from fuzzysearch_amd import _native
     what = argv[0]
+    if what == "seams":
+        # one route of tests/seam_case.py under the process-wide switch it needs (FZ_NO_BITS, FZ_WF32, FZ_FORCE_BIG_VERIFY,
+        # FZ_NO_SLOT_AND): argv = route name, CU count of the device
+        from tests import seam_case as sc
+        route = next(r for r in sc.ROUTES if r.name == argv[1])
+        eng = _native.Engine([0])
+        line, n_search, n_rows = run_seam_route(eng, route, int(argv[2]))
+        print(line)
+        line, rows, _text, _bg = run_seam_route_iterations(eng, route, int(argv[2]))
+        n_search, n_rows = n_search + 1, n_rows + rows
+        eng.close()
+        print(line)
+        print("OK %d %d" % (n_search, n_rows))
+        return
     eng = _native.Engine([0])
     rnd = random.Random(int(argv[2]) if len(argv) > 2 else 5)
     n = int(argv[1]) if len(argv) > 1 else 300
