@@ -21,12 +21,14 @@ from .levenshtein import LevenshteinSearch
 from .search_exact import ExactSearch
 from .substitutions_only import SubstitutionsOnlySearch
 from . import _file_stream
+from .multi import find_near_matches_multi
 
 __version__ = '0.1.0'
 
 __all__ = [
     'find_near_matches',
     'find_near_matches_in_file',
+    'find_near_matches_multi',
     'Match',
     'resident',
     'cache_info',

@@ -27,6 +27,7 @@ EXPORTED_SYMBOLS = (
     "fz_comm_unique_id", "fz_comm_init_rank", "fz_comm_init_all", "fz_comm_info", "fz_comm_set_collective",
     "fz_comm_allgather", "fz_comm_max_f64", "fz_comm_barrier", "fz_comm_destroy", "fz_comm_gather_ms", "fz_comm_backend", "fz_debug_reload_switches", "fz_debug_gather_merge", "fz_debug_scan_regions",
     "fz_debug_scan_plan",
+    "fz_lev_ngrams_multi", "fz_lev_ngrams_multi_consolidated", "fz_debug_multi_plan",
 )
 
 
@@ -156,6 +157,11 @@ def load_library():
         L.fz_generic_lp.argtypes = [vp, vp, u8p, u32, u32, u32, u32, u32, mpp, u64p]
         L.fz_lev_ngrams_consolidated.restype = ci
         L.fz_lev_ngrams_consolidated.argtypes = [vp, vp, u8p, u32, u32, mpp, u64p]
+        for fn in (L.fz_lev_ngrams_multi, L.fz_lev_ngrams_multi_consolidated):
+            fn.restype = ci
+            fn.argtypes = [vp, vp, u8p, u64p, u32, u32, mpp, ctypes.POINTER(u64p)]
+        L.fz_debug_multi_plan.restype = ci
+        L.fz_debug_multi_plan.argtypes = [u8p, u64p, u32, u32, ctypes.POINTER(u32), ctypes.POINTER(u32)]
         L.fz_subs_ngrams_best.restype = ci
         L.fz_subs_ngrams_best.argtypes = [vp, vp, u8p, u32, u32, mpp, u64p]
         L.fz_generic_ngrams_consolidated.restype = ci
@@ -364,6 +370,29 @@ def consolidate(raw):
 
 def group_best(raw):
     return group_best_array(raw).tolist()
+
+
+def pack_patterns(patterns):
+    """Byte patterns -> (the patterns back to back, uint64 offsets array of len + 1 entries) as fz_lev_ngrams_multi takes them."""
+    parts = [bytes(memoryview(p)) if not isinstance(p, bytes) else p for p in patterns]
+    offs = (ctypes.c_uint64 * (len(parts) + 1))()
+    at = 0
+    for i, p in enumerate(parts):
+        offs[i] = at
+        at += len(p)
+    offs[len(parts)] = at
+    return b"".join(parts) or b"\0", offs
+
+
+def multi_plan(patterns, k):
+    """fz_debug_multi_plan (no device): -> (group of every pattern, None = the single-pattern route; number of groups)."""
+    L = load_library()
+    blob, offs = pack_patterns(patterns)
+    n = len(patterns)
+    group_of = (ctypes.c_uint32 * max(1, n))()
+    ng = ctypes.c_uint32(0)
+    _check(L.fz_debug_multi_plan(blob, offs, n, k, group_of, ctypes.byref(ng)))
+    return [None if group_of[i] == 0xffffffff else group_of[i] for i in range(n)], ng.value
 
 
 class OwnedRows(object):
@@ -683,6 +712,40 @@ class Engine(object):
         tuples, or a numpy structured array with those fields (as_array=True, no per-record
         Python objects)."""
         return self._match_call(self._lib.fz_lev_ngrams, seq, pattern, k, as_array=as_array)
+
+    def _multi_call(self, fn, seq, patterns, k):
+        """-> (result pointer, per-pattern row offsets) of one fz_lev_ngrams_multi* call; the caller frees the pointer."""
+        blob, offs = pack_patterns(patterns)
+        ptr = ctypes.POINTER(FzMatch)()
+        optr = ctypes.POINTER(ctypes.c_uint64)()
+        with self._lock:
+            _check(fn(self._h, seq._h, blob, offs, len(patterns), k, ctypes.byref(ptr), ctypes.byref(optr)))
+        bounds = optr[:len(patterns) + 1]
+        self._lib.fz_free(optr)
+        return ptr, bounds
+
+    def _multi(self, fn, seq, patterns, k, as_array):
+        patterns = list(patterns)
+        ptr, bounds = self._multi_call(fn, seq, patterns, k)
+        rows = _take_matches_array(self._lib, ptr, bounds[-1])
+        out = [rows[bounds[i]:bounds[i + 1]] for i in range(len(patterns))]
+        return out if as_array else [r.tolist() for r in out]
+
+    def lev_ngrams_multi(self, seq, patterns, k, as_array=False):
+        """[lev_ngrams(seq, p, k) for p in patterns] in as few passes over the sequence as the patterns allow
+        (fz_lev_ngrams_multi): a list with one raw stream per pattern, in the shapes lev_ngrams returns."""
+        return self._multi(self._lib.fz_lev_ngrams_multi, seq, patterns, k, as_array)
+
+    def lev_ngrams_multi_consolidated(self, seq, patterns, k, as_array=False):
+        """[lev_ngrams_consolidated(seq, p, k) for p in patterns] (fz_lev_ngrams_multi_consolidated)."""
+        return self._multi(self._lib.fz_lev_ngrams_multi_consolidated, seq, patterns, k, as_array)
+
+    def multi_rows_call(self, seq, patterns, k):
+        """fz_lev_ngrams_multi_consolidated -> (OwnedRows of all patterns' rows, row offsets per pattern), for callers that
+        build Match objects in C straight from the result buffer."""
+        patterns = list(patterns)
+        ptr, bounds = self._multi_call(self._lib.fz_lev_ngrams_multi_consolidated, seq, patterns, k)
+        return OwnedRows(self._lib, ptr, bounds[-1]), bounds
 
     def lev_ngrams_begin(self, seq, pattern, k):
         """Launch lev_ngrams and return; lev_ngrams_end() delivers the result of the OLDEST search in flight.

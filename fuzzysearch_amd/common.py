@@ -203,6 +203,22 @@ def matches_from_rows(rows, sequence):
         rows.release()
 
 
+def matches_from_rows_multi(rows, bounds, sequence):
+    """The result buffer of a multi-pattern C-ABI call (_native.OwnedRows holding every pattern's rows, bounds[i] ..
+    bounds[i + 1] those of pattern i) -> one list of Match per pattern, built like matches_from_rows; the buffer is released."""
+    try:
+        out = []
+        if _fzmatch is not None:
+            base = rows.address
+            for lo, hi in zip(bounds[:-1], bounds[1:]):
+                out.append(_fzmatch.make_matches_at(base + 24 * lo, hi - lo, sequence, 0) if hi > lo else [])
+            return out
+        arr = rows.to_array()
+        return [RawMatches(arr[lo:hi], sequence).materialize() for lo, hi in zip(bounds[:-1], bounds[1:])]
+    finally:
+        rows.release()
+
+
 def _rows_of(matches):
     return [(m.start, m.end, m.dist) for m in matches]
 

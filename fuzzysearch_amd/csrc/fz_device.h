@@ -1009,3 +1009,120 @@ struct FzSeqView {
     uint64_t buf_off;
     FZ_HD uint8_t at(uint64_t gidx) const { return buf[gidx - buf_off]; }
 };
+
+// ---------------------------------------------------------------------------------------------
+// Multi-pattern search (fz_lev_ngrams_multi): ONE pass over the sequence tests every byte offset against the n-gram
+// blocks of a GROUP of patterns that share the n-gram length L (fz_kernels.h: fz_mp_filter_kernel / fz_mp_verify_kernel).
+//
+// Batched domain of a pattern (everything else takes the single-pattern route inside the same call):
+//     1 <= k <= FZ_MP_MAX_K,   m <= FZ_MP_MAX_M,   L = m / (k + 1) >= FZ_MP_MIN_L
+// A group holds at most FZ_MP_MAX_PATS patterns with together at most FZ_MP_MAX_BLOCKS blocks.
+//
+// The filter's table, built per group on the host (fz_mp_build) and copied to LDS by every workgroup:
+//   sig    a signature of 2^16 bits (8 KiB): bit fz_mp_sig_bit(h) is set for the hash h of every block's n-gram.  One LDS
+//          dword read per byte offset; a random dword of 2048 spreads over the 64 banks like any random lookup (the scan
+//          kernel's one-slot-per-bank table cannot hold 256 n-grams).
+//   slots  FZ_MP_SLOTS open-addressed {hash, first entry | count << 16} pairs (linear probing, load <= 1/2): an offset whose
+//          signature bit is set looks its full 32-bit hash up here; equal hashes (equal n-grams of several patterns or
+//          blocks, or a true 32-bit collision) share one slot and name a RUN of entries.
+//   ent    the group's block table, sorted by hash: pattern id | block number << 8 | block start s << 16.
+// h covers the first min(L, 8) bytes of the window exactly as fz_hash_windows does (x = bytes [0, 4), yh = the three bytes
+// that end at byte min(L, 8)), so the filter may over-report (a hash is no comparison) and never misses: every occurrence
+// of a block's n-gram has that block's hash, its signature bit is set and its slot is found.  The verify kernel confirms the
+// n-gram exactly.
+#define FZ_MP_MAX_PATS 64u
+#define FZ_MP_MAX_BLOCKS 256u
+#define FZ_MP_MAX_M 128u
+#define FZ_MP_MAX_K 8u
+#define FZ_MP_MIN_L 4u
+#define FZ_MP_SIG_BITS 16u
+#define FZ_MP_SIG_WORDS (1u << (FZ_MP_SIG_BITS - 5u))
+#define FZ_MP_SLOTS 512u
+#define FZ_MP_HASH_K 0x9e3779u                   // odd 24-bit multiplier of the window hash (one v_mad_u32_u24 per offset)
+// descriptor in HBM, in dwords: what the filter copies, then what the verification copies
+#define FZ_MP_DESC_SLOTS FZ_MP_SIG_WORDS
+#define FZ_MP_DESC_ENT (FZ_MP_DESC_SLOTS + 2u * FZ_MP_SLOTS)
+#define FZ_MP_DESC_M (FZ_MP_DESC_ENT + FZ_MP_MAX_BLOCKS)
+#define FZ_MP_DESC_PAT (FZ_MP_DESC_M + FZ_MP_MAX_PATS)
+#define FZ_MP_DESC_WORDS (FZ_MP_DESC_PAT + FZ_MP_MAX_PATS * FZ_MP_MAX_M / 4u)
+#define FZ_MP_FILTER_WORDS FZ_MP_DESC_ENT        // sig + slots
+#define FZ_MP_VERIFY_WORDS (FZ_MP_DESC_WORDS - FZ_MP_DESC_ENT)
+
+FZ_HD uint32_t fz_mp_dh(uint32_t L) { return (L < 8u ? L : 8u) - 3u; }           // byte offset of the hash's second window
+FZ_HD uint32_t fz_mp_hash(uint32_t x, uint32_t yh) { return fz_hash_windows(x, yh, FZ_MP_HASH_K); }
+FZ_HD uint32_t fz_mp_sig_bit(uint32_t h) { return (h ^ (h >> 16)) & ((1u << FZ_MP_SIG_BITS) - 1u); }
+FZ_HD uint32_t fz_mp_slot(uint32_t h) { return (h * 0x9e3779b1u) >> 23; }        // 9 bits: FZ_MP_SLOTS
+FZ_HD uint32_t fz_mp_entry(uint32_t pid, uint32_t g, uint32_t s) { return pid | (g << 8) | (s << 16); }
+
+// The hash of the window that starts at w (at least min(L, 8) readable bytes).
+FZ_HD uint32_t fz_mp_hash_bytes(const uint8_t *w, uint32_t L) {
+    const uint32_t dh = fz_mp_dh(L);
+    const uint32_t x = (uint32_t)w[0] | ((uint32_t)w[1] << 8) | ((uint32_t)w[2] << 16) | ((uint32_t)w[3] << 24);
+    const uint32_t yh = (uint32_t)w[dh] | ((uint32_t)w[dh + 1] << 8) | ((uint32_t)w[dh + 2] << 16);
+    return fz_mp_hash(x, yh);
+}
+
+FZ_HD bool fz_mp_sig_test(const uint32_t *sig, uint32_t h) {
+    const uint32_t t = fz_mp_sig_bit(h);
+    return ((sig[t >> 5] >> (t & 31u)) & 1u) != 0;
+}
+
+// -> first entry | count << 16 of the run of entries whose hash is h; 0: none.
+FZ_HD uint32_t fz_mp_lookup(const uint32_t *slots, uint32_t h) {
+    uint32_t s = fz_mp_slot(h);
+    for (;;) {
+        const uint32_t e = slots[2u * s + 1u];
+        if ((e >> 16) == 0u) return 0u;                                          // an empty slot ends the probe
+        if (slots[2u * s] == h) return e;
+        s = (s + 1u) & (FZ_MP_SLOTS - 1u);
+    }
+}
+
+// Host: the descriptor of a group.  pat[i] / m[i] = pattern i (npat <= FZ_MP_MAX_PATS, each inside the batched domain for
+// this k and L); desc = FZ_MP_DESC_WORDS dwords.  -> number of entries (blocks), 0 when they exceed FZ_MP_MAX_BLOCKS.
+inline uint32_t fz_mp_build(uint32_t *desc, const uint8_t *const *pat, const uint32_t *m, uint32_t npat, uint32_t L) {
+    for (uint32_t i = 0; i < FZ_MP_DESC_WORDS; ++i) desc[i] = 0u;
+    uint32_t hs[FZ_MP_MAX_BLOCKS], es[FZ_MP_MAX_BLOCKS], n = 0;
+    for (uint32_t i = 0; i < npat; ++i) {
+        uint32_t g = 0;
+        for (uint32_t s = 0; s + L <= m[i]; s += L, ++g) {
+            if (n == FZ_MP_MAX_BLOCKS) return 0u;
+            hs[n] = fz_mp_hash_bytes(pat[i] + s, L);
+            es[n] = fz_mp_entry(i, g, s);
+            ++n;
+        }
+        desc[FZ_MP_DESC_M + i] = m[i];
+        uint8_t *dst = reinterpret_cast<uint8_t *>(desc + FZ_MP_DESC_PAT) + i * FZ_MP_MAX_M;
+        for (uint32_t q = 0; q < m[i]; ++q) dst[q] = pat[i][q];
+    }
+    for (uint32_t i = 1; i < n; ++i) {                                           // insertion sort by hash: runs of equal hashes
+        const uint32_t h = hs[i], e = es[i];
+        uint32_t j = i;
+        for (; j > 0 && hs[j - 1] > h; --j) { hs[j] = hs[j - 1]; es[j] = es[j - 1]; }
+        hs[j] = h; es[j] = e;
+    }
+    uint32_t *slots = desc + FZ_MP_DESC_SLOTS;
+    for (uint32_t i = 0; i < n;) {
+        uint32_t j = i;
+        while (j < n && hs[j] == hs[i]) ++j;
+        const uint32_t t = fz_mp_sig_bit(hs[i]);
+        desc[t >> 5] |= 1u << (t & 31u);
+        uint32_t s = fz_mp_slot(hs[i]);
+        while ((slots[2u * s + 1u] >> 16) != 0u) s = (s + 1u) & (FZ_MP_SLOTS - 1u);
+        slots[2u * s] = hs[i];
+        slots[2u * s + 1u] = i | ((j - i) << 16);
+        i = j;
+    }
+    for (uint32_t i = 0; i < n; ++i) desc[FZ_MP_DESC_ENT + i] = es[i];
+    return n;
+}
+
+// Arguments of the two multi-pattern kernels.
+struct FzMpArgs {
+    FzGeom   geom;
+    uint32_t k, L;
+    uint32_t win_dwords;                         // window dwords staged per lane ((longest m + 2k + 6) / 4 + 1)
+    uint32_t nent;                               // entries of the block table
+    uint64_t hit_cap;                            // capacity of EACH of the FZ_MP_LISTS hit lists
+    uint64_t rec_cap;
+};

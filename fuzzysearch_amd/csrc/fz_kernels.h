@@ -2503,3 +2503,198 @@ __global__ __launch_bounds__(256) void fz_hamming_kernel(const uint8_t *__restri
         }
     }
 }
+
+// ---------------------------------------------------------------------------------------------
+// Multi-pattern search (fz_device.h: the fz_mp_* table).  Two kernels per group of patterns, whatever their number:
+//
+//   fz_mp_filter_kernel  one streaming pass in fz_scan_kernel's layout (16 KiB tiles, a 16-byte load + 8-byte halo per lane
+//       and row).  Per byte offset: the window hash (two v_alignbyte, one v_mad_u32_u24), one LDS dword of the signature, one
+//       bit test.  With hundreds of n-grams "some lane fired" is the common case, not the rare one, so survivors do not go
+//       through a wave-uniform branch per group of offsets and a queue of positions to re-check: every offset of a row has
+//       its own ballot, a fired offset looks its full hash up in the slot table (the signature's false positives end here)
+//       and the run of block-table entries it names is compacted by ballot / mbcnt into the wave's queue of finished hits
+//       (entry << 48 | global index).  A full queue is appended to a hit list in HBM with ONE atomic; the workgroups spread
+//       over FZ_MP_LISTS lists with counters a cache line apart (a single counter word sustains ~90 atomics/us chip-wide:
+//       5e7 hits per GiB in queues of 256 would spend 2 ms on one word).
+//       LDS: 12 KiB of table + 4 x 2 KiB of queues = 20 KiB per workgroup, 8 workgroups per CU.
+//   fz_mp_verify_kernel  the hit lists, one candidate per lane, 64 at a time, as fz_verify_kernel does for one pattern — the
+//       acceptance range of the block (fz_block_range + ownership), the window staged in LDS, the exact n-gram test, then
+//       fz_verify_lev (right, then left, last arg-min) — against the LANE's pattern: bytes and length come from the group's
+//       pattern table in LDS, the block's start from its block-table entry.  Records carry the pattern id in `aux`.
+#define FZ_MP_LISTS 16u
+#define FZ_MP_QCAP 256u                                    // hits a wave queues before it appends them
+#define FZ_MP_CTR_WORDS 512u                               // 64-bit counters of a group launch:
+#define FZ_MP_CTR_RECS 1u                                  //   [1] records, [8 .. 71] confirmed-hit tallies,
+#define FZ_MP_CTR_LIST(l) (128u + 16u * (l))               //   [128 + 16 l] hits appended to list l (128 bytes apart)
+#define FZ_MP_FILTER_LDS (FZ_MP_FILTER_WORDS * 4u + FZ_WAVES_PER_BLOCK * FZ_MP_QCAP * 8u)
+#define FZ_MP_RING_SLOTS (2u * FZ_MP_MAX_K + 2u)           // score ring of fz_expand (budgets above FZ_REG_BAND_MAX only)
+
+__host__ __device__ inline uint32_t fz_mp_verify_wave_bytes(uint32_t win_dwords) { return win_dwords * 256u + FZ_MP_RING_SLOTS * 128u; }
+__host__ __device__ inline uint32_t fz_mp_verify_lds(uint32_t win_dwords) {
+    return FZ_MP_VERIFY_WORDS * 4u + FZ_WAVES_PER_BLOCK * fz_mp_verify_wave_bytes(win_dwords);
+}
+
+template <int DH>
+__global__ __launch_bounds__(FZ_FILTER_THREADS) void fz_mp_filter_kernel(const uint8_t *__restrict__ buf, const FzMpArgs a, uint64_t ntiles,
+                                                                         const uint32_t *__restrict__ desc, uint64_t *__restrict__ hits,
+                                                                         unsigned long long *__restrict__ counters) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    uint32_t *sig = reinterpret_cast<uint32_t *>(smem);
+    const uint32_t *slots = sig + FZ_MP_DESC_SLOTS;
+    for (uint32_t i = threadIdx.x; i < FZ_MP_FILTER_WORDS; i += FZ_FILTER_THREADS) sig[i] = desc[i];
+    __syncthreads();
+    const uint32_t wave = fz_uniform(threadIdx.x >> 6);
+    const uint32_t lane = fz_lane();
+    const uint32_t lane_off = threadIdx.x * 16u;
+    uint64_t *queue = reinterpret_cast<uint64_t *>(smem + FZ_MP_FILTER_WORDS * 4u) + wave * FZ_MP_QCAP;
+    const uint32_t list = blockIdx.x % FZ_MP_LISTS;
+    uint64_t *lhits = hits + (uint64_t)list * a.hit_cap;
+    unsigned long long *lctr = counters + FZ_MP_CTR_LIST(list);
+    const uint64_t data_end = a.geom.buf_off + a.geom.buf_len;
+    uint32_t qn = 0;                                       // wave-uniform queue fill
+
+    auto flush = [&]() {
+        fz_wave_lds_sync();
+        unsigned long long base = 0;
+        if (lane == 0) base = atomicAdd(lctr, (unsigned long long)qn);
+        base = fz_bcast64(base);
+        for (uint32_t i = lane; i < qn; i += 64u)
+            if (base + i < a.hit_cap) lhits[base + i] = queue[i];      // (an overflowing list: the counter tells, the host re-runs)
+        qn = 0;
+        fz_wave_lds_sync();
+    };
+
+    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const uint8_t *tsrc = buf + fz_bcast64(tile * (uint64_t)FZ_TILE_BYTES);
+        uint4 v[FZ_FILTER_ROWS];
+        uint2 hl[FZ_FILTER_ROWS];
+#pragma unroll
+        for (int r = 0; r < FZ_FILTER_ROWS; ++r) {
+            v[r] = *reinterpret_cast<const uint4 *>(tsrc + r * FZ_ROW_BYTES + lane_off);
+            hl[r] = *reinterpret_cast<const uint2 *>(tsrc + r * FZ_ROW_BYTES + lane_off + 16);
+        }
+        const uint64_t gtile = a.geom.buf_off + tile * (uint64_t)FZ_TILE_BYTES + lane_off;
+#pragma unroll
+        for (int r = 0; r < FZ_FILTER_ROWS; ++r) {
+            const uint32_t w[7] = {v[r].x, v[r].y, v[r].z, v[r].w, hl[r].x, hl[r].y, 0u};
+            uint32_t hv[16];
+            uint32_t fired = 0;
+#pragma unroll
+            for (int o = 0; o < 16; ++o) {
+                hv[o] = __umul24(FZ_WIN(w, o + DH), FZ_MP_HASH_K) + FZ_WIN(w, o);
+                const uint32_t t = fz_mp_sig_bit(hv[o]);
+                fired |= ((sig[t >> 5] >> (t & 31u)) & 1u) << o;
+            }
+            if (!__ballot(fired != 0u)) continue;
+#pragma unroll
+            for (int o = 0; o < 16; ++o) {
+                const bool f = ((fired >> o) & 1u) != 0u;
+                if (!__ballot(f)) continue;
+                const uint64_t gidx = gtile + (uint64_t)(r * FZ_ROW_BYTES + o);
+                uint32_t e = 0;
+                if (f && gidx >= a.geom.own_lo && gidx < a.geom.own_hi && gidx + a.L <= data_end) e = fz_mp_lookup(slots, hv[o]);
+                uint32_t first = e & 0xffffu, cnt = e >> 16;
+                for (;;) {
+                    const unsigned long long mk = __ballot(cnt != 0u);
+                    if (!mk) break;
+                    if (qn + 64u > FZ_MP_QCAP) flush();
+                    if (cnt != 0u) queue[qn + fz_rank(mk)] = fz_hit_pack(first, gidx);
+                    qn += (uint32_t)__popcll(mk);
+                    if (cnt != 0u) { ++first; --cnt; }
+                }
+            }
+        }
+    }
+    if (qn) flush();
+}
+
+__global__ __launch_bounds__(FZ_FILTER_THREADS) void fz_mp_verify_kernel(const uint8_t *__restrict__ buf, const FzMpArgs a,
+                                                                         const uint32_t *__restrict__ desc, const uint64_t *__restrict__ hits,
+                                                                         FzRec *__restrict__ recs, unsigned long long *__restrict__ counters) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    uint32_t *tab = reinterpret_cast<uint32_t *>(smem);
+    for (uint32_t i = threadIdx.x; i < FZ_MP_VERIFY_WORDS; i += FZ_FILTER_THREADS) tab[i] = desc[FZ_MP_DESC_ENT + i];
+    __syncthreads();
+    const uint32_t *ent = tab;
+    const uint32_t *pm = tab + (FZ_MP_DESC_M - FZ_MP_DESC_ENT);
+    const uint8_t *pats = reinterpret_cast<const uint8_t *>(tab + (FZ_MP_DESC_PAT - FZ_MP_DESC_ENT));
+    const uint32_t lane = fz_lane();
+    uint8_t *wbytes = smem + FZ_MP_VERIFY_WORDS * 4u + (threadIdx.x >> 6) * fz_mp_verify_wave_bytes(a.win_dwords);
+    uint32_t *win = reinterpret_cast<uint32_t *>(wbytes);
+    uint16_t *ring = reinterpret_cast<uint16_t *>(wbytes + a.win_dwords * 256u);
+    const uint64_t waves = (uint64_t)gridDim.x * FZ_WAVES_PER_BLOCK;
+    const uint64_t wave = (uint64_t)blockIdx.x * FZ_WAVES_PER_BLOCK + (threadIdx.x >> 6);
+    const uint64_t n = a.geom.n;
+    const uint64_t data_end = a.geom.buf_off + a.geom.buf_len;
+    uint32_t confirmed = 0;
+    for (uint32_t l = 0; l < FZ_MP_LISTS; ++l) {
+        unsigned long long nh = counters[FZ_MP_CTR_LIST(l)];
+        if (nh > a.hit_cap) nh = a.hit_cap;
+        const uint64_t *lh = hits + (uint64_t)l * a.hit_cap;
+        // (the lists start at different waves: a short list keeps other waves busy than its neighbour's)
+        for (uint64_t q0 = ((wave + 251u * l) % waves) * 64u; q0 < nh; q0 += waves * 64u) {
+            const uint64_t q = q0 + lane;
+            const bool have = q < nh;
+            const uint64_t hit = have ? lh[q] : 0ull;
+            const uint32_t e = ent[fz_hit_block(hit) & (FZ_MP_MAX_BLOCKS - 1u)];
+            const uint32_t pid = e & 0xffu, g = (e >> 8) & 0xffu, s = e >> 16;
+            const uint32_t m = pm[pid & (FZ_MP_MAX_PATS - 1u)];
+            const uint8_t *p = pats + (pid & (FZ_MP_MAX_PATS - 1u)) * FZ_MP_MAX_M;
+            const uint64_t idx = fz_hit_index(hit);
+            // acceptance range of the block (levenshtein_ngram.py:171-176) in the whole sequence [0, n), and ownership
+            uint32_t lo_rel, hi_sub;
+            fz_block_range(FZ_MODE_LEV, m, a.k, a.L, s, lo_rel, hi_sub);
+            bool valid = have && fz_hit_block(hit) < a.nent && m != 0u && idx >= lo_rel && n >= hi_sub && idx + a.L <= n - hi_sub &&
+                         idx >= a.geom.own_lo && idx < a.geom.own_hi && idx >= a.geom.buf_off && idx + a.L <= data_end;
+            if (!__ballot(valid)) continue;
+            // the window [max(0, idx - s - k), min(n, idx - s + m + k)) clipped to the buffer, dword-aligned, into LDS
+            const uint64_t reach = (uint64_t)s + a.k;
+            uint64_t wlo = idx > reach ? idx - reach : 0ull;
+            if (wlo < a.geom.buf_off) wlo = a.geom.buf_off;
+            const uint64_t wbase = a.geom.buf_off + ((wlo - a.geom.buf_off) & ~(uint64_t)3);
+            uint64_t whi = idx - s + m + a.k;
+            if (whi > data_end) whi = data_end;
+            if (whi > n) whi = n;
+            uint32_t nd = valid ? (uint32_t)((whi - wbase + 3) >> 2) : 0u;
+            if (nd > a.win_dwords) nd = a.win_dwords;
+            const int64_t lbase = (int64_t)(wbase - a.geom.buf_off);
+            for (uint32_t d0 = 0; d0 < a.win_dwords; d0 += 8) {
+                uint32_t x[8];
+#pragma unroll
+                for (uint32_t j = 0; j < 8; ++j)
+                    x[j] = (d0 + j < nd) ? *reinterpret_cast<const uint32_t *>(buf + lbase + (int64_t)(d0 + j) * 4) : 0u;
+#pragma unroll
+                for (uint32_t j = 0; j < 8; ++j)
+                    if (d0 + j < nd) win[(d0 + j) * 64u + lane] = x[j];
+            }
+            fz_wave_lds_sync();
+            const FzLdsWindow t{reinterpret_cast<const uint8_t *>(win + lane), wbase, 256u};
+            if (valid) {
+                const uint8_t *ng = p + s;
+                for (uint32_t b = 0; b < a.L; ++b)
+                    if (ng[b] != t.at(idx + b)) { valid = false; break; }
+            }
+            confirmed += (uint32_t)__popcll(__ballot(valid));
+            FzRec rec;
+            bool ok = false;
+            if (valid) {
+                FzLdsScores sc{ring + lane, 64u};
+                ok = fz_verify_lev<FZ_REG_BAND_MAX>(sc, t, 0ull, n, p, m, a.k, a.L, s, idx, rec);
+            }
+            const unsigned long long mask = __ballot(ok);
+            if (mask) {
+                unsigned long long base = 0;
+                if (lane == 0) base = atomicAdd(&counters[FZ_MP_CTR_RECS], (unsigned long long)__popcll(mask));
+                base = fz_bcast64(base);
+                if (ok) {
+                    rec.key = fz_hit_pack(g, idx);
+                    rec.aux = pid;
+                    const unsigned long long slot = base + fz_rank(mask);
+                    if (slot < a.rec_cap) recs[slot] = rec;
+                }
+            }
+            fz_wave_lds_sync();
+        }
+    }
+    if (lane == 0 && confirmed) atomicAdd(&counters[8u + (blockIdx.x & 63u)], (unsigned long long)confirmed);
+}

@@ -201,6 +201,11 @@ struct DevState {
     int lp_end_event = 2;                        // which event marks the end of the last automaton kernel (2, or 3 = the completion)
     uint8_t *d_pat = nullptr;                    // pattern in HBM (subsequences longer than FZ_MAX_M, fz_verify_big_kernel)
     uint64_t pat_cap = 0;
+    // multi-pattern search (fz_lev_ngrams_multi): the group descriptor and the counters (fixed sizes, allocated on first use),
+    // FZ_MP_LISTS hit lists of mp_hit_cap entries each and mp_rec_cap records — buffers of their own, so that nothing the
+    // single-pattern searches keep between calls (zeroed headers, result slots, the direct mode) is touched
+    uint8_t *d_mp_desc = nullptr, *d_mp_ctr = nullptr, *d_mp_hits = nullptr, *d_mp_recs = nullptr;
+    uint64_t mp_hit_cap = 0, mp_rec_cap = 0;
     int slot_id = 0;                             // which of the two result slots is the current one
     uint32_t launches_used = 0;                  // scan launches of the last enqueue on this device
     // Two fused searches in flight: the younger one's scan on the stream the older one does not use, so that it starts
@@ -2263,6 +2268,7 @@ static void devstate_destroy(DevState &d) {
     if (d.h_big) (void)hipHostFree(d.h_big);
     if (d.d_cand) (void)hipFree(d.d_cand);
     if (d.d_pat) (void)hipFree(d.d_pat);
+    for (uint8_t *mp : {d.d_mp_desc, d.d_mp_ctr, d.d_mp_hits, d.d_mp_recs}) if (mp) (void)hipFree(mp);
     if (d.d_gen_order) (void)hipFree(d.d_gen_order);
     if (d.d_gen_rows) (void)hipFree(d.d_gen_rows);
     if (d.d_gen_dedup) (void)hipFree(d.d_gen_dedup);
@@ -2612,6 +2618,330 @@ int fz_lev_ngrams_consolidated(fz_ctx *ctx, fz_seq *seq, const uint8_t *p, uint3
     rc = fz_consolidate(raw, nraw, out, n);
     release_out(raw);
     return rc;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Multi-pattern search: many patterns, one budget, one resident sequence, as few passes over it as the patterns allow
+// (fz_device.h: the fz_mp_* table; fz_kernels.h: fz_mp_filter_kernel / fz_mp_verify_kernel).
+
+// Where every pattern of a list rides: a function of the arguments alone.  Patterns inside the batched domain are grouped by
+// their n-gram length L = m / (k + 1) in input order; a group is closed when the next pattern of its L would take it beyond
+// FZ_MP_MAX_PATS patterns or FZ_MP_MAX_BLOCKS blocks.  A group of one pattern, and every pattern outside the domain, takes
+// the single-pattern route, and so does a group that the cost rule below gives to the loop.  Groups are numbered in the order
+// of their first pattern.
+struct MpGroup { uint32_t L = 0, blocks = 0; std::vector<uint32_t> pats; };
+
+static bool mp_in_domain(uint32_t m, uint32_t k) {
+    return k >= 1 && k <= FZ_MP_MAX_K && m <= FZ_MP_MAX_M && m / (k + 1) >= FZ_MP_MIN_L;
+}
+
+// Is one pass for the group expected to beat one search per pattern?  Both sides in ms per GiB, from the measurement of
+// profiles/r08_multi_pattern.txt (1 GiB of DNA), as functions of the arguments: P patterns, G blocks and
+// the project's estimate of expected candidates, C = G / sigma^L of the offsets (sigma = distinct symbols of the group's
+// patterns), in millions per GiB:
+//     one pass      kMpPass + kMpPerBlock G + kMpPerCand C     (the filter's rare path grows with the blocks, the hit list
+//                                                                and the lane-per-candidate verification with the candidates)
+//     the loop      kLoopScan P + kLoopPerCand C               (a scan per pattern; its fused verification per candidate)
+// The group rides one pass when that is expected to cost less than kMpMargin of the loop.
+constexpr double kMpPass = 0.50, kMpPerBlock = 0.0098, kMpPerCand = 0.085;
+constexpr double kLoopScan = 0.185, kLoopPerCand = 0.032;
+constexpr double kMpMargin = 0.9;
+
+static bool mp_worth_a_pass(const uint8_t *pats, const uint64_t *offs, const MpGroup &g) {
+    bool seen[256] = {false};
+    uint32_t sigma = 0;
+    for (uint32_t i : g.pats)
+        for (uint64_t q = offs[i]; q < offs[i + 1]; ++q)
+            if (!seen[pats[q]]) { seen[pats[q]] = true; ++sigma; }
+    double frac = (double)g.blocks;
+    for (uint32_t i = 0; i < g.L && frac > 1e-12; ++i) frac /= (double)sigma;
+    const double cand = std::min(frac, (double)g.blocks) * 1073.741824;      // millions per GiB
+    const double pass = kMpPass + kMpPerBlock * g.blocks + kMpPerCand * cand;
+    const double loop = kLoopScan * (double)g.pats.size() + kLoopPerCand * cand;
+    return pass < kMpMargin * loop;
+}
+
+static void mp_plan(const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k, std::vector<MpGroup> &groups,
+                    std::vector<uint32_t> &group_of) {
+    groups.clear();
+    group_of.assign(n_pats, 0xffffffffu);
+    std::vector<MpGroup> open;                                  // at most one open group per L
+    std::vector<MpGroup> closed;
+    auto close = [&](MpGroup &g) { if (g.pats.size() > 1 && mp_worth_a_pass(pats, offs, g)) closed.push_back(g); };
+    for (uint32_t i = 0; i < n_pats; ++i) {
+        const uint64_t m64 = offs[i + 1] - offs[i];
+        if (m64 > FZ_MP_MAX_M || !mp_in_domain((uint32_t)m64, k)) continue;
+        const uint32_t m = (uint32_t)m64, L = m / (k + 1), nb = m / L;
+        MpGroup *g = nullptr;
+        for (MpGroup &o : open) if (o.L == L) g = &o;
+        if (g && (g->pats.size() + 1 > FZ_MP_MAX_PATS || g->blocks + nb > FZ_MP_MAX_BLOCKS)) {
+            close(*g);
+            g->pats.clear();
+            g->blocks = 0;
+        }
+        if (!g) { open.emplace_back(); g = &open.back(); g->L = L; }
+        g->pats.push_back(i);
+        g->blocks += nb;
+    }
+    for (MpGroup &o : open) close(o);
+    std::sort(closed.begin(), closed.end(), [](const MpGroup &x, const MpGroup &y) { return x.pats[0] < y.pats[0]; });
+    groups.swap(closed);
+    for (uint32_t gi = 0; gi < groups.size(); ++gi)
+        for (uint32_t i : groups[gi].pats) group_of[i] = gi;
+}
+
+static int mp_ensure(DevState &d, uint64_t hit_cap, uint64_t rec_cap) {
+    HIP_TRY(hipSetDevice(d.device));
+    if (!d.d_mp_desc) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d.d_mp_desc), FZ_MP_DESC_WORDS * 4u));
+    if (!d.d_mp_ctr) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d.d_mp_ctr), FZ_MP_CTR_WORDS * 8u));
+    if (d.mp_hit_cap < hit_cap) {
+        if (d.d_mp_hits) { HIP_TRY(hipFree(d.d_mp_hits)); d.d_mp_hits = nullptr; d.mp_hit_cap = 0; }
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d.d_mp_hits), (size_t)FZ_MP_LISTS * hit_cap * sizeof(uint64_t)));
+        d.mp_hit_cap = hit_cap;
+    }
+    if (d.mp_rec_cap < rec_cap) {
+        if (d.d_mp_recs) { HIP_TRY(hipFree(d.d_mp_recs)); d.d_mp_recs = nullptr; d.mp_rec_cap = 0; }
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d.d_mp_recs), (size_t)rec_cap * sizeof(FzRec)));
+        d.mp_rec_cap = rec_cap;
+    }
+    return FZ_OK;
+}
+
+struct MpTotals { uint64_t bytes = 0, hits = 0, rows = 0; uint32_t launches = 0; double filter_ms = 0, verify_ms = 0; };
+
+// One group over one shard: descriptor up, filter, verification, counters and records back.  Capacities come from the
+// arguments — the project's estimate of expected candidates, sequence bytes x blocks / sigma^L (sigma = distinct symbols
+// of the group's patterns), twice over and spread over the lists; a launch that overflows a list or the record buffer is
+// run again with what its counters ask for.
+static int mp_run_shard(fz_ctx *ctx, const Shard &sh, const uint32_t *desc, uint32_t nent, uint32_t k, uint32_t L, uint32_t max_m,
+                        uint32_t sigma, std::vector<FzRec> &recs, MpTotals &tot) {
+    DevState &d = ctx->devs[sh.dev];
+    const uint64_t ntiles = (sh.geom.buf_len + FZ_TILE_BYTES - 1) / FZ_TILE_BYTES;
+    tot.bytes += sh.geom.buf_len;
+    if (ntiles == 0) return FZ_OK;
+    double expect = (double)sh.geom.buf_len * (double)nent;
+    for (uint32_t i = 0; i < L && expect > 1.0; ++i) expect /= (double)sigma;
+    uint64_t hit_cap = std::max<uint64_t>(4096, (uint64_t)(2.0 * expect / FZ_MP_LISTS) + 1024);
+    uint64_t rec_cap = 1u << 16;
+    FzMpArgs a;
+    memset(&a, 0, sizeof a);
+    a.geom = sh.geom;
+    a.k = k; a.L = L; a.nent = nent;
+    a.win_dwords = (max_m + 2 * k + 6) / 4 + 1;
+    using FilterKernel = void (*)(const uint8_t *, const FzMpArgs, uint64_t, const uint32_t *, uint64_t *, unsigned long long *);
+    static const FilterKernel filters[6] = {nullptr, fz_mp_filter_kernel<1>, fz_mp_filter_kernel<2>, fz_mp_filter_kernel<3>,
+                                            fz_mp_filter_kernel<4>, fz_mp_filter_kernel<5>};
+    const FilterKernel fk = filters[fz_mp_dh(L)];
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(ntiles, (uint64_t)d.n_cus * 8);
+    for (int attempt = 0; attempt < 4; ++attempt) {
+        int rc = mp_ensure(d, hit_cap, rec_cap);
+        if (rc) return rc;
+        a.hit_cap = d.mp_hit_cap;
+        a.rec_cap = d.mp_rec_cap;
+        const uint32_t *ddesc = reinterpret_cast<const uint32_t *>(d.d_mp_desc);
+        unsigned long long *dctr = reinterpret_cast<unsigned long long *>(d.d_mp_ctr);
+        HIP_TRY(hipMemcpyAsync(d.d_mp_desc, desc, FZ_MP_DESC_WORDS * 4u, hipMemcpyHostToDevice, d.stream));
+        HIP_TRY(hipMemsetAsync(d.d_mp_ctr, 0, FZ_MP_CTR_WORDS * 8u, d.stream));
+        if (ctx->timing) HIP_TRY(hipEventRecord(d.ev[0], d.stream));
+        hipLaunchKernelGGL(fk, dim3(grid), dim3(FZ_FILTER_THREADS), FZ_MP_FILTER_LDS, d.stream, sh.d_buf, a, ntiles, ddesc,
+                           reinterpret_cast<uint64_t *>(d.d_mp_hits), dctr);
+        HIP_TRY(hipGetLastError());
+        if (ctx->timing) HIP_TRY(hipEventRecord(d.ev[1], d.stream));
+        hipLaunchKernelGGL(fz_mp_verify_kernel, dim3((uint32_t)d.n_cus * 4), dim3(FZ_FILTER_THREADS), fz_mp_verify_lds(a.win_dwords), d.stream,
+                           sh.d_buf, a, ddesc, reinterpret_cast<const uint64_t *>(d.d_mp_hits), reinterpret_cast<FzRec *>(d.d_mp_recs), dctr);
+        HIP_TRY(hipGetLastError());
+        if (ctx->timing) HIP_TRY(hipEventRecord(d.ev[2], d.stream));
+        unsigned long long ctr[FZ_MP_CTR_WORDS];
+        HIP_TRY(hipMemcpyAsync(ctr, d.d_mp_ctr, sizeof ctr, hipMemcpyDeviceToHost, d.stream));
+        HIP_TRY(hipStreamSynchronize(d.stream));
+        ++tot.launches;
+        if (ctx->timing) {
+            float f = 0, v = 0;
+            if (hipEventElapsedTime(&f, d.ev[0], d.ev[1]) == hipSuccess) tot.filter_ms += f;
+            if (hipEventElapsedTime(&v, d.ev[1], d.ev[2]) == hipSuccess) tot.verify_ms += v;
+            (void)hipGetLastError();
+        }
+        uint64_t need_hits = 0;
+        for (uint32_t l = 0; l < FZ_MP_LISTS; ++l) need_hits = std::max<uint64_t>(need_hits, ctr[FZ_MP_CTR_LIST(l)]);
+        const uint64_t nr = ctr[FZ_MP_CTR_RECS];
+        if (need_hits > a.hit_cap || nr > a.rec_cap) {
+            hit_cap = std::max(hit_cap, need_hits);
+            // (records of a run whose hit lists were cut short are a lower bound: leave room for as many again)
+            rec_cap = std::max(rec_cap, need_hits > a.hit_cap ? 2 * nr : nr);
+            continue;
+        }
+        const size_t at = recs.size();
+        recs.resize(at + nr);
+        if (nr) HIP_TRY(hipMemcpy(recs.data() + at, d.d_mp_recs, nr * sizeof(FzRec), hipMemcpyDeviceToHost));
+        uint64_t confirmed = 0, appended = 0;
+        for (uint32_t i = 0; i < 64; ++i) confirmed += ctr[8 + i];
+        for (uint32_t l = 0; l < FZ_MP_LISTS; ++l) appended += ctr[FZ_MP_CTR_LIST(l)];
+        tot.hits += confirmed;
+        if (sw().trace)
+            fprintf(stderr, "[fz] multi group: %u blocks, %llu hits appended (%llu bytes written and read), %llu confirmed, %llu records\n",
+                    nent, (unsigned long long)appended, (unsigned long long)(16 * appended), (unsigned long long)confirmed, (unsigned long long)nr);
+        return FZ_OK;
+    }
+    return fail(FZ_EDEVICE, "result buffers kept overflowing");
+}
+
+static int mp_run_group(fz_ctx *ctx, fz_seq *seq, const uint8_t *pats, const uint64_t *offs, uint32_t k, const MpGroup &g,
+                        std::vector<std::vector<fz_match>> &rows, MpTotals &tot) {
+    const uint32_t np = (uint32_t)g.pats.size();
+    const uint8_t *pp[FZ_MP_MAX_PATS];
+    uint32_t pm[FZ_MP_MAX_PATS], max_m = 0;
+    bool seen[256] = {false};
+    uint32_t sigma = 0;
+    for (uint32_t j = 0; j < np; ++j) {
+        pp[j] = pats + offs[g.pats[j]];
+        pm[j] = (uint32_t)(offs[g.pats[j] + 1] - offs[g.pats[j]]);
+        max_m = std::max(max_m, pm[j]);
+        for (uint32_t q = 0; q < pm[j]; ++q) if (!seen[pp[j][q]]) { seen[pp[j][q]] = true; ++sigma; }
+    }
+    std::vector<uint32_t> desc(FZ_MP_DESC_WORDS);
+    const uint32_t nent = fz_mp_build(desc.data(), pp, pm, np, g.L);
+    if (nent == 0 || nent != g.blocks) return fail(FZ_EDEVICE, "internal: the group's block table does not match its plan");
+    std::vector<FzRec> recs;
+    for (const Shard &sh : seq->shards) {
+        int rc = mp_run_shard(ctx, sh, desc.data(), nent, k, g.L, max_m, std::max(1u, sigma), recs, tot);
+        if (rc) return rc;
+    }
+    // per pattern: its records (aux = the pattern's number in the group) in the reference's order — block ascending, hit
+    // index ascending, by the host ordering every search uses.  Shards own disjoint index ranges in global coordinates,
+    // so the records of all shards are ordered together.
+    std::vector<std::vector<FzRec>> per(np);
+    for (const FzRec &r : recs) {
+        if (r.aux >= np) return fail(FZ_EDEVICE, "internal: a record names pattern %u of a group of %u", r.aux, np);
+        per[r.aux].push_back(r);
+    }
+    for (uint32_t j = 0; j < np; ++j) {
+        for (FzRec &r : per[j]) r.aux = 0;
+        int rc = emit_matches(per[j].data(), per[j].size(), g.L, nullptr, nullptr, 0, 0, false, &rows[g.pats[j]]);
+        if (rc) return rc;
+        tot.rows += rows[g.pats[j]].size();
+    }
+    return FZ_OK;
+}
+
+static int mp_check_lists(const uint8_t *pats, const uint64_t *offs, uint32_t n_pats) {
+    if (n_pats && (!pats || !offs)) return fail(FZ_EINVAL, "null argument");
+    for (uint32_t i = 0; i < n_pats; ++i)
+        if (offs[i + 1] < offs[i]) return fail(FZ_EINVAL, "pattern offsets must not decrease");
+    return FZ_OK;
+}
+
+static int lev_multi_impl(fz_ctx *ctx, fz_seq *seq, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k,
+                          bool consolidated, fz_match **out, uint64_t **out_offs) {
+    if (!out || !out_offs) return fail(FZ_EINVAL, "null argument");
+    *out = nullptr; *out_offs = nullptr;
+    if (!ctx || !seq || seq->ctx != ctx) return fail(FZ_EINVAL, "bad ctx/seq handle");
+    if (ctx->npend) return fail(FZ_EINVAL, "a search started with fz_lev_ngrams_begin is still in flight");
+    if (ctx->stream_inflight) return fail(FZ_EINVAL, "a file stream of this context has a batch in flight (finish or close it first)");
+    int rc = mp_check_lists(pats, offs, n_pats);
+    if (rc) return rc;
+    // every pattern passes the single call's checks before anything is searched
+    for (uint32_t i = 0; i < n_pats; ++i) {
+        const uint64_t m = offs[i + 1] - offs[i];
+        if (m > FZ_MAX_M_ANY) return fail(FZ_EUNSUPPORTED, "subsequence longer than %u bytes", FZ_MAX_M_ANY);
+        Search q;
+        rc = lev_plan(ctx, seq, m ? pats + offs[i] : nullptr, (uint32_t)m, k, q);
+        if (rc) return rc;
+    }
+    std::vector<MpGroup> groups;
+    std::vector<uint32_t> group_of;
+    // a context in a communicator searches collectively, pattern by pattern, through the existing collective search
+    bool batched = !ctx->snapshot;
+    for (const Shard &sh : seq->shards) batched = batched && sh.geom.seg_stride == 0;
+    if (batched) mp_plan(pats, offs, n_pats, k, groups, group_of);
+    else group_of.assign(n_pats, 0xffffffffu);
+    std::vector<std::vector<fz_match>> rows(n_pats);
+    MpTotals tot;
+    uint32_t form = FZ_FORM_NONE;
+    for (uint32_t i = 0; i < n_pats; ++i) {
+        if (group_of[i] != 0xffffffffu) continue;
+        fz_match *one = nullptr;
+        uint64_t n_one = 0;
+        rc = fz_lev_ngrams(ctx, seq, pats + offs[i], (uint32_t)(offs[i + 1] - offs[i]), k, &one, &n_one);
+        if (rc) return rc;
+        rows[i].assign(one, one + n_one);
+        release_out(one);
+        tot.bytes += ctx->stats.bytes_scanned; tot.hits += ctx->stats.ngram_hits; tot.rows += n_one;
+        tot.launches += ctx->stats.filter_launches;
+        form = ctx->stats.verify_form;
+    }
+    ctx->view = nullptr; ctx->view_n = 0; ctx->rows_ready = false;
+    for (const MpGroup &g : groups) {
+        rc = mp_run_group(ctx, seq, pats, offs, k, g, rows, tot);
+        if (rc) return rc;
+        form = FZ_FORM_KERNEL;
+    }
+    uint64_t total = 0;
+    if (consolidated) {
+        for (uint32_t i = 0; i < n_pats; ++i) {
+            fz_match *c = nullptr;
+            uint64_t nc = 0;
+            rc = fz_consolidate(rows[i].data(), rows[i].size(), &c, &nc);
+            if (rc) return rc;
+            rows[i].assign(c, c + nc);
+            release_out(c);
+        }
+    }
+    for (uint32_t i = 0; i < n_pats; ++i) total += rows[i].size();
+    void *mem = nullptr, *omem = nullptr;
+    rc = alloc_out(total, sizeof(fz_match), &mem);
+    if (rc) return rc;
+    rc = alloc_out((uint64_t)n_pats + 1, sizeof(uint64_t), &omem);
+    if (rc) { release_out(mem); return rc; }
+    fz_match *mo = static_cast<fz_match *>(mem);
+    uint64_t *oo = static_cast<uint64_t *>(omem);
+    uint64_t at = 0;
+    for (uint32_t i = 0; i < n_pats; ++i) {
+        oo[i] = at;
+        if (!rows[i].empty()) memcpy(mo + at, rows[i].data(), rows[i].size() * sizeof(fz_match));
+        at += rows[i].size();
+    }
+    oo[n_pats] = at;
+    *out = mo; *out_offs = oo;
+    memset(&ctx->stats, 0, sizeof ctx->stats);
+    ctx->tref.clear();
+    ctx->stats.n_devices = (uint32_t)ctx->devs.size();
+    ctx->stats.filter_launches = tot.launches;
+    ctx->stats.bytes_scanned = tot.bytes;
+    ctx->stats.ngram_hits = tot.hits;
+    ctx->stats.raw_matches = tot.rows;
+    ctx->stats.filter_ms = tot.filter_ms;
+    ctx->stats.verify_ms = tot.verify_ms;
+    ctx->stats.device_ms = tot.filter_ms + tot.verify_ms;
+    ctx->stats.verify_form = form;
+    return FZ_OK;
+}
+
+int fz_lev_ngrams_multi(fz_ctx *ctx, fz_seq *seq, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k,
+                        fz_match **out, uint64_t **out_offs) {
+    return lev_multi_impl(ctx, seq, pats, offs, n_pats, k, false, out, out_offs);
+}
+
+int fz_lev_ngrams_multi_consolidated(fz_ctx *ctx, fz_seq *seq, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k,
+                                     fz_match **out, uint64_t **out_offs) {
+    return lev_multi_impl(ctx, seq, pats, offs, n_pats, k, true, out, out_offs);
+}
+
+int fz_debug_multi_plan(const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k, uint32_t *group_of, uint32_t *n_groups) {
+    if (!group_of || !n_groups) return fail(FZ_EINVAL, "null argument");
+    int rc = mp_check_lists(pats, offs, n_pats);
+    if (rc) return rc;
+    for (uint32_t i = 0; i < n_pats; ++i) {
+        const uint64_t m = offs[i + 1] - offs[i];
+        if (m == 0) return fail(FZ_EINVAL, "subsequence must not be empty");
+        if (m > FZ_MAX_M_ANY) return fail(FZ_EUNSUPPORTED, "subsequence longer than %u bytes", FZ_MAX_M_ANY);
+        if (m / ((uint64_t)k + 1) == 0) return fail(FZ_EINVAL, "the subsequence length must be greater than max_l_dist");
+    }
+    std::vector<MpGroup> groups;
+    std::vector<uint32_t> of;
+    mp_plan(pats, offs, n_pats, k, groups, of);
+    for (uint32_t i = 0; i < n_pats; ++i) group_of[i] = of[i];
+    *n_groups = (uint32_t)groups.size();
+    return FZ_OK;
 }
 
 // Argument checks and the block plan of the substitutions-only n-gram search (template :92-101).

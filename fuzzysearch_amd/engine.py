@@ -20,7 +20,7 @@ import numpy as np
 from . import _native
 from ._native import UnsupportedSearch
 
-__all__ = ['DeviceSequence', 'resident', 'encode_pair', 'is_byteslike', 'ResidencyCache', 'residency_cache']
+__all__ = ['DeviceSequence', 'resident', 'encode_pair', 'is_byteslike', 'ResidencyCache', 'residency_cache', 'prepare_shared']
 
 
 _BIO_SEQ = []                                    # [Seq class or None] once looked up
@@ -406,6 +406,42 @@ class _Prepared(object):
             self.entry = None
         elif self.owned:
             self.handle.release()
+
+
+def prepare_shared(sequence):
+    """One preparation of `sequence` for MANY subsequences (find_near_matches_multi): -> (_Prepared without a pattern, a
+    DeviceSequence over the same handle that stands for the sequence in per-pattern calls), or None when the device form
+    of the sequence depends on the subsequence (symbol-remapped lists and wide text) or is not this function's business
+    (Biopython sequences).  One residency-cache acquire or one upload, exactly as prepare() would do for one query."""
+    pr = _Prepared()
+    pr.entry = None
+    pr.pattern = None
+    if isinstance(sequence, DeviceSequence):
+        pr.engine, pr.handle, pr.original = sequence.engine, sequence.handle, sequence.original
+        pr.byteslike, pr.owned = sequence.byteslike, False
+        return pr, sequence
+    if _unwrap_bio(sequence)[1]:
+        return None
+    if is_byteslike(sequence):
+        pr.byteslike, make_data = True, (lambda: sequence)
+    elif isinstance(sequence, str):
+        pr.byteslike, make_data = False, (lambda: sequence.encode('latin-1'))
+    else:
+        return None
+    pr.engine = _native.default_engine()
+    pr.original = sequence
+    pr.owned = True
+    _cache.sweep()
+    try:
+        if len(sequence) >= ResidencyCache.MIN_BYTES and not _cache.bypassed() and _cache.budget > 0 and ResidencyCache.cacheable(sequence):
+            pr.handle, pr.entry = _cache.acquire(pr.engine, sequence, make_data)
+        else:
+            pr.handle = pr.engine.upload(make_data())
+    except UnicodeEncodeError:
+        return None                                      # wide code points: the coding depends on the subsequence
+    view = DeviceSequence.__new__(DeviceSequence)
+    view.original, view.engine, view.byteslike, view.handle = sequence, pr.engine, pr.byteslike, pr.handle
+    return pr, view
 
 
 def prepare(subsequence, sequence):

@@ -1,0 +1,70 @@
+"""find_near_matches_multi: many subsequences, one sequence, one call.
+
+The value (and any exception) is that of ``[find_near_matches(p, sequence, ...) for p in subsequences]``.  What is new
+is the cost: the sequence is prepared once (one residency-cache acquire, or one upload), and the patterns on the
+Levenshtein n-gram route go through ONE C-ABI call (fz_lev_ngrams_multi_consolidated) that tests every byte offset of the
+sequence against the n-gram blocks of up to 64 patterns per pass.  Everything else — other strategy classes, the exact and
+linear-programming routes, sequences whose coding depends on the subsequence — takes the per-pattern code inside the same
+call, with the results in input order.
+"""
+from .common import LevenshteinSearchParams, matches_from_rows_multi
+from .engine import is_byteslike, prepare_shared
+
+__all__ = ['find_near_matches_multi']
+
+
+def _batch_pattern(p, byteslike):
+    """The bytes of subsequence `p` as the resident sequence is coded, or None when it cannot ride the batched call."""
+    if byteslike:
+        return bytes(memoryview(p)) if is_byteslike(p) else None
+    if isinstance(p, str):
+        try:
+            return p.encode('latin-1')
+        except UnicodeEncodeError:
+            return None
+    return None
+
+
+def find_near_matches_multi(subsequences, sequence,
+                            max_substitutions=None,
+                            max_insertions=None,
+                            max_deletions=None,
+                            max_l_dist=None):
+    """search for near-matches of every subsequence in sequence -> a list with one list of Match per subsequence,
+    equal to ``[find_near_matches(p, sequence, ...) for p in subsequences]`` (same limits for all of them).
+
+    ``sequence`` may be a ``resident()`` handle.  The first subsequence that ``find_near_matches`` would refuse raises
+    its exception before anything is searched."""
+    from . import find_near_matches, choose_search_class, LevenshteinSearch
+    subsequences = list(subsequences)
+    if not subsequences:
+        return []
+    limits = (max_substitutions, max_insertions, max_deletions, max_l_dist)
+    search_params = LevenshteinSearchParams(*limits)
+    k = search_params.max_l_dist
+    batched_class = choose_search_class(search_params) is LevenshteinSearch and k > 0
+    shared = prepare_shared(sequence) if all(len(p) for p in subsequences) else None
+    if shared is None:
+        # nothing to share (or an empty subsequence, which raises at its turn): today's code, pattern by pattern
+        return [find_near_matches(p, sequence, *limits) for p in subsequences]
+    pr, view = shared
+    try:
+        results = [None] * len(subsequences)
+        batch = []
+        for i, p in enumerate(subsequences):
+            pb = _batch_pattern(p, pr.byteslike) if batched_class and len(p) // (k + 1) >= 3 else None
+            if pb is not None:
+                batch.append((i, pb))
+        riding = set(i for i, _ in batch)
+        for i, p in enumerate(subsequences):             # the per-pattern routes first: what they refuse raises before the batch runs
+            if i not in riding:
+                # (a subsequence of the wrong kind for the sequence meets the sequence itself: find_near_matches' own error)
+                fits = is_byteslike(p) if pr.byteslike else isinstance(p, str)
+                results[i] = find_near_matches(p, view if fits else sequence, *limits)
+        if batch:
+            rows, bounds = pr.engine.multi_rows_call(pr.handle, [pb for _, pb in batch], k)
+            for (i, _), matches in zip(batch, matches_from_rows_multi(rows, bounds, pr.original)):
+                results[i] = matches
+        return results
+    finally:
+        pr.release()

@@ -184,6 +184,37 @@ int fz_generic_ngrams_consolidated(fz_ctx *ctx, fz_seq *seq, const uint8_t *p, u
 int fz_lev_ngrams_consolidated(fz_ctx *ctx, fz_seq *seq, const uint8_t *p, uint32_t m, uint32_t k, fz_match **out, uint64_t *n);
 int fz_subs_ngrams_best(fz_ctx *ctx, fz_seq *seq, const uint8_t *p, uint32_t m, uint32_t k, fz_match **out, uint64_t *n);
 
+/* n_pats Levenshtein n-gram searches with one budget k over one resident sequence, in as few passes over it as the
+ * patterns allow.  pats = the patterns back to back, offs[i] .. offs[i+1] the bytes of pattern i (offs has n_pats + 1
+ * entries).  *out = the raw streams of all patterns one after the other, (*out_offs)[i] .. (*out_offs)[i+1] the rows of
+ * pattern i: byte for byte what fz_lev_ngrams(ctx, seq, pats + offs[i], offs[i+1] - offs[i], k, ...) returns, `block`
+ * included.  Both outputs are released with fz_free.  Any pattern the single call refuses (empty, length <= k, beyond
+ * the limits, halo too small) fails the whole call with that call's code and message before anything is searched.
+ *
+ * Planning is a function of the arguments alone.  The batched route takes the patterns with
+ *     1 <= k <= 8,   m <= 128,   L = m / (k + 1) >= 4:
+ * they are grouped by L in input order, a group holding at most 64 patterns with together at most 256 n-gram blocks
+ * (the next pattern of that L that would exceed either starts a new group).  A group is ONE pass over the sequence: one
+ * filter launch that tests every byte offset against all blocks of the group and appends the survivors to hit lists, and
+ * one verification launch over those lists, per shard and whatever the number of patterns.  A group of one pattern and
+ * every pattern outside the domain run through fz_lev_ngrams inside the same call.
+ * Sequences of several shards: the group kernels run on every shard (global coordinates, ownership and halo as in the
+ * single search) and the host orders every pattern's records of all shards together.  A context in a communicator
+ * searches collectively: there the call is a loop over the collective fz_lev_ngrams, pattern by pattern, on every rank.
+ * The call is synchronous; with a _begin outstanding it answers FZ_EINVAL.
+ * fz_stats afterwards: filter_launches / bytes_scanned = filter launches of the whole call and the bytes they streamed,
+ * ngram_hits = exactly confirmed hits, raw_matches = rows, all summed over the patterns; verify_form = FZ_FORM_KERNEL
+ * when at least one group ran batched. */
+int fz_lev_ngrams_multi(fz_ctx *ctx, fz_seq *seq, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats,
+                        uint32_t k, fz_match **out, uint64_t **out_offs);
+/* The same with every pattern's slice consolidated: slice i = what fz_lev_ngrams_consolidated returns for pattern i. */
+int fz_lev_ngrams_multi_consolidated(fz_ctx *ctx, fz_seq *seq, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats,
+                                     uint32_t k, fz_match **out, uint64_t **out_offs);
+/* Test hook, no device needed: group_of[i] = the pass pattern i rides in (0 .. *n_groups - 1), or 0xffffffff when it
+ * takes the single-pattern route. */
+int fz_debug_multi_plan(const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k,
+                        uint32_t *group_of, uint32_t *n_groups);
+
 /* has_near_match_* (substitutions_only.py:139-145, :218-233; generic_search.py:240-253): *found = 1 iff the
  * corresponding search would return at least one record.  Nothing is ordered or copied, and device work that starts
  * after the first record has been counted is skipped (workgroups of the scan, hits of the automaton kernel). */
