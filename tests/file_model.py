@@ -73,8 +73,24 @@ def route(kwargs):
     return "generic", ml, (ms, mi, md, ml), max(x for x in (ml, mi) if x is not None)
 
 
-def search_chunk(kind, k, limits, p, t, text):
-    """Raw (start, end, dist, block) stream of one chunk, as search_class.search(subsequence, chunk) yields it."""
+def reduce_subs(raw, text):
+    """What SubstitutionsOnlySearch.search makes of a chunk's n-gram stream: str - every window once, sorted by start;
+    bytes - the best of every overlap group."""
+    if text:                             # pure-Python path: every window once, sorted by start
+        seen, out = set(), []
+        for r in raw:
+            if r[0] not in seen:
+                seen.add(r[0])
+                out.append(r)
+        return sorted(out)
+    best, _hull = oracle.group_best(raw)
+    return best
+
+
+def search_chunk(kind, k, limits, p, t, text, raw=False):
+    """Raw (start, end, dist, block) stream of one chunk, as search_class.search(subsequence, chunk) yields it.
+    `raw`: substitutions-only n-gram searches keep the unreduced stream of the chunk in its in-memory order - what
+    fz_stream_finish returns, before fuzzysearch_amd._file_stream._post_process reduces it chunk by chunk."""
     m = len(p)
     exact = lambda: [(i, i + m, 0, 0) for i in oracle.search_exact(p, t)]       # noqa: E731
     if kind == "exact" or k == 0:
@@ -83,28 +99,21 @@ def search_chunk(kind, k, limits, p, t, text):
     if kind == "subs":
         if not ngram:
             return oracle.subs_lp_raw(p, t, k)
-        raw = oracle.subs_ngrams_raw(p, t, k)
-        if text:                         # pure-Python path: every window once, sorted by start
-            seen, out = set(), []
-            for r in raw:
-                if r[0] not in seen:
-                    seen.add(r[0])
-                    out.append(r)
-            return sorted(out)
-        best, _hull = oracle.group_best(raw)
-        return best
+        rows = oracle.subs_ngrams_raw(p, t, k)
+        return rows if raw else reduce_subs(rows, text)
     if kind == "lev":
         return oracle.lev_ngrams_raw(p, t, k) if ngram else oracle.lev_lp_raw(p, t, k)
     return oracle.generic_ngrams_raw(p, t, *limits) if ngram else oracle.generic_lp_raw(p, t, *limits)
 
 
-def file_raw(p, data, kwargs, chunk_size, text):
-    """-> (kind, rows): the concatenated per-chunk streams in file coordinates, rows = (start, end, dist, block, chunk)."""
+def file_raw(p, data, kwargs, chunk_size, text, raw=False):
+    """-> (kind, rows): the concatenated per-chunk streams in file coordinates, rows = (start, end, dist, block, chunk).
+    `raw`: see search_chunk."""
     kind, k, limits, extra = route(kwargs)
     keep = len(p) - 1 + extra
     rows = []
     for j, (a, e) in enumerate(chunk_bounds(len(data), chunk_size, keep, text)):
-        for (s, en, d, g) in search_chunk(kind, k, limits, p, data[a:e], text):
+        for (s, en, d, g) in search_chunk(kind, k, limits, p, data[a:e], text, raw):
             rows.append((s + a, en + a, d, g, j))
     return kind, rows
 

@@ -3,6 +3,7 @@ of the library are process-wide statics read from the environment (FZ_FORCE_BIG_
 FZ_MAX_BLOCKS, FZ_NO_DIRECT), so a test that wants them set starts a fresh interpreter.  Prints "OK <n cases> <n records>".
 The seam sweeps of tests/seam_case.py run through here as well (`seams <route> <CUs>`: the route's small texts, then the
 text with several tiles per workgroup; in-process from tests/test_gpu_scan_seams.py for the routes that need no switch)."""
+import io
 import os
 import random
 import sys
@@ -245,9 +246,279 @@ def run_seam_route_iterations(engine, route, n_cus, text=None, bg=None):
     return "%s | grid %d, %d MiB" % (sc.coverage_line(route.name, case.coverage, route.form), case.plan[0], n >> 20), rows, case.text, case.bg
 
 
+# -- the file stream (tests/file_seam_case.py) -------------------------------------------------------------------------------
+DEFAULT_BATCH = 64 << 20
+
+
+def file_stream(engine, route, p, S, pre, post, batch_bytes):
+    from fuzzysearch_amd import _native
+    from tests import file_seam_case as fc
+    return _native.FileStream(engine, fc.MODE[route.kind], p, route.limits or (0, 0, 0), route.k, S, pre, post, batch_bytes)
+
+
+def feed_full(st, data):
+    """Every staging buffer filled to its end; a short fill is the last one (fuzzysearch_amd._file_stream._feed_readinto)."""
+    pos = 0
+    while True:
+        view = st.buffer()
+        room = len(view)
+        if room == 0:
+            break
+        piece = data[pos:pos + room]
+        view[:len(piece)] = piece
+        del view
+        st.submit(len(piece), len(piece) < room)
+        pos += len(piece)
+        if len(piece) < room:
+            break
+
+
+def feed_random(st, data, rnd):
+    """Submits of 0, 1 .. 64 KiB bytes, then submit(0, last)."""
+    pos = 0
+    while pos < len(data):
+        view = st.buffer()
+        take = min(len(view), len(data) - pos, rnd.choice([0, 1, 2, rnd.randint(1, 4096), rnd.randint(1, 65536)]))
+        view[:take] = data[pos:pos + take]
+        del view
+        st.submit(take, False)
+        pos += take
+    st.submit(0, True)
+
+
+def stream_rows(engine, case, batch_bytes, feed="full", seed=0, fd=None, threads=1, as_arrays=False):
+    """One file stream over the case's file -> (rows (start, end, dist, block) as a list, chunk numbers as a list, form);
+    `as_arrays`: as finish() returns them."""
+    st = file_stream(engine, case.route, case.pattern, case.S, case.pre, case.post, batch_bytes)
+    try:
+        if feed == "full":
+            feed_full(st, case.data)
+        elif feed == "random":
+            feed_random(st, case.data, random.Random(seed))
+        else:
+            assert st.read_fd(fd, 0, threads) == len(case.data)
+        raw, seg = st.finish()
+        form = engine.stats()["verify_form"]
+    finally:
+        st.close()
+    if as_arrays:
+        return raw, seg, form
+    return raw.tolist(), seg.tolist(), form
+
+
+def check_file_stream(engine, case, want, batch_bytes, what, **feed):
+    """The stream's rows and chunk numbers against the model's, exactly and in order; the form the route is there for
+    (files with at least one whole chunk: the last batch ran a search).  `want`: the model's rows, or (millions of them) an
+    int64 array of shape (rows, 5), compared column by column; the rows are listed only when a column differs."""
+    import numpy as np
+    got, seg, form = stream_rows(engine, case, batch_bytes, as_arrays=isinstance(want, np.ndarray), **feed)
+    if isinstance(want, np.ndarray):
+        if len(got) == len(want) and all(np.array_equal(got[f], want[:, i]) for i, f in enumerate(("start", "end", "dist", "block"))) \
+                and np.array_equal(seg, want[:, 4]):
+            assert form == case.route.form, (case.route.name, what, "verify_form", form)
+            return len(got)
+        got, seg, want = got.tolist(), seg.tolist(), [tuple(r) for r in want.tolist()]
+    exp = [r[:4] for r in want]
+    exp_seg = [r[4] for r in want]
+    if got != exp or seg != exp_seg:
+        both = list(zip(zip(got, seg), zip(exp, exp_seg)))
+        bad = next((i for i, (a, b) in enumerate(both) if a != b), min(len(got), len(exp)))
+        raise AssertionError("%s %s S %d %s batch %d, %d bytes: %d rows against %d expected, first difference at row %d: got %r / %r, "
+                             "expected %r / %r" % (case.route.name, what, case.S, "text" if case.text else "binary", batch_bytes,
+                                                    len(case.data), len(got), len(exp), bad, got[bad:bad + 3], seg[bad:bad + 3],
+                                                    exp[bad:bad + 3], exp_seg[bad:bad + 3]))
+    if len(case.data) > case.S + case.pre + case.post:
+        assert form == case.route.form, (case.route.name, what, "verify_form", form)
+    return len(got)
+
+
+def eight_chunk_batch(S):
+    """A batch size of about eight chunks of stride S whose batch buffers start off the 16 KiB tile grid."""
+    return 8 * S + S // 3 + 5
+
+
+def run_file_route(engine, route, ends=True, public=False):
+    """One route of tests/file_seam_case.py: every sweep of fc.sweeps(route) and the file ends, each at the default batch (one
+    batch), a batch of about eight chunks, the three-chunk batch the sweep is planted on and the smallest batch; `public`: every
+    third sweep through find_near_matches_in_file as well.  -> (coverage lines, streams run, rows compared)."""
+    from tests import file_seam_case as fc
+    lines, n_streams, n_rows, n_cases, n_public = [], 0, 0, 0, 0
+    for (g, text, background) in fc.sweeps(route):
+        case = fc.build(route, fc.stride(route, g), text, background)
+        want = fc.expected(case)
+        fc.check_expectation(case, want, count=False)          # (the counts: tests/test_file_seam_case.py)
+        small = set(fc.batch_seams(len(case.data), case.S, case.pre, case.post, fc.small_batch(case.S)))
+        assert all(pl.seam in small for pl in case.plants)
+        for batch in (DEFAULT_BATCH, eight_chunk_batch(case.S), fc.small_batch(case.S), 1):
+            n_rows += check_file_stream(engine, case, want, batch, "%s %s" % (g, background))
+            n_streams += 1
+        if public and n_cases % 3 == 0:
+            n_public += check_public(case)
+        n_cases += 1
+        if background == "quiet":
+            lines.append(fc.coverage_line(route.name, case, route.form) + ", %d rows" % len(want))
+    if ends:
+        for text in (False, True):
+            S = fc.odd_stride(route)
+            _S, pre, post, _c = fc.geometry(route, S, text)
+            j_end = fc.batches(12 * S, S, pre, post, eight_chunk_batch(S))[0].j1
+            covers = {"start": set(), "end": set()}
+            for case in fc.end_cases(route, S, text, (3, j_end)):
+                want = fc.expected(case)
+                for batch in (DEFAULT_BATCH, eight_chunk_batch(case.S), fc.small_batch(case.S), 1):
+                    n_rows += check_file_stream(engine, case, want, batch, "file end n = %d" % len(case.data))
+                    n_streams += 1
+                for side in covers:
+                    covers[side] |= case.coverage[side]["exact"] | case.coverage[side]["edited"]
+            lines.append("file ends  %-22s %-6s S %5d | chunk %d ends a batch; start items %d, end items %d" % (
+                route.name, "text" if text else "binary", S, j_end, len(covers["start"]), len(covers["end"])))
+    if public:
+        lines.append("%s: %d matches through find_near_matches_in_file (every third sweep)" % (route.name, n_public))
+    return lines, n_streams, n_rows
+
+
+class NamedBytesIO(io.BytesIO):
+    mode = 'rb'
+
+
+def file_route(name):
+    from tests import file_seam_case as fc
+    return next(r for r in fc.ROUTES if r.name == name)
+
+
+def plain_case(r, p, data, S, text):
+    from tests import file_seam_case as fc
+    S, pre, post, chunk_size = fc.geometry(r, S, text)
+    return fc.Case(r, p, data, S, pre, post, chunk_size, text, [], {})
+
+
+def check_public(case):
+    """find_near_matches_in_file on the case's file against file_model.file_result: Levenshtein and generic equal or equal
+    modulo ties inside an overlap group, substitutions equal modulo ties of equal distance and length, exact equal."""
+    import fuzzysearch_amd as fa
+    from tests import file_model, golden_io
+    from tests import file_seam_case as fc
+    r = case.route
+    kw = fc.kwargs(r)
+    exp, rows = file_model.file_result(case.pattern, case.data, kw, case.chunk_size, case.text)
+    if case.text:
+        text = case.data.decode('latin-1')
+        got = fa.find_near_matches_in_file(case.pattern.decode('latin-1'), io.StringIO(text), _chunk_size=case.chunk_size, **kw)
+        assert all(m.matched == text[m.start:m.end] for m in got)
+    else:
+        got = fa.find_near_matches_in_file(case.pattern, NamedBytesIO(case.data), _chunk_size=case.chunk_size, **kw)
+        assert all(bytes(m.matched) == case.data[m.start:m.end] for m in got)
+    got = [(m.start, m.end, m.dist) for m in got]
+    what = (r.name, case.S, case.text, len(case.data))
+    if r.kind in ("lev", "generic"):
+        assert got == exp or golden_io.equal_modulo_ties(got, exp, [x[:3] for x in rows]), what
+    elif r.kind == "subs":
+        assert len(got) == len(exp) and all(g == e or (g[2] == e[2] and g[1] - g[0] == e[1] - e[0]) for g, e in zip(got, exp)), what
+    else:
+        assert got == exp, what
+    return len(got)
+
+
+# -- re-runs inside a stream -----------------------------------------------------------------------------------------------------
+def rerun_many_rows(engine):
+    """More than 16 384 records in ONE batch (the search leaves direct mode): files of back-to-back copies, every fifth one
+    edited, through the stream (one batch, and batches of about eight chunks) and through the API."""
+    from tests import file_seam_case as fc
+    n_rows = 0
+    # (KiB of file: as small as gives the route its 16 384 rows with a margin - the generic search reports 570 rows per KiB)
+    for name, kib in (("seg-band-20-2", 168), ("seg-wf-24-5", 104), ("file-subs-24-3", 152), ("file-generic-20", 40), ("file-exact-8", 216)):
+        r = file_route(name)
+        p = fc.route_pattern(r)
+        rnd = random.Random(9)
+        parts = []
+        while sum(len(x) for x in parts) < (kib << 10):
+            v = p if len(parts) % 5 else fc.edited_copy(rnd, p, r.k, bytes(r.alpha), r.kind == "subs", r.limits)
+            parts.append(v + b"0123456"[:len(parts) % 7 + 1])
+        for text in (False, True):
+            case = plain_case(r, p, b"".join(parts), 7001, text)
+            want = fc.expected(case)
+            assert len(fc.batches(len(case.data), case.S, case.pre, case.post, DEFAULT_BATCH)) == 1 and len(want) > 16384, len(want)
+            for batch in (DEFAULT_BATCH, eight_chunk_batch(case.S)):
+                n_rows += check_file_stream(engine, case, want, batch, "many rows")
+            if not text:
+                check_public(case)
+    return n_rows
+
+
+HIT_LIST_BYTES = (80 << 20) + 4099
+
+
+def rerun_hit_list(cache):
+    """DNA, 80 MiB, m = 20, k = 5 (L = 3, six blocks: about len * 6 / 64 hits) at the default batch: stream_launch sizes the hit
+    list max(2^20, len / 64), so the first batch overflows it and runs again.  On an engine of its own: the list only ever
+    grows, so on a used engine an earlier search may have left one that is large enough.  `cache`: where the model's rows (and
+    the matches expected of the API) are kept between the run in this process and the one under FZ_NO_DIRECT=1."""
+    import time
+    import numpy as np
+    import fuzzysearch_amd as fa
+    from fuzzysearch_amd import _native
+    from tests import golden_io, workloads
+    from tests import file_seam_case as fc
+    r = fc.Route("rerun-20-5", "lev", 20, 5, None, fc.DNA, fc.FORM_KERNEL, {}, True, 2)
+    t0 = time.time()
+    seq = workloads.dna(HIT_LIST_BYTES, 777)
+    pattern = workloads.dna(20, 1)
+    workloads.plant_variants(seq, pattern, 400, 6)
+    keep = fc.keep_of(r)
+    case = plain_case(r, pattern.tobytes(), seq.tobytes(), (1 << 20) - keep, False)
+    if os.path.exists(cache):
+        with np.load(cache) as f:
+            want, exp = f["rows"], f["matches"]
+    else:
+        import oracle
+        rows = fc.expected(case)
+        want = np.array(rows, dtype=np.int64).reshape(-1, 5)
+        exp = np.array(oracle.consolidate([x[:4] for x in rows]), dtype=np.int64).reshape(-1, 3)
+        with open(cache, "wb") as f:
+            np.savez(f, rows=want, matches=exp)
+    bs = fc.batches(len(case.data), case.S, case.pre, case.post, DEFAULT_BATCH)
+    first, last = bs[0], bs[-1]
+    t1 = time.time()
+    eng = _native.Engine([0])
+    try:
+        n_rows = check_file_stream(eng, case, want, DEFAULT_BATCH, "hit list")
+        hits = eng.stats()["ngram_hits"]                      # (of the last batch: every launch starts the counters again)
+    finally:
+        eng.close()
+    # the first batch of this engine met a list of max(2^20, len / 64) entries; the last batch gives the hits per byte
+    last_len, first_len = last.data_hi - last.stage_off, first.data_hi - first.stage_off
+    room = max(1 << 20, first_len // 64)
+    print("hit list: %d rows; last batch %d bytes, %d hits; first batch %d bytes for a list of %d" % (n_rows, last_len, hits, first_len, room))
+    assert hits > max(1 << 20, last_len // 64) and first_len > last_len and hits / last_len * first_len > 2 * room, (hits, room)
+    t2 = time.time()
+    got = fa.find_near_matches_in_file(case.pattern, NamedBytesIO(case.data), max_l_dist=5)
+    got = [(m.start, m.end, m.dist) for m in got]
+    print("hit list: file and model %.1f s, stream %.1f s, API %.1f s" % (t1 - t0, t2 - t1, time.time() - t2))
+    exp = [tuple(x) for x in exp.tolist()]
+    assert got == exp or golden_io.equal_modulo_ties(got, exp, [tuple(x) for x in want[:, :3].tolist()])
+    assert len(exp) > 300
+    return n_rows
+
+
 def main(argv):
     from fuzzysearch_amd import _native
     what = argv[0]
+    if what == "file":
+        # one route of tests/file_seam_case.py under the process-wide switch it needs (FZ_FORCE_BIG_VERIFY): argv = route name
+        from tests import file_seam_case as fc
+        route = next(r for r in fc.ROUTES if r.name == argv[1])
+        eng = _native.Engine([0])
+        lines, n_streams, n_rows = run_file_route(eng, route)
+        eng.close()
+        print("\n".join(lines))
+        print("OK %d %d" % (n_streams, n_rows))
+        return
+    if what == "file-reruns":
+        # FZ_NO_DIRECT=1: the re-runs inside a stream with records and counters through D2H copies
+        eng = _native.default_engine()
+        n_rows = rerun_many_rows(eng) + rerun_hit_list(argv[1])
+        print("OK 2 %d" % n_rows)
+        return
     if what == "seams":
         # one route of tests/seam_case.py under the process-wide switch it needs (FZ_NO_BITS, FZ_WF32, FZ_FORCE_BIG_VERIFY,
         # FZ_NO_SLOT_AND): argv = route name, CU count of the device
