@@ -9,7 +9,9 @@ include/fzhip.h; this package is plain Python + ctypes (no PyTorch) and has NO C
 [Match(start=3, end=9, dist=1, matched=b'PATERN')]
 
 Extra, MI355X-specific surface: ``resident(sequence)`` uploads a long sequence to HBM once so that
-many patterns can be searched without re-crossing PCIe.
+many patterns can be searched without re-crossing PCIe; ``find_near_matches_multi`` searches many subsequences in one
+sequence and ``find_near_matches_batch`` one subsequence in many sequences (``resident_batch`` keeps them in HBM), each
+in one pass.
 """
 import io
 
@@ -22,6 +24,7 @@ from .search_exact import ExactSearch
 from .substitutions_only import SubstitutionsOnlySearch
 from . import _file_stream
 from .multi import find_near_matches_multi
+from .batch import find_near_matches_batch, resident_batch
 
 __version__ = '0.1.0'
 
@@ -29,8 +32,10 @@ __all__ = [
     'find_near_matches',
     'find_near_matches_in_file',
     'find_near_matches_multi',
+    'find_near_matches_batch',
     'Match',
     'resident',
+    'resident_batch',
     'cache_info',
     'cache_clear',
     'UnsupportedSearch',

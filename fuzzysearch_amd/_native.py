@@ -28,6 +28,7 @@ EXPORTED_SYMBOLS = (
     "fz_comm_allgather", "fz_comm_max_f64", "fz_comm_barrier", "fz_comm_destroy", "fz_comm_gather_ms", "fz_comm_backend", "fz_debug_reload_switches", "fz_debug_gather_merge", "fz_debug_scan_regions",
     "fz_debug_scan_plan",
     "fz_lev_ngrams_multi", "fz_lev_ngrams_multi_consolidated", "fz_debug_multi_plan",
+    "fz_batch_upload", "fz_batch_search", "fz_debug_batch_segment",
 )
 
 
@@ -162,6 +163,12 @@ def load_library():
             fn.argtypes = [vp, vp, u8p, u64p, u32, u32, mpp, ctypes.POINTER(u64p)]
         L.fz_debug_multi_plan.restype = ci
         L.fz_debug_multi_plan.argtypes = [u8p, u64p, u32, u32, ctypes.POINTER(u32), ctypes.POINTER(u32)]
+        L.fz_batch_upload.restype = ci
+        L.fz_batch_upload.argtypes = [vp, u8p, u64p, u64, ctypes.POINTER(vp)]
+        L.fz_batch_search.restype = ci
+        L.fz_batch_search.argtypes = [vp, vp, u32, u8p, u32, u32, ci, mpp, ctypes.POINTER(ctypes.POINTER(u32)), u64p]
+        L.fz_debug_batch_segment.restype = ci
+        L.fz_debug_batch_segment.argtypes = [u64p, u64, u64, u64p, u64p, u64p]
         L.fz_subs_ngrams_best.restype = ci
         L.fz_subs_ngrams_best.argtypes = [vp, vp, u8p, u32, u32, mpp, u64p]
         L.fz_generic_ngrams_consolidated.restype = ci
@@ -395,6 +402,19 @@ def multi_plan(patterns, k):
     return [None if group_of[i] == 0xffffffff else group_of[i] for i in range(n)], ng.value
 
 
+MODE_EXACT, MODE_LEV, MODE_SUBS = 0, 1, 2          # fz_batch_search's mode (FzMode of csrc/fz_device.h)
+
+
+def batch_segment(offs, idx):
+    """fz_debug_batch_segment (no device): -> (sequence number, start, end) of position idx of a batch whose sequences
+    lie at offs[j] .. offs[j + 1].  `offs`: a C-contiguous numpy uint64 array (kept by the caller across calls)."""
+    L = load_library()
+    j, sa, se = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+    _check(L.fz_debug_batch_segment(offs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), len(offs) - 1, idx,
+                                    ctypes.byref(j), ctypes.byref(sa), ctypes.byref(se)))
+    return j.value, sa.value, se.value
+
+
 class OwnedRows(object):
     """A C-ABI result buffer (fz_match rows) that has not been copied anywhere: address, n, and fz_free on release."""
     __slots__ = ('_lib', '_ptr', 'n')
@@ -552,6 +572,53 @@ class Engine(object):
             _check(self._lib.fz_seq_upload(self._h, addr, n, ctypes.byref(h)))
         del keep
         return ResidentSequence(self, h, n)
+
+    def upload_batch(self, data, offs):
+        """fz_batch_upload: `data` = the sequences back to back (bytes-like), `offs` = numpy uint64 array of their
+        len + 1 offsets.  -> a ResidentSequence that only batch_search accepts."""
+        import numpy as np
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        addr, n, keep = _buffer_address(data)
+        h = ctypes.c_void_p()
+        with self._lock:
+            _check(self._lib.fz_batch_upload(self._h, addr, offs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                                             len(offs) - 1, ctypes.byref(h)))
+        del keep
+        return ResidentSequence(self, h, n)
+
+    def _batch_call(self, batch, mode, pattern, k, reduced):
+        if type(pattern) is bytes:
+            paddr, m, keep = pattern, len(pattern), None
+        else:
+            paddr, m, keep = _buffer_address(pattern)
+        ptr = ctypes.POINTER(FzMatch)()
+        sptr = ctypes.POINTER(ctypes.c_uint32)()
+        cnt = ctypes.c_uint64(0)
+        with self._lock:
+            _check(self._lib.fz_batch_search(self._h, batch._h, mode, paddr, m, k, 1 if reduced else 0,
+                                             ctypes.byref(ptr), ctypes.byref(sptr), ctypes.byref(cnt)))
+        return ptr, sptr, cnt.value
+
+    def batch_search(self, batch, mode, pattern, k, reduced=False):
+        """fz_batch_search -> (rows, seq_of): an fz_match structured array in the local coordinates of the rows' sequences,
+        ordered by sequence, and the uint32 array of their sequence numbers."""
+        import numpy as np
+        ptr, sptr, n = self._batch_call(batch, mode, pattern, k, reduced)
+        seq_of = np.empty(n, dtype=np.uint32)
+        if n:
+            ctypes.memmove(seq_of.ctypes.data, sptr, 4 * n)
+        self._lib.fz_free(sptr)
+        return _take_matches_array(self._lib, ptr, n), seq_of
+
+    def batch_rows_call(self, batch, mode, pattern, k, reduced=True):
+        """The same as (OwnedRows, seq_of array), for callers that build Match objects in C straight from the result buffer."""
+        import numpy as np
+        ptr, sptr, n = self._batch_call(batch, mode, pattern, k, reduced)
+        seq_of = np.empty(n, dtype=np.uint32)
+        if n:
+            ctypes.memmove(seq_of.ctypes.data, sptr, 4 * n)
+        self._lib.fz_free(sptr)
+        return OwnedRows(self._lib, ptr, n), seq_of
 
     def upload_shard(self, data, buf_global_off, own_lo, own_hi, global_n):
         addr, n, keep = _buffer_address(data)

@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libfzhip.so")
 RESOURCES = os.path.join(HERE, "libfzhip.resources.txt")
 SOURCES = ["fzhip.hip"]
-DEPS = ["fzhip.hip", "fz_kernels.h", "fz_device.h", os.path.join("..", "..", "include", "fzhip.h")]
+DEPS = ["fzhip.hip", "fz_kernels.h", "fz_kernel_bodies.inc", "fz_device.h", os.path.join("..", "..", "include", "fzhip.h")]
 
 
 def hipcc():

@@ -97,6 +97,81 @@ FZ_HD FzSeg fz_segment(const FzGeom &g, uint64_t idx, uint32_t c) {
 }
 FZ_HD uint32_t fz_segment_candidates(const FzGeom &g) { return (g.seg_stride && (g.seg_pre || g.seg_post)) ? 2u : 1u; }
 
+// Ragged segments (fz_batch_upload: one pattern, many sequences): the buffer holds n_seqs sequences packed back to back,
+// no separators, no padding; sequence j = [j ? ends[j-1] : 0, ends[j]) with ends[] the cumulative end offsets (u64,
+// non-decreasing; equal neighbours = an empty sequence).  A position lies in exactly ONE sequence:
+//     j = the first j with ends[j] > idx.
+// The binary search is bounded by a second table built at upload, first[t] = the first j with ends[j] > t * 16 KiB (the
+// sequence that holds the first byte of tile t; n_seqs past the end), ntiles + 1 entries: the sequence of a position in
+// tile t is one of first[t] .. first[t+1] — one step where sequences are longer than a tile, ~7 for 150-byte reads.
+// To the host's planning and to every clamp that is not per sequence a batch is ONE in-memory sequence (seg_stride = 0,
+// n = total bytes); the segment fields of FzGeom, unused in that form, carry the tables, and only the ragged kernel
+// instances (fz_kernels.h: RAG) read them:
+//     seg_org = device address of ends[],  seg_j0 = device address of first[],  seg_j1 = n_seqs.
+#define FZ_RAG_TILE_BITS 14            // = FZ_TILE_BITS (fz_kernels.h): the granule of first[]
+struct FzRagged { const uint64_t *ends; const uint32_t *first; uint64_t n_seqs; };
+
+FZ_HD FzRagged fz_ragged(const FzGeom &g) {
+    FzRagged r;
+    r.ends = reinterpret_cast<const uint64_t *>(g.seg_org);
+    r.first = reinterpret_cast<const uint32_t *>(g.seg_j0);
+    r.n_seqs = g.seg_j1;
+    return r;
+}
+
+// first[] of an offset table: `ntiles` + 1 entries.
+FZ_HD void fz_ragged_first(const uint64_t *ends, uint64_t n_seqs, uint64_t ntiles, uint32_t *first) {
+    uint64_t j = 0;
+    for (uint64_t t = 0; t <= ntiles; ++t) {
+        while (j < n_seqs && ends[j] <= (t << FZ_RAG_TILE_BITS)) ++j;
+        first[t] = (uint32_t)j;
+    }
+}
+
+// The sequence of position idx (idx < n = ends[n_seqs - 1], else ok = 0).
+FZ_HD FzSeg fz_segment_ragged(const FzRagged &t, uint64_t n, uint64_t idx) {
+    FzSeg r;
+    r.sa = r.se = 0; r.j = 0; r.ok = 0;
+    if (idx >= n || t.n_seqs == 0) return r;
+    const uint64_t tile = idx >> FZ_RAG_TILE_BITS;
+    uint32_t lo = t.first[tile], hi = t.first[tile + 1];   // (n_seqs < 2^32)
+    if (hi >= t.n_seqs) hi = (uint32_t)t.n_seqs - 1u;
+    while (lo < hi) {                                      // first j in [lo, hi] with ends[j] > idx
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (t.ends[mid] > idx) hi = mid; else lo = mid + 1u;
+    }
+    r.sa = lo ? t.ends[lo - 1] : 0;
+    r.se = t.ends[lo];
+    r.j = lo;
+    r.ok = 1;
+    return r;
+}
+
+// fz_segment / fz_segment_candidates of a kernel instance: strided (or unsegmented) by the geometry, or (RAG) ragged.
+template <bool RAG>
+FZ_HD uint32_t fz_segment_candidates_of(const FzGeom &g) { return RAG ? 1u : fz_segment_candidates(g); }
+template <bool RAG>
+FZ_HD FzSeg fz_segment_of(const FzGeom &g, uint64_t idx, uint32_t c) {
+    if constexpr (RAG) {
+        return fz_segment_ragged(fz_ragged(g), g.n, idx);
+    } else {
+        return fz_segment(g, idx, c);
+    }
+}
+
+// The segment a kernel instance verifies a position in when it does not go through fz_segment's strided candidates:
+// the whole sequence, or (RAG) the position's own sequence of a batch.
+template <bool RAG>
+FZ_HD FzSeg fz_segment_one(const FzGeom &g, uint64_t idx) {
+    if constexpr (RAG) {
+        return fz_segment_ragged(fz_ragged(g), g.n, idx);
+    } else {
+        FzSeg r;
+        r.sa = 0; r.se = g.n; r.j = 0; r.ok = 1;
+        return r;
+    }
+}
+
 // One scan launch: up to FZ_MAX_BLOCKS_PER_LAUNCH n-gram blocks of length L.  A hit of block b at global index idx is
 // accepted for the segment [sa, se) iff
 //     sa + lo_rel[b] <= idx  &&  idx + L <= se - hi_sub[b]  &&  abs_lo <= idx  &&  idx + L <= abs_hi

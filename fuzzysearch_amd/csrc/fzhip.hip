@@ -253,6 +253,9 @@ struct DevState {
     }
 };
 
+// A batch of sequences (fz_batch_upload): unsegmented to the planner, the tables in the segment fields (fz_device.h).
+inline bool geom_is_ragged(const FzGeom &g) { return g.seg_stride == 0 && g.seg_j1 != 0; }
+
 struct Shard {
     int dev = 0;                                 // index into ctx->devs
     uint8_t *d_alloc = nullptr;                  // allocation base
@@ -411,6 +414,7 @@ struct fz_ctx {
     // RCCL: number of ranks of the communicator this context joined (0: none) and whether its Levenshtein n-gram
     // searches are collective (every rank gets the merged global stream)
     bool any_found = false;                      // result of the last has_near_match_* (fz_*_any) search
+    bool batch_call = false;                     // inside fz_batch_search: the one caller a batch handle is valid for (validate)
     // sharded searches: where every shard's (rank's) records end in the collected vector, and the shards in ascending
     // order of the index range they own (emit_matches orders shard by shard)
     std::vector<size_t> seg_ends;
@@ -446,6 +450,13 @@ struct fz_seq {
     // collective searches: the first index every rank of the communicator owns of THIS sequence (~0: nothing), exchanged
     // on the sequence's first collective search; the ranks' segments are merged in that order
     std::vector<uint64_t> rank_lo;
+    // fz_batch_upload: n_seqs sequences packed back to back (fz_device.h: ragged segments).  ends = the host copy of the
+    // cumulative end offsets (rows -> sequences), d_ends / d_first the device tables (null for an empty batch).
+    bool is_batch = false;
+    uint64_t n_seqs = 0;
+    std::vector<uint64_t> ends;
+    uint64_t *d_ends = nullptr;
+    uint32_t *d_first = nullptr;
 };
 
 namespace {
@@ -634,6 +645,34 @@ ScanKernel scan_kernel(int nwin, int dh, bool fused, bool seg, bool sa, int wf_g
     if (seg) return fused ? scan_kernel_s<true, true>(nwin, dh, sa) : scan_kernel_s<false, true>(nwin, dh, sa);
     return fused ? scan_kernel_s<true, false>(nwin, dh, sa) : scan_kernel_s<false, false>(nwin, dh, sa);
 #endif
+}
+
+// The ragged instances (fz_batch_search: a batch of sequences packed back to back): every form of the in-memory search.
+// The register-band / Hamming-count / hit-emitting forms come with and without the one-v_and slot address (sa); the
+// bit-vector and lane-per-cell forms only in the general form, which serves every slot shift.
+template <bool FUSED, bool SA, int WFG>
+ScanKernel batch_scan_kernel_f(int nwin, int dh) {
+    if (nwin == 1) return fz_batch_scan_kernel<1, 0, FUSED, SA, WFG>;
+    switch (dh) {
+        case 2: return fz_batch_scan_kernel<2, 2, FUSED, SA, WFG>;
+        case 3: return fz_batch_scan_kernel<2, 3, FUSED, SA, WFG>;
+        case 4: return fz_batch_scan_kernel<2, 4, FUSED, SA, WFG>;
+        default: return fz_batch_scan_kernel<2, 5, FUSED, SA, WFG>;
+    }
+}
+
+ScanKernel batch_scan_kernel(int nwin, int dh, bool fused, bool sa, int wf_gw) {
+    switch (wf_gw) {
+        case 1: return batch_scan_kernel_f<true, false, 1>(nwin, dh);
+        case 2: return batch_scan_kernel_f<true, false, 2>(nwin, dh);
+        case 3: return batch_scan_kernel_f<true, false, 3>(nwin, dh);
+        case 4: return batch_scan_kernel_f<true, false, 4>(nwin, dh);
+        case 16: return batch_scan_kernel_f<true, false, 16>(nwin, dh);
+        case 32: return batch_scan_kernel_f<true, false, 32>(nwin, dh);
+        default: break;
+    }
+    if (fused) return sa ? batch_scan_kernel_f<true, true, 0>(nwin, dh) : batch_scan_kernel_f<true, false, 0>(nwin, dh);
+    return sa ? batch_scan_kernel_f<false, true, 0>(nwin, dh) : batch_scan_kernel_f<false, false, 0>(nwin, dh);
 }
 
 // Odd multipliers tried for the window hash (24-bit ones serve v_mad_u32_u24).  One search needs a
@@ -1138,7 +1177,9 @@ int enqueue_shard(fz_ctx *ctx, const Shard &sh, const Search &q, bool with_verif
         for (uint32_t b = 1; b < nblk; ++b)
             for (uint32_t c = 0; c < b; ++c)
                 if (fa.H[b] == fa.H[c]) fa.flags |= FZ_FLAG_DUP_HASHES;
-        ScanKernel kern = scan_kernel(nwin, dh, fa.fused != 0, sh.geom.seg_stride != 0, fa.lut_shift == 2, sp.wfg);
+        const bool ragged = geom_is_ragged(sh.geom);
+        ScanKernel kern = ragged ? batch_scan_kernel(nwin, dh, fa.fused != 0, fa.lut_shift == 2, sp.wfg)
+                                 : scan_kernel(nwin, dh, fa.fused != 0, sh.geom.seg_stride != 0, fa.lut_shift == 2, sp.wfg);
         if (!kern) return fail(FZ_EUNSUPPORTED, "this (lab) build carries no scan kernel for nwin=%d dh=%d", nwin, dh);
         hipEvent_t ev_start = (attach && ctx->timing && g0 == 0) ? d.ev[0] : nullptr;
         hipEvent_t ev_stop = g0 + nblk >= G ? (ext_events ? d.ev[3] : (attach && ctx->timing) ? d.ev[1] : nullptr) : nullptr;
@@ -1169,25 +1210,30 @@ int enqueue_shard(fz_ctx *ctx, const Shard &sh, const Search &q, bool with_verif
         if (vp.big) {
             if (!fa.pat_g) return fail(FZ_EDEVICE, "internal: the pattern was not staged for the big verification");
             const uint32_t cells = q.mode == FZ_MODE_LEV ? 2 * q.k + 1 : 1;
-            if (cells <= 64) vk = fz_verify_big_kernel<1>;
-            else if (cells <= 128) vk = fz_verify_big_kernel<2>;
-            else if (cells <= 256) vk = fz_verify_big_kernel<4>;
-            else if (cells <= 512) vk = fz_verify_big_kernel<8>;
-            else if (cells <= 1024) vk = fz_verify_big_kernel<16>;
-            else vk = fz_verify_big_kernel<32>;
+            const bool rag = geom_is_ragged(sh.geom);
+            if (cells <= 64) vk = rag ? fz_batch_verify_big_kernel<1> : fz_verify_big_kernel<1>;
+            else if (cells <= 128) vk = rag ? fz_batch_verify_big_kernel<2> : fz_verify_big_kernel<2>;
+            else if (cells <= 256) vk = rag ? fz_batch_verify_big_kernel<4> : fz_verify_big_kernel<4>;
+            // (a batch takes the 16-cells-per-lane instance here as well — a wider band is as exact: the ragged instance
+            //  with 8 cells per lane is the one kernel hipcc gives a 36-byte private segment, and no kernel of this library
+            //  uses scratch memory)
+            else if (cells <= 512) vk = rag ? fz_batch_verify_big_kernel<16> : fz_verify_big_kernel<8>;
+            else if (cells <= 1024) vk = rag ? fz_batch_verify_big_kernel<16> : fz_verify_big_kernel<16>;
+            else vk = rag ? fz_batch_verify_big_kernel<32> : fz_verify_big_kernel<32>;
             vgrid = dim3(d.n_cus * 32); vblock = dim3(64); vlds = 0;
         } else if (vp.want_wf) {
             // lane-per-cell: 64 / gw candidates per wave, one contiguous byte window per candidate
             fa.gw = (uint32_t)vp.gw;
-            if (vp.gw == 16) vk = fz_verify_wf_kernel<16>;
-            else if (vp.gw == 32) vk = fz_verify_wf_kernel<32>;
-            else vk = fz_verify_wf_kernel<64>;
+            const bool rag = geom_is_ragged(sh.geom);
+            if (vp.gw == 16) vk = rag ? fz_batch_verify_wf_kernel<16> : fz_verify_wf_kernel<16>;
+            else if (vp.gw == 32) vk = rag ? fz_batch_verify_wf_kernel<32> : fz_verify_wf_kernel<32>;
+            else vk = rag ? fz_batch_verify_wf_kernel<64> : fz_verify_wf_kernel<64>;
             // 16 waves per workgroup: few workgroups = few finish tickets (every ticket is an atomic on one word)
             vgrid = dim3(d.n_cus * 2); vblock = dim3(1024); vlds = vp.wf_lds;
         } else {
             // LDS: pattern + per-wave window and score ring; the block was shrunk until it fits.
             fa.vlanes = 64;
-            vk = fz_verify_kernel;
+            vk = geom_is_ragged(sh.geom) ? fz_batch_verify_kernel : fz_verify_kernel;
             if (vp.ring_lds > 64 * 1024)
                 HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(vk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)vp.ring_lds));
             vgrid = dim3(d.n_cus * 4); vblock = dim3(64 * vp.waves); vlds = vp.ring_lds;
@@ -1938,6 +1984,9 @@ void release_out(void *p) {
 
 int validate(fz_ctx *ctx, fz_seq *seq, const uint8_t *p, uint32_t m, bool in_pipeline = false) {
     if (!ctx || !seq || seq->ctx != ctx) return fail(FZ_EINVAL, "bad ctx/seq handle");
+    if (seq->is_batch != ctx->batch_call)
+        return fail(FZ_EINVAL, seq->is_batch ? "a batch handle (fz_batch_upload) is searched with fz_batch_search only"
+                                             : "fz_batch_search takes a batch handle (fz_batch_upload)");
     if (ctx->npend && !in_pipeline) return fail(FZ_EINVAL, "a search started with fz_lev_ngrams_begin is still in flight");
     if (ctx->stream_inflight) return fail(FZ_EINVAL, "a file stream of this context has a batch in flight (finish or close it first)");
     if (!p || m == 0) return fail(FZ_EINVAL, "subsequence must not be empty");
@@ -2471,6 +2520,7 @@ int fz_seq_add_shard(fz_seq *seq, int dev_index, const uint8_t *host_buf, uint64
                      uint64_t own_lo, uint64_t own_hi) {
     if (!seq || !seq->ctx || (!host_buf && buf_len)) return fail(FZ_EINVAL, "null argument");
     fz_ctx *ctx = seq->ctx;
+    if (seq->is_batch) return fail(FZ_EINVAL, "a batch handle takes no shards");
     if (ctx->npend || ctx->stream_inflight) return fail(FZ_EINVAL, "a search of this context is in flight");
     if (dev_index < 0 || dev_index >= (int)ctx->devs.size()) return fail(FZ_EINVAL, "device index %d outside the context (%zu devices)", dev_index, ctx->devs.size());
     if (buf_global_off + buf_len > seq->n || own_lo > own_hi || own_hi > seq->n)
@@ -2529,7 +2579,91 @@ void fz_seq_release(fz_seq *seq) {
             }
         }
     }
+    if (seq->ctx && (seq->d_ends || seq->d_first)) {
+        (void)hipSetDevice(seq->ctx->devs[0].device);
+        if (seq->d_ends) (void)hipFree(seq->d_ends);
+        if (seq->d_first) (void)hipFree(seq->d_first);
+    }
     delete seq;
+}
+
+int fz_batch_upload(fz_ctx *ctx, const uint8_t *bytes, const uint64_t *offs, uint64_t n_seqs, fz_seq **out) {
+    if (!ctx || !out || !offs) return fail(FZ_EINVAL, "null argument");
+    *out = nullptr;
+    if (n_seqs >= (1ull << 32)) return fail(FZ_EUNSUPPORTED, "more than 2^32 - 1 sequences in a batch");
+    if (offs[0] != 0) return fail(FZ_EINVAL, "offs[0] must be 0");
+    for (uint64_t j = 0; j < n_seqs; ++j)
+        if (offs[j + 1] < offs[j]) return fail(FZ_EINVAL, "sequence offsets must not decrease");
+    const uint64_t n = offs[n_seqs];
+    if (!bytes && n) return fail(FZ_EINVAL, "null argument");
+    if (n >= (1ull << FZ_IDX_BITS)) return fail(FZ_EUNSUPPORTED, "sequence too long");
+    if (ctx->devs.size() != 1 || ctx->snapshot || comm_multi_process(ctx))
+        return fail(FZ_EUNSUPPORTED, "batches are searched by single-device, non-collective contexts");
+    if (ctx->npend || ctx->stream_inflight) return fail(FZ_EINVAL, "a search of this context is in flight");
+    fz_seq *seq = new (std::nothrow) fz_seq();
+    if (!seq) return fail(FZ_ENOMEM, "out of memory");
+    seq->ctx = ctx;
+    seq->n = n;
+    seq->is_batch = true;
+    seq->n_seqs = n_seqs;
+    FzGeom g{};
+    g.n = n;
+    g.buf_off = 0;
+    g.buf_len = n;
+    g.own_lo = 0;
+    g.own_hi = n;
+    seq->shards.emplace_back();
+    int rc = upload_one(ctx, 0, bytes, g, seq->shards.back());
+    std::vector<uint32_t> first;
+    if (rc == FZ_OK && n_seqs) {
+        // the tables: cumulative end offsets, and per tile the first sequence that touches it (fz_device.h)
+        static_assert(FZ_RAG_TILE_BITS == FZ_TILE_BITS, "first[] is indexed by the scan's tiles");
+        DevState &d = ctx->devs[0];
+        seq->ends.assign(offs + 1, offs + 1 + n_seqs);
+        const uint64_t ntiles = (n + FZ_TILE_BYTES - 1) / FZ_TILE_BYTES;
+        first.resize(ntiles + 1);
+        fz_ragged_first(seq->ends.data(), n_seqs, ntiles, first.data());
+        hipError_t e = hipMalloc(reinterpret_cast<void **>(&seq->d_ends), n_seqs * sizeof(uint64_t));
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&seq->d_first), first.size() * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMemcpyAsync(seq->d_ends, seq->ends.data(), n_seqs * sizeof(uint64_t), hipMemcpyHostToDevice, d.stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(seq->d_first, first.data(), first.size() * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream);
+        if (e != hipSuccess) rc = fail(e == hipErrorOutOfMemory ? FZ_ENOMEM : FZ_EDEVICE, "batch tables: %s", hipGetErrorString(e));
+        FzGeom &sg = seq->shards.back().geom;
+        sg.seg_org = reinterpret_cast<uint64_t>(seq->d_ends);
+        sg.seg_j0 = reinterpret_cast<uint64_t>(seq->d_first);
+        sg.seg_j1 = n_seqs;
+    }
+    if (rc == FZ_OK) {
+        hipError_t e = hipStreamSynchronize(ctx->devs[0].stream);      // bytes, offs and the tables' host copies are only borrowed
+        if (e != hipSuccess) rc = fail(FZ_EDEVICE, "upload failed: %s", hipGetErrorString(e));
+    }
+    if (rc) { fz_seq_release(seq); return rc; }
+    ctx->live.push_back(seq);
+    *out = seq;
+    return FZ_OK;
+}
+
+int fz_debug_batch_segment(const uint64_t *offs, uint64_t n_seqs, uint64_t idx, uint64_t *j, uint64_t *sa, uint64_t *se) {
+    if (!offs || !j || !sa || !se) return fail(FZ_EINVAL, "null argument");
+    if (n_seqs >= (1ull << 32)) return fail(FZ_EUNSUPPORTED, "more than 2^32 - 1 sequences in a batch");
+    const uint64_t n = offs[n_seqs];
+    if (idx >= n) return fail(FZ_EINVAL, "position outside the batch");
+    // the per-tile table of the offset array the last call named, kept while the caller keeps asking about that array
+    static thread_local const uint64_t *c_offs = nullptr;
+    static thread_local uint64_t c_nseqs = 0, c_n = 0;
+    static thread_local std::vector<uint32_t> c_first;
+    if (c_offs != offs || c_nseqs != n_seqs || c_n != n || c_first.empty()) {
+        const uint64_t ntiles = (n + FZ_TILE_BYTES - 1) / FZ_TILE_BYTES;
+        c_first.resize(ntiles + 1);
+        fz_ragged_first(offs + 1, n_seqs, ntiles, c_first.data());
+        c_offs = offs; c_nseqs = n_seqs; c_n = n;
+    }
+    FzRagged t;
+    t.ends = offs + 1; t.first = c_first.data(); t.n_seqs = n_seqs;
+    const FzSeg sg = fz_segment_ragged(t, n, idx);
+    if (!sg.ok) return fail(FZ_EINVAL, "position outside the batch");
+    *j = sg.j; *sa = sg.sa; *se = sg.se;
+    return FZ_OK;
 }
 
 int fz_search_exact(fz_ctx *ctx, fz_seq *seq, const uint8_t *p, uint32_t m, uint64_t lo, uint64_t hi,
@@ -2835,6 +2969,7 @@ static int lev_multi_impl(fz_ctx *ctx, fz_seq *seq, const uint8_t *pats, const u
     if (!out || !out_offs) return fail(FZ_EINVAL, "null argument");
     *out = nullptr; *out_offs = nullptr;
     if (!ctx || !seq || seq->ctx != ctx) return fail(FZ_EINVAL, "bad ctx/seq handle");
+    if (seq->is_batch) return fail(FZ_EINVAL, "a batch handle (fz_batch_upload) is searched with fz_batch_search only");
     if (ctx->npend) return fail(FZ_EINVAL, "a search started with fz_lev_ngrams_begin is still in flight");
     if (ctx->stream_inflight) return fail(FZ_EINVAL, "a file stream of this context has a batch in flight (finish or close it first)");
     int rc = mp_check_lists(pats, offs, n_pats);
@@ -3191,6 +3326,117 @@ int fz_subs_ngrams_any(fz_ctx *ctx, fz_seq *seq, const uint8_t *p, uint32_t m, u
     if (!found) return fail(FZ_EINVAL, "null argument");
     *found = 0;
     return subs_ngrams_impl(ctx, seq, p, m, k, nullptr, nullptr, found);
+}
+
+int fz_batch_search(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8_t *p, uint32_t m, uint32_t k,
+                    int reduced, fz_match **out, uint32_t **seq_of, uint64_t *n) {
+    if (!out || !seq_of || !n) return fail(FZ_EINVAL, "null argument");
+    *out = nullptr; *seq_of = nullptr; *n = 0;
+    if (!ctx || !batch || batch->ctx != ctx) return fail(FZ_EINVAL, "bad ctx/seq handle");
+    if (mode != FZ_MODE_EXACT && mode != FZ_MODE_LEV && mode != FZ_MODE_SUBS) return fail(FZ_EINVAL, "mode must be exact, Levenshtein or substitutions-only");
+    if (mode == FZ_MODE_EXACT && k != 0) return fail(FZ_EINVAL, "an exact search has no budget");
+    struct Scope {                                         // validate() accepts a batch handle inside this call only
+        fz_ctx *c;
+        explicit Scope(fz_ctx *c_) : c(c_) { c->batch_call = true; }
+        ~Scope() { c->batch_call = false; }
+    } scope(ctx);
+    Search q;
+    int rc;
+    if (mode == FZ_MODE_LEV) rc = lev_plan(ctx, batch, p, m, k, q);
+    else if (mode == FZ_MODE_SUBS) rc = subs_plan(ctx, batch, p, m, k, q);
+    else {
+        rc = validate(ctx, batch, p, m);
+        if (rc == FZ_OK) rc = check_halo(batch, m);
+        q.mode = FZ_MODE_EXACT; q.m = m; q.k = 0; q.p = p;
+        q.plan.L = m;
+        q.plan.s = {0};
+        q.plan.abs_lo = 0;
+        q.plan.abs_hi = batch->n;
+    }
+    if (rc) return rc;
+    if (ctx->devs.size() != 1 || ctx->snapshot || comm_multi_process(ctx) || batch->shards.size() != 1)
+        return fail(FZ_EUNSUPPORTED, "batches are searched by single-device, non-collective contexts");
+    q.collective = false;
+    // the rows of the packed bytes in the in-memory order (block, index), global coordinates
+    std::vector<fz_match> rows;
+    memset(&ctx->stats, 0, sizeof ctx->stats);
+    ctx->stats.n_devices = 1;
+    if (batch->n_seqs && batch->n) {
+        std::vector<FzRec> recs;
+        std::vector<uint64_t> hits;
+        rc = run_search(ctx, batch, q, mode != FZ_MODE_EXACT, recs, hits);
+        if (rc) return rc;
+        if (mode == FZ_MODE_EXACT) {
+            std::sort(hits.begin(), hits.end());
+            rows.resize(hits.size());
+            for (size_t i = 0; i < hits.size(); ++i) {
+                const int64_t at = (int64_t)fz_hit_index(hits[i]);
+                rows[i].start = at; rows[i].end = at + m; rows[i].dist = 0; rows[i].block = -1;
+            }
+        } else {
+            fz_match *mo = nullptr;
+            uint64_t cnt = 0;
+            rc = emit_matches(ctx, recs, q.plan.L, &mo, &cnt, batch->n, (uint32_t)q.plan.s.size());
+            if (rc) return rc;
+            rows.assign(mo, mo + cnt);
+            release_out(mo);
+        }
+    }
+    ctx->stats.raw_matches = rows.size();
+    // a row's sequence = the sequence of its first byte (a match lies inside the sequence of its n-gram hit); rows are
+    // ordered the way fz_stream_finish orders chunks: a stable sort by sequence of the in-memory order
+    const std::vector<uint64_t> &ends = batch->ends;
+    std::vector<std::pair<uint32_t, uint32_t>> order(rows.size());       // (sequence, row)
+    for (size_t i = 0; i < rows.size(); ++i) {
+        const size_t j = (size_t)(std::upper_bound(ends.begin(), ends.end(), (uint64_t)rows[i].start) - ends.begin());
+        if (j >= ends.size()) return fail(FZ_EDEVICE, "internal: a batch row outside every sequence");
+        order[i] = {(uint32_t)j, (uint32_t)i};
+    }
+    if (rows.size() >= (1ull << 32)) return fail(FZ_EUNSUPPORTED, "more than 2^32 - 1 rows in a batch search");
+    std::stable_sort(order.begin(), order.end(), [](const std::pair<uint32_t, uint32_t> &x, const std::pair<uint32_t, uint32_t> &y) { return x.first < y.first; });
+    std::vector<fz_match> fin;
+    std::vector<uint32_t> fin_seq;
+    fin.reserve(rows.size());
+    fin_seq.reserve(rows.size());
+    std::vector<fz_match> slice;
+    const bool reduce = reduced != 0 && mode != FZ_MODE_EXACT;
+    for (size_t a = 0; a < order.size();) {
+        size_t b = a;
+        const uint32_t j = order[a].first;
+        const int64_t base = (int64_t)(j ? ends[j - 1] : 0);
+        slice.clear();
+        for (; b < order.size() && order[b].first == j; ++b) {
+            fz_match r = rows[order[b].second];
+            r.start -= base; r.end -= base;
+            slice.push_back(r);
+        }
+        if (reduce) {
+            fz_match *ro = nullptr;
+            uint64_t rn = 0;
+            rc = mode == FZ_MODE_LEV ? fz_consolidate(slice.data(), slice.size(), &ro, &rn) : fz_group_best(slice.data(), slice.size(), &ro, &rn);
+            if (rc) return rc;
+            fin.insert(fin.end(), ro, ro + rn);
+            fin_seq.insert(fin_seq.end(), rn, j);
+            release_out(ro);
+        } else {
+            fin.insert(fin.end(), slice.begin(), slice.end());
+            fin_seq.insert(fin_seq.end(), slice.size(), j);
+        }
+        a = b;
+    }
+    void *mem = nullptr, *smem_ = nullptr;
+    rc = alloc_out(fin.size(), sizeof(fz_match), &mem);
+    if (rc) return rc;
+    rc = alloc_out(fin_seq.size(), sizeof(uint32_t), &smem_);
+    if (rc) { release_out(mem); return rc; }
+    if (!fin.empty()) {
+        memcpy(mem, fin.data(), fin.size() * sizeof(fz_match));
+        memcpy(smem_, fin_seq.data(), fin_seq.size() * sizeof(uint32_t));
+    }
+    *out = static_cast<fz_match *>(mem);
+    *seq_of = static_cast<uint32_t *>(smem_);
+    *n = fin.size();
+    return FZ_OK;
 }
 
 static int generic_ngrams_impl(fz_ctx *ctx, fz_seq *seq, const uint8_t *p, uint32_t m, uint32_t max_subs, uint32_t max_ins,

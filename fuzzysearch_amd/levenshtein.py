@@ -49,6 +49,15 @@ class LevenshteinSearch(FuzzySearchBase):
         return raw_levenshtein(subsequence, sequence, search_params.max_l_dist)
 
     @classmethod
+    def one_call_route(cls, m, search_params, byteslike):
+        """Which route a subsequence of m items takes, as raw_levenshtein decides it: ('exact', 0), ('lev', k) for the
+        n-gram route — whose consolidated rows one C-ABI call delivers — or None (linear programming)."""
+        k = search_params.max_l_dist
+        if k == 0:
+            return ('exact', 0)
+        return ('lev', k) if m // (k + 1) >= 3 else None
+
+    @classmethod
     def search_consolidated(cls, subsequence, sequence, search_params):
         """search() + consolidate_matches() in ONE C-ABI call for the n-gram route (fz_lev_ngrams_consolidated: the
         consolidation runs on the rows where they are) and Match objects built in C straight from the result buffer.
@@ -56,7 +65,7 @@ class LevenshteinSearch(FuzzySearchBase):
         if not len(subsequence):
             raise ValueError('Given subsequence is empty!')
         k = search_params.max_l_dist
-        if k == 0 or len(subsequence) // (k + 1) < 3:
+        if cls.one_call_route(len(subsequence), search_params, True) != ('lev', k):
             return None
         pr = prepare(subsequence, sequence)
         try:

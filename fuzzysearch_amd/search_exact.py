@@ -51,5 +51,9 @@ class ExactSearch(FuzzySearchBase):
         return exact_raw(subsequence, sequence)
 
     @classmethod
+    def one_call_route(cls, m, search_params, byteslike):
+        return ('exact', 0)
+
+    @classmethod
     def extra_items_for_chunked_search(cls, subsequence, search_params):
         return 0

@@ -118,6 +118,16 @@ class SubstitutionsOnlySearch(FuzzySearchBase):
         return find_near_matches_substitutions(subsequence, sequence, k)
 
     @classmethod
+    def one_call_route(cls, m, search_params, byteslike):
+        """Which route a subsequence of m items takes, as find_near_matches_substitutions decides it: ('exact', 0),
+        ('subs', k) for the n-gram route on bytes-like input — whose result (the best of every overlap group) one C-ABI
+        call delivers — or None (linear programming; str input, whose result is every window sorted by start)."""
+        k = min(x for x in (search_params.max_l_dist, search_params.max_substitutions) if x is not None)
+        if k == 0:
+            return ('exact', 0)
+        return ('subs', k) if m // (k + 1) >= 3 and byteslike else None
+
+    @classmethod
     def search_consolidated(cls, subsequence, sequence, search_params):
         """The n-gram route on bytes-like input in ONE C-ABI call (fz_subs_ngrams_best: search + best of every overlap
         group in group-list order, substitutions_only.py:258-282), Match objects built in C straight from the result
@@ -125,7 +135,7 @@ class SubstitutionsOnlySearch(FuzzySearchBase):
         linear programming; n-gram length 0)."""
         k = min(x for x in (search_params.max_l_dist, search_params.max_substitutions) if x is not None)
         _check_arguments(subsequence, sequence, k)
-        if k == 0 or len(subsequence) // (k + 1) < 3:
+        if cls.one_call_route(len(subsequence), search_params, True) != ('subs', k):
             return None
         if isinstance(sequence, DeviceSequence):
             if not sequence.byteslike:

@@ -215,6 +215,35 @@ int fz_lev_ngrams_multi_consolidated(fz_ctx *ctx, fz_seq *seq, const uint8_t *pa
 int fz_debug_multi_plan(const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k,
                         uint32_t *group_of, uint32_t *n_groups);
 
+/* One pattern, many sequences, one pass.  fz_batch_upload makes n_seqs sequences resident, packed back to back without
+ * separators: sequence j = bytes[offs[j] .. offs[j+1]) (offs has n_seqs + 1 entries, offs[0] == 0, non-decreasing; equal
+ * neighbours = an empty sequence).  n_seqs < 2^32.  Next to the bytes two tables go to the device: the cumulative end
+ * offsets (u64 per sequence) and, per 16 KiB tile, the first sequence that touches it (u32), which bounds the search for
+ * a position's sequence.  Single-device, non-collective contexts (else FZ_EUNSUPPORTED).  The handle is a batch handle:
+ * fz_batch_search takes it, every other search function answers FZ_EINVAL for it (and fz_batch_search answers FZ_EINVAL
+ * for a plain sequence); fz_seq_len = the packed length; fz_seq_release / fz_destroy free bytes and tables. */
+int fz_batch_upload(fz_ctx *ctx, const uint8_t *bytes, const uint64_t *offs, uint64_t n_seqs, fz_seq **out);
+
+/* mode: FZ_MODE_EXACT / _LEV / _SUBS = 0 / 1 / 2 (k = 0 / max_l_dist / max_substitutions).
+ * Every sequence is searched as a sequence of its own — window clamps and accepted n-gram ranges use its own ends, and
+ * nothing that needs bytes of two sequences is found — in ONE pass over the packed bytes: the same filter launches as the
+ * unsegmented search of the pattern over those bytes, whatever n_seqs is, and the same verification form (a function of
+ * the arguments alone); a candidate additionally pays the lookup of its sequence.
+ * Rows are in the LOCAL coordinates of their sequence, ordered by sequence; within one sequence they are byte for byte
+ * what the single call returns for that sequence alone: fz_search_exact as (i, i + m, 0, -1), fz_lev_ngrams,
+ * fz_subs_ngrams; with reduced != 0 what fz_lev_ngrams_consolidated / fz_subs_ngrams_best return for it (exact rows are
+ * not reduced).  (*seq_of)[r] = sequence of row r.  Both outputs are released with fz_free.
+ * The pattern is refused as the single calls refuse it, with their codes, before anything is searched.
+ * fz_stats afterwards as for any search (raw_matches = rows before the reduction). */
+int fz_batch_search(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8_t *p, uint32_t m, uint32_t k,
+                    int reduced, fz_match **out, uint32_t **seq_of, uint64_t *n);
+
+/* Test hook, no device needed: the sequence of position idx of a batch with the offsets `offs` — the lookup the kernels
+ * run (fz_device.h: fz_segment_ragged, the per-tile bound included), on the host.  *j = its number, [*sa, *se) its bytes.
+ * FZ_EINVAL for idx >= offs[n_seqs].  The tables are built on the first call for an offset array and kept for the next
+ * calls with the same array (same address, length and total). */
+int fz_debug_batch_segment(const uint64_t *offs, uint64_t n_seqs, uint64_t idx, uint64_t *j, uint64_t *sa, uint64_t *se);
+
 /* has_near_match_* (substitutions_only.py:139-145, :218-233; generic_search.py:240-253): *found = 1 iff the
  * corresponding search would return at least one record.  Nothing is ordered or copied, and device work that starts
  * after the first record has been counted is skipped (workgroups of the scan, hits of the automaton kernel). */
