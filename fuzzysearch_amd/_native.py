@@ -28,6 +28,7 @@ EXPORTED_SYMBOLS = (
     "fz_comm_allgather", "fz_comm_max_f64", "fz_comm_barrier", "fz_comm_destroy", "fz_comm_gather_ms", "fz_comm_backend", "fz_debug_reload_switches", "fz_debug_gather_merge", "fz_debug_scan_regions",
     "fz_debug_scan_plan",
     "fz_lev_ngrams_multi", "fz_lev_ngrams_multi_consolidated", "fz_debug_multi_plan",
+    "fz_subs_ngrams_multi", "fz_subs_ngrams_multi_best", "fz_debug_multi_plan_mode",
     "fz_batch_upload", "fz_batch_search", "fz_debug_batch_segment",
 )
 
@@ -158,11 +159,13 @@ def load_library():
         L.fz_generic_lp.argtypes = [vp, vp, u8p, u32, u32, u32, u32, u32, mpp, u64p]
         L.fz_lev_ngrams_consolidated.restype = ci
         L.fz_lev_ngrams_consolidated.argtypes = [vp, vp, u8p, u32, u32, mpp, u64p]
-        for fn in (L.fz_lev_ngrams_multi, L.fz_lev_ngrams_multi_consolidated):
+        for fn in (L.fz_lev_ngrams_multi, L.fz_lev_ngrams_multi_consolidated, L.fz_subs_ngrams_multi, L.fz_subs_ngrams_multi_best):
             fn.restype = ci
             fn.argtypes = [vp, vp, u8p, u64p, u32, u32, mpp, ctypes.POINTER(u64p)]
         L.fz_debug_multi_plan.restype = ci
         L.fz_debug_multi_plan.argtypes = [u8p, u64p, u32, u32, ctypes.POINTER(u32), ctypes.POINTER(u32)]
+        L.fz_debug_multi_plan_mode.restype = ci
+        L.fz_debug_multi_plan_mode.argtypes = [u32, u8p, u64p, u32, u32, ctypes.POINTER(u32), ctypes.POINTER(u32)]
         L.fz_batch_upload.restype = ci
         L.fz_batch_upload.argtypes = [vp, u8p, u64p, u64, ctypes.POINTER(vp)]
         L.fz_batch_search.restype = ci
@@ -391,18 +394,19 @@ def pack_patterns(patterns):
     return b"".join(parts) or b"\0", offs
 
 
-def multi_plan(patterns, k):
-    """fz_debug_multi_plan (no device): -> (group of every pattern, None = the single-pattern route; number of groups)."""
+MODE_EXACT, MODE_LEV, MODE_SUBS = 0, 1, 2          # fz_batch_search's mode (FzMode of csrc/fz_device.h)
+
+
+def multi_plan(patterns, k, mode=MODE_LEV):
+    """fz_debug_multi_plan_mode (no device): -> (group of every pattern, None = the single-pattern route; number of groups)
+    for the Levenshtein (MODE_LEV) or the substitutions-only (MODE_SUBS) multi-pattern search."""
     L = load_library()
     blob, offs = pack_patterns(patterns)
     n = len(patterns)
     group_of = (ctypes.c_uint32 * max(1, n))()
     ng = ctypes.c_uint32(0)
-    _check(L.fz_debug_multi_plan(blob, offs, n, k, group_of, ctypes.byref(ng)))
+    _check(L.fz_debug_multi_plan_mode(mode, blob, offs, n, k, group_of, ctypes.byref(ng)))
     return [None if group_of[i] == 0xffffffff else group_of[i] for i in range(n)], ng.value
-
-
-MODE_EXACT, MODE_LEV, MODE_SUBS = 0, 1, 2          # fz_batch_search's mode (FzMode of csrc/fz_device.h)
 
 
 def batch_segment(offs, idx):
@@ -807,11 +811,20 @@ class Engine(object):
         """[lev_ngrams_consolidated(seq, p, k) for p in patterns] (fz_lev_ngrams_multi_consolidated)."""
         return self._multi(self._lib.fz_lev_ngrams_multi_consolidated, seq, patterns, k, as_array)
 
-    def multi_rows_call(self, seq, patterns, k):
-        """fz_lev_ngrams_multi_consolidated -> (OwnedRows of all patterns' rows, row offsets per pattern), for callers that
-        build Match objects in C straight from the result buffer."""
+    def subs_ngrams_multi(self, seq, patterns, k, as_array=False):
+        """[subs_ngrams(seq, p, k) for p in patterns] in as few passes over the sequence as the patterns allow
+        (fz_subs_ngrams_multi): a list with one raw stream per pattern."""
+        return self._multi(self._lib.fz_subs_ngrams_multi, seq, patterns, k, as_array)
+
+    def subs_ngrams_multi_best(self, seq, patterns, k, as_array=False):
+        """[subs_ngrams_best(seq, p, k) for p in patterns] (fz_subs_ngrams_multi_best)."""
+        return self._multi(self._lib.fz_subs_ngrams_multi_best, seq, patterns, k, as_array)
+
+    def multi_rows_call(self, seq, patterns, k, fn=None):
+        """fz_lev_ngrams_multi_consolidated (or `fn`: fz_subs_ngrams_multi_best) -> (OwnedRows of all patterns' rows, row
+        offsets per pattern), for callers that build Match objects in C straight from the result buffer."""
         patterns = list(patterns)
-        ptr, bounds = self._multi_call(self._lib.fz_lev_ngrams_multi_consolidated, seq, patterns, k)
+        ptr, bounds = self._multi_call(fn or self._lib.fz_lev_ngrams_multi_consolidated, seq, patterns, k)
         return OwnedRows(self._lib, ptr, bounds[-1]), bounds
 
     def lev_ngrams_begin(self, seq, pattern, k):

@@ -1196,8 +1196,65 @@ inline uint32_t fz_mp_build(uint32_t *desc, const uint8_t *const *pat, const uin
 struct FzMpArgs {
     FzGeom   geom;
     uint32_t k, L;
-    uint32_t win_dwords;                         // window dwords staged per lane ((longest m + 2k + 6) / 4 + 1)
+    uint32_t win_dwords;                         // window dwords staged per lane ((longest m + 2k + 6) / 4 + 1; substitutions
+                                                 // only: (longest m + 3) / 4 + 1 — no reach beyond the window)
     uint32_t nent;                               // entries of the block table
     uint64_t hit_cap;                            // capacity of EACH of the FZ_MP_LISTS hit lists
     uint64_t rec_cap;
 };
+
+// ---------------------------------------------------------------------------------------------
+// Multi-pattern search, substitutions only (fz_subs_ngrams_multi; fz_kernels.h: fz_mp_verify_subs_kernel).  The per-candidate
+// part works a dword at a time on two dword-readable sources:
+//   t.dword(j)   dword j of the candidate's staged window; the window [i0, i0 + m) starts `sh` (0 .. 3) bytes into dword 0
+//   p4[j * ps]   dword j of the candidate's pattern (the descriptor's row: dword-aligned, bytes behind m are zero)
+// Each step brings two window dwords to the pattern's alignment, xors, reduces the xor to one bit per differing byte and
+// keeps the bytes a mask names.
+
+// Bytes b of the dword at pattern offset q (q % 4 == 0) with lo <= q + b < hi, as a mask of whole bytes.
+FZ_HD uint32_t fz_dword_bytes_in(uint32_t q, uint32_t lo, uint32_t hi) {
+    const uint32_t b0 = lo > q ? lo - q : 0u;
+    const uint32_t b1 = hi > q ? (hi - q < 4u ? hi - q : 4u) : 0u;
+    if (b0 >= b1) return 0u;                                                     // (b0 < b1 <= 4: b0 <= 3)
+    const uint32_t upto = b1 == 4u ? 0xffffffffu : (1u << (8u * b1)) - 1u;
+    return upto & ~((1u << (8u * b0)) - 1u);
+}
+
+// Bit 7 of every byte in which the window dword (hi:lo shifted right by sh bytes) differs from the pattern dword.
+FZ_HD uint32_t fz_dword_diff(uint32_t lo, uint32_t hi, uint32_t sh, uint32_t pat) {
+    const uint32_t d = (uint32_t)(((((uint64_t)hi) << 32) | lo) >> (8u * sh)) ^ pat;
+    return (((d & 0x7f7f7f7fu) + 0x7f7f7f7fu) | d) & 0x80808080u;
+}
+
+// The exact n-gram test: does the window equal the pattern on [s, s + L)?  (The filter reports hashes, not comparisons.)
+// Every lane walks the dwords that hold ITS block: (L + 6) / 4 + 1 steps at the most, the same number for the wave.
+template <class Win>
+FZ_HD bool fz_mp_block_equal(const Win &t, uint32_t sh, const uint32_t *p4, uint32_t ps, uint32_t L, uint32_t s) {
+    const uint32_t q0 = s & ~3u;
+    uint32_t prev = t.dword(q0 >> 2), bad = 0;
+    for (uint32_t q = q0; q < s + L; q += 4u) {
+        const uint32_t next = t.dword((q >> 2) + 1u);
+        bad |= fz_dword_diff(prev, next, sh, p4[(q >> 2) * ps]) & fz_dword_bytes_in(q, s, s + L);
+        prev = next;
+    }
+    return bad == 0u;
+}
+
+// fz_verify_subs for a candidate of a group (same rec.l = s, rec.r = m - s - L, rec.dist): the mismatches of the window
+// against the pattern OUTSIDE the block [s, s + L), accepted when they are <= k.  The loop runs over the dwords of the
+// group's longest pattern m_max (wave-uniform; a shorter pattern's bytes behind m are masked out) and is left, every other
+// dword, once no lane of the wave is within its budget — as fz_verify_subs_wave does for one pattern.
+template <class Win>
+FZ_HD bool fz_mp_verify_subs(const Win &t, uint32_t sh, const uint32_t *p4, uint32_t ps, uint32_t m, uint32_t m_max, uint32_t k,
+                             uint32_t L, uint32_t s, bool valid, FzRec &rec) {
+    uint32_t prev = t.dword(0u), nd = 0;
+    for (uint32_t q = 0; q < m_max; q += 4u) {
+        const uint32_t next = t.dword((q >> 2) + 1u);
+        const uint32_t keep = fz_dword_bytes_in(q, 0u, s) | fz_dword_bytes_in(q, s + L, m);
+        nd += (uint32_t)__builtin_popcount(fz_dword_diff(prev, next, sh, p4[(q >> 2) * ps]) & keep);
+        prev = next;
+        if ((q & 4u) && !FZ_WAVE_BALLOT(valid && nd <= k)) break;
+    }
+    rec.l = s; rec.r = m - s - L; rec.dist = nd; rec.aux = 0;
+    return valid && nd <= k;
+}

@@ -2283,3 +2283,108 @@ __global__ __launch_bounds__(FZ_FILTER_THREADS) void fz_mp_verify_kernel(const u
     }
     if (lane == 0 && confirmed) atomicAdd(&counters[8u + (blockIdx.x & 63u)], (unsigned long long)confirmed);
 }
+
+// fz_mp_verify_kernel's counterpart for substitutions-only groups (fz_subs_ngrams_multi): same launch shape, hit lists,
+// counters and records; per candidate the reference's _substitutions_only_ngrams_template.h:97-121 against the LANE's pattern.
+//   * the block's hit range is fz_block_range(FZ_MODE_SUBS): the window [idx - s, idx - s + m) lies inside [0, n) — no clamps,
+//     no +-k reach, so the window is staged whole or the candidate is dropped, and there is no score ring: a wave's LDS is
+//     win_dwords x 256 bytes with win_dwords = (longest m + 3) / 4 + 1;
+//   * window dword d of lane l sits at win[d * 64 + l]: a ds_read_b32 banks by dword address mod 32 within each 32-lane
+//     half, so the lanes of a half read 32 different banks — no conflicts, whatever the lanes' alignments;
+//   * the pattern table is TRANSPOSED on its way into LDS: dword j of pattern i at pat4[j * 64 + i].  The descriptor's rows
+//     are 128 bytes = 32 dwords apart, which would put dword j of EVERY pattern on bank j: up to 32-way when every lane of a
+//     half holds another pattern.  Transposed, the bank is i mod 32: lanes of one pattern broadcast, lanes of different
+//     patterns conflict two-way at the most (patterns i and i + 32 in one half);
+//   * exact n-gram test (fz_mp_block_equal), then the mismatches outside the block (fz_mp_verify_subs), both a dword per
+//     step and wave-uniform in their trip counts.
+struct FzLdsColumn {
+    const uint32_t *base;                                  // the lane's dword 0; consecutive dwords are 64 apart
+    __device__ __forceinline__ uint32_t dword(uint32_t j) const { return base[j * 64u]; }
+};
+
+__host__ __device__ inline uint32_t fz_mp_verify_subs_lds(uint32_t win_dwords) {
+    return FZ_MP_VERIFY_WORDS * 4u + FZ_WAVES_PER_BLOCK * win_dwords * 256u;
+}
+
+__global__ __launch_bounds__(FZ_FILTER_THREADS) void fz_mp_verify_subs_kernel(const uint8_t *__restrict__ buf, const FzMpArgs a,
+                                                                              const uint32_t *__restrict__ desc, const uint64_t *__restrict__ hits,
+                                                                              FzRec *__restrict__ recs, unsigned long long *__restrict__ counters) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    uint32_t *tab = reinterpret_cast<uint32_t *>(smem);
+    constexpr uint32_t kPat = FZ_MP_DESC_PAT - FZ_MP_DESC_ENT, kRow = FZ_MP_MAX_M / 4u;
+    static_assert(FZ_MP_MAX_PATS == 64u, "the transposed pattern table has one column per pattern");
+    for (uint32_t i = threadIdx.x; i < FZ_MP_VERIFY_WORDS; i += FZ_FILTER_THREADS) {
+        const uint32_t v = desc[FZ_MP_DESC_ENT + i];
+        if (i < kPat) tab[i] = v;
+        else tab[kPat + ((i - kPat) % kRow) * FZ_MP_MAX_PATS + (i - kPat) / kRow] = v;
+    }
+    __syncthreads();
+    const uint32_t *ent = tab;
+    const uint32_t *pm = tab + (FZ_MP_DESC_M - FZ_MP_DESC_ENT);
+    const uint32_t *pat4 = tab + kPat;
+    const uint32_t lane = fz_lane();
+    uint32_t *win = reinterpret_cast<uint32_t *>(smem + FZ_MP_VERIFY_WORDS * 4u) + (threadIdx.x >> 6) * a.win_dwords * 64u;
+    const uint32_t m_max = (a.win_dwords - 1u) * 4u;       // (the longest pattern rounded up to dwords)
+    const uint64_t waves = (uint64_t)gridDim.x * FZ_WAVES_PER_BLOCK;
+    const uint64_t wave = (uint64_t)blockIdx.x * FZ_WAVES_PER_BLOCK + (threadIdx.x >> 6);
+    const uint64_t n = a.geom.n;
+    const uint64_t data_end = a.geom.buf_off + a.geom.buf_len;
+    uint32_t confirmed = 0;
+    for (uint32_t l = 0; l < FZ_MP_LISTS; ++l) {
+        unsigned long long nh = counters[FZ_MP_CTR_LIST(l)];
+        if (nh > a.hit_cap) nh = a.hit_cap;
+        const uint64_t *lh = hits + (uint64_t)l * a.hit_cap;
+        for (uint64_t q0 = ((wave + 251u * l) % waves) * 64u; q0 < nh; q0 += waves * 64u) {
+            const uint64_t q = q0 + lane;
+            const bool have = q < nh;
+            const uint64_t hit = have ? lh[q] : 0ull;
+            const uint32_t e = ent[fz_hit_block(hit) & (FZ_MP_MAX_BLOCKS - 1u)];
+            const uint32_t pid = e & (FZ_MP_MAX_PATS - 1u), g = (e >> 8) & 0xffu, s = e >> 16;
+            const uint32_t m = pm[pid];
+            const uint64_t idx = fz_hit_index(hit);
+            // the block's hit range (template.h:97-101): s <= idx and idx - s + m <= n; ownership; the whole window resident
+            uint32_t lo_rel, hi_sub;
+            fz_block_range(FZ_MODE_SUBS, m, a.k, a.L, s, lo_rel, hi_sub);
+            bool valid = have && fz_hit_block(hit) < a.nent && m != 0u && m <= m_max && s + a.L <= m &&
+                         idx >= lo_rel && n >= hi_sub && idx + a.L <= n - hi_sub &&
+                         idx >= a.geom.own_lo && idx < a.geom.own_hi && idx - lo_rel >= a.geom.buf_off && idx + a.L + hi_sub <= data_end;
+            if (!__ballot(valid)) continue;
+            const uint64_t i0 = valid ? idx - s : a.geom.buf_off;
+            const uint64_t wbase = a.geom.buf_off + ((i0 - a.geom.buf_off) & ~(uint64_t)3);
+            const uint32_t sh = (uint32_t)(i0 - wbase);
+            uint32_t nd = valid ? (uint32_t)((i0 + m - wbase + 3) >> 2) : 0u;      // <= (m + 6) / 4 <= win_dwords
+            if (nd > a.win_dwords) nd = a.win_dwords;
+            const int64_t lbase = (int64_t)(wbase - a.geom.buf_off);
+            for (uint32_t d0 = 0; d0 < a.win_dwords; d0 += 8) {
+                uint32_t x[8];
+#pragma unroll
+                for (uint32_t j = 0; j < 8; ++j)
+                    x[j] = (d0 + j < nd) ? *reinterpret_cast<const uint32_t *>(buf + lbase + (int64_t)(d0 + j) * 4) : 0u;
+#pragma unroll
+                for (uint32_t j = 0; j < 8; ++j)
+                    if (d0 + j < a.win_dwords) win[(d0 + j) * 64u + lane] = x[j];
+            }
+            fz_wave_lds_sync();
+            const FzLdsColumn t{win + lane};
+            const uint32_t *p4 = pat4 + pid;
+            valid = valid && fz_mp_block_equal(t, sh, p4, FZ_MP_MAX_PATS, a.L, valid ? s : 0u);
+            confirmed += (uint32_t)__popcll(__ballot(valid));
+            FzRec rec;
+            const bool ok = fz_mp_verify_subs(t, sh, p4, FZ_MP_MAX_PATS, m, m_max, a.k, a.L, s, valid, rec);
+            const unsigned long long mask = __ballot(ok);
+            if (mask) {
+                unsigned long long base = 0;
+                if (lane == 0) base = atomicAdd(&counters[FZ_MP_CTR_RECS], (unsigned long long)__popcll(mask));
+                base = fz_bcast64(base);
+                if (ok) {
+                    rec.key = fz_hit_pack(g, idx);
+                    rec.aux = pid;
+                    const unsigned long long slot = base + fz_rank(mask);
+                    if (slot < a.rec_cap) recs[slot] = rec;
+                }
+            }
+            fz_wave_lds_sync();
+        }
+    }
+    if (lane == 0 && confirmed) atomicAdd(&counters[8u + (blockIdx.x & 63u)], (unsigned long long)confirmed);
+}

@@ -64,6 +64,8 @@ struct Switches {
     int gh_waves = 0;                  // FZ_GH_WAVES=1 / 2 / 4: waves per hit of fz_gen_hit_kernel
     bool gh_no_bits = false;           // FZ_GH_NO_BITS: round 4's candidate step instead of the bit-parallel one
     int cand_lds_max = 0;              // FZ_CAND_LDS_MAX=n: candidate lists beyond n entries live in HBM
+    bool mp_force_pass = false;        // FZ_MP_FORCE_PASS: every multi-pattern group of two or more rides a pass, whatever the cost rule expects
+                                       // (how benchmarks/multi_pattern.py measures the cells the rule gives to the loop)
     bool no_dev_threads = false;       // FZ_NO_DEV_THREADS: a multi-device context drives every device from the calling thread
     int taper_steps = 4;               // FZ_TAPER_STEPS (0: no regions), FZ_TAPER_MIN, FZ_TAPER_WG_PER_CU: the scan grid's last round
     double taper_min = 0.25;
@@ -92,6 +94,7 @@ Switches read_switches() {
         if (const char *e = getenv("FZ_RCCL_LIB")) v.rccl_lib = e;
         if (const char *e = getenv("ROCM_PATH")) v.rocm_path = e;
         if (const char *e = getenv("FZ_COMM_TIMEOUT_MS")) v.comm_timeout_ms = std::max(1L, atol(e));
+        v.mp_force_pass = flag("FZ_MP_FORCE_PASS");
         v.trace = flag("FZ_TRACE"); v.stream_trace = flag("FZ_STREAM_TRACE");
         return v;
 }
@@ -2756,7 +2759,9 @@ int fz_lev_ngrams_consolidated(fz_ctx *ctx, fz_seq *seq, const uint8_t *p, uint3
 
 // ---------------------------------------------------------------------------------------------
 // Multi-pattern search: many patterns, one budget, one resident sequence, as few passes over it as the patterns allow
-// (fz_device.h: the fz_mp_* table; fz_kernels.h: fz_mp_filter_kernel / fz_mp_verify_kernel).
+// (fz_device.h: the fz_mp_* table; fz_kernels.h: fz_mp_filter_kernel / fz_mp_verify_kernel / fz_mp_verify_subs_kernel).
+// The filter knows nothing about the distance; `mode` (FZ_MODE_LEV or FZ_MODE_SUBS) picks the verification kernel, the
+// window a candidate needs and the cost rule's constants.
 
 // Where every pattern of a list rides: a function of the arguments alone.  Patterns inside the batched domain are grouped by
 // their n-gram length L = m / (k + 1) in input order; a group is closed when the next pattern of its L would take it beyond
@@ -2765,7 +2770,10 @@ int fz_lev_ngrams_consolidated(fz_ctx *ctx, fz_seq *seq, const uint8_t *p, uint3
 // of their first pattern.
 struct MpGroup { uint32_t L = 0, blocks = 0; std::vector<uint32_t> pats; };
 
-static bool mp_in_domain(uint32_t m, uint32_t k) {
+// (The same domain for both modes.  Hamming verification has no register band and would take k above FZ_MP_MAX_K; nothing
+// measured asks for it yet, so substitutions keep the Levenshtein domain.)
+static bool mp_in_domain(uint32_t mode, uint32_t m, uint32_t k) {
+    (void)mode;
     return k >= 1 && k <= FZ_MP_MAX_K && m <= FZ_MP_MAX_M && m / (k + 1) >= FZ_MP_MIN_L;
 }
 
@@ -2780,8 +2788,16 @@ static bool mp_in_domain(uint32_t m, uint32_t k) {
 constexpr double kMpPass = 0.50, kMpPerBlock = 0.0098, kMpPerCand = 0.085;
 constexpr double kLoopScan = 0.185, kLoopPerCand = 0.032;
 constexpr double kMpMargin = 0.9;
+// Substitutions only (profiles/r10_multi_pattern_subs.txt, the same 1 GiB of DNA, every cell forced onto a pass; DESIGN.md
+// section 6).  The pass keeps the filter's terms — it is the same kernel.  The loop is one synchronous fz_subs_ngrams per
+// pattern: 0.201 P + 0.031 C by least squares over the sixteen cells (residuals below 9 %).  The pass's cost per candidate
+// is not a constant — 0.062 ms per million at 3 M candidates, 0.016 at 268 M: the filter's rare path saturates — so it is
+// set where the rule decides: every value in [0.032, 0.054] sends each of the sixteen cells where it measured faster, and
+// the constant is the middle of that interval.
+constexpr double kMpSubsPerCand = 0.043;
+constexpr double kLoopSubsScan = 0.201, kLoopSubsPerCand = 0.031;
 
-static bool mp_worth_a_pass(const uint8_t *pats, const uint64_t *offs, const MpGroup &g) {
+static bool mp_worth_a_pass(uint32_t mode, const uint8_t *pats, const uint64_t *offs, const MpGroup &g) {
     bool seen[256] = {false};
     uint32_t sigma = 0;
     for (uint32_t i : g.pats)
@@ -2790,21 +2806,22 @@ static bool mp_worth_a_pass(const uint8_t *pats, const uint64_t *offs, const MpG
     double frac = (double)g.blocks;
     for (uint32_t i = 0; i < g.L && frac > 1e-12; ++i) frac /= (double)sigma;
     const double cand = std::min(frac, (double)g.blocks) * 1073.741824;      // millions per GiB
-    const double pass = kMpPass + kMpPerBlock * g.blocks + kMpPerCand * cand;
-    const double loop = kLoopScan * (double)g.pats.size() + kLoopPerCand * cand;
+    const bool subs = mode == FZ_MODE_SUBS;
+    const double pass = kMpPass + kMpPerBlock * g.blocks + (subs ? kMpSubsPerCand : kMpPerCand) * cand;
+    const double loop = (subs ? kLoopSubsScan : kLoopScan) * (double)g.pats.size() + (subs ? kLoopSubsPerCand : kLoopPerCand) * cand;
     return pass < kMpMargin * loop;
 }
 
-static void mp_plan(const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k, std::vector<MpGroup> &groups,
+static void mp_plan(uint32_t mode, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k, std::vector<MpGroup> &groups,
                     std::vector<uint32_t> &group_of) {
     groups.clear();
     group_of.assign(n_pats, 0xffffffffu);
     std::vector<MpGroup> open;                                  // at most one open group per L
     std::vector<MpGroup> closed;
-    auto close = [&](MpGroup &g) { if (g.pats.size() > 1 && mp_worth_a_pass(pats, offs, g)) closed.push_back(g); };
+    auto close = [&](MpGroup &g) { if (g.pats.size() > 1 && (sw().mp_force_pass || mp_worth_a_pass(mode, pats, offs, g))) closed.push_back(g); };
     for (uint32_t i = 0; i < n_pats; ++i) {
         const uint64_t m64 = offs[i + 1] - offs[i];
-        if (m64 > FZ_MP_MAX_M || !mp_in_domain((uint32_t)m64, k)) continue;
+        if (m64 > FZ_MP_MAX_M || !mp_in_domain(mode, (uint32_t)m64, k)) continue;
         const uint32_t m = (uint32_t)m64, L = m / (k + 1), nb = m / L;
         MpGroup *g = nullptr;
         for (MpGroup &o : open) if (o.L == L) g = &o;
@@ -2847,7 +2864,7 @@ struct MpTotals { uint64_t bytes = 0, hits = 0, rows = 0; uint32_t launches = 0;
 // arguments — the project's estimate of expected candidates, sequence bytes x blocks / sigma^L (sigma = distinct symbols
 // of the group's patterns), twice over and spread over the lists; a launch that overflows a list or the record buffer is
 // run again with what its counters ask for.
-static int mp_run_shard(fz_ctx *ctx, const Shard &sh, const uint32_t *desc, uint32_t nent, uint32_t k, uint32_t L, uint32_t max_m,
+static int mp_run_shard(fz_ctx *ctx, const Shard &sh, uint32_t mode, const uint32_t *desc, uint32_t nent, uint32_t k, uint32_t L, uint32_t max_m,
                         uint32_t sigma, std::vector<FzRec> &recs, MpTotals &tot) {
     DevState &d = ctx->devs[sh.dev];
     const uint64_t ntiles = (sh.geom.buf_len + FZ_TILE_BYTES - 1) / FZ_TILE_BYTES;
@@ -2861,7 +2878,8 @@ static int mp_run_shard(fz_ctx *ctx, const Shard &sh, const uint32_t *desc, uint
     memset(&a, 0, sizeof a);
     a.geom = sh.geom;
     a.k = k; a.L = L; a.nent = nent;
-    a.win_dwords = (max_m + 2 * k + 6) / 4 + 1;
+    const bool subs = mode == FZ_MODE_SUBS;
+    a.win_dwords = subs ? (max_m + 3) / 4 + 1 : (max_m + 2 * k + 6) / 4 + 1;
     using FilterKernel = void (*)(const uint8_t *, const FzMpArgs, uint64_t, const uint32_t *, uint64_t *, unsigned long long *);
     static const FilterKernel filters[6] = {nullptr, fz_mp_filter_kernel<1>, fz_mp_filter_kernel<2>, fz_mp_filter_kernel<3>,
                                             fz_mp_filter_kernel<4>, fz_mp_filter_kernel<5>};
@@ -2881,8 +2899,12 @@ static int mp_run_shard(fz_ctx *ctx, const Shard &sh, const uint32_t *desc, uint
                            reinterpret_cast<uint64_t *>(d.d_mp_hits), dctr);
         HIP_TRY(hipGetLastError());
         if (ctx->timing) HIP_TRY(hipEventRecord(d.ev[1], d.stream));
-        hipLaunchKernelGGL(fz_mp_verify_kernel, dim3((uint32_t)d.n_cus * 4), dim3(FZ_FILTER_THREADS), fz_mp_verify_lds(a.win_dwords), d.stream,
-                           sh.d_buf, a, ddesc, reinterpret_cast<const uint64_t *>(d.d_mp_hits), reinterpret_cast<FzRec *>(d.d_mp_recs), dctr);
+        if (subs)
+            hipLaunchKernelGGL(fz_mp_verify_subs_kernel, dim3((uint32_t)d.n_cus * 4), dim3(FZ_FILTER_THREADS), fz_mp_verify_subs_lds(a.win_dwords), d.stream,
+                               sh.d_buf, a, ddesc, reinterpret_cast<const uint64_t *>(d.d_mp_hits), reinterpret_cast<FzRec *>(d.d_mp_recs), dctr);
+        else
+            hipLaunchKernelGGL(fz_mp_verify_kernel, dim3((uint32_t)d.n_cus * 4), dim3(FZ_FILTER_THREADS), fz_mp_verify_lds(a.win_dwords), d.stream,
+                               sh.d_buf, a, ddesc, reinterpret_cast<const uint64_t *>(d.d_mp_hits), reinterpret_cast<FzRec *>(d.d_mp_recs), dctr);
         HIP_TRY(hipGetLastError());
         if (ctx->timing) HIP_TRY(hipEventRecord(d.ev[2], d.stream));
         unsigned long long ctr[FZ_MP_CTR_WORDS];
@@ -2919,7 +2941,7 @@ static int mp_run_shard(fz_ctx *ctx, const Shard &sh, const uint32_t *desc, uint
     return fail(FZ_EDEVICE, "result buffers kept overflowing");
 }
 
-static int mp_run_group(fz_ctx *ctx, fz_seq *seq, const uint8_t *pats, const uint64_t *offs, uint32_t k, const MpGroup &g,
+static int mp_run_group(fz_ctx *ctx, fz_seq *seq, uint32_t mode, const uint8_t *pats, const uint64_t *offs, uint32_t k, const MpGroup &g,
                         std::vector<std::vector<fz_match>> &rows, MpTotals &tot) {
     const uint32_t np = (uint32_t)g.pats.size();
     const uint8_t *pp[FZ_MP_MAX_PATS];
@@ -2937,7 +2959,7 @@ static int mp_run_group(fz_ctx *ctx, fz_seq *seq, const uint8_t *pats, const uin
     if (nent == 0 || nent != g.blocks) return fail(FZ_EDEVICE, "internal: the group's block table does not match its plan");
     std::vector<FzRec> recs;
     for (const Shard &sh : seq->shards) {
-        int rc = mp_run_shard(ctx, sh, desc.data(), nent, k, g.L, max_m, std::max(1u, sigma), recs, tot);
+        int rc = mp_run_shard(ctx, sh, mode, desc.data(), nent, k, g.L, max_m, std::max(1u, sigma), recs, tot);
         if (rc) return rc;
     }
     // per pattern: its records (aux = the pattern's number in the group) in the reference's order — block ascending, hit
@@ -2964,8 +2986,13 @@ static int mp_check_lists(const uint8_t *pats, const uint64_t *offs, uint32_t n_
     return FZ_OK;
 }
 
-static int lev_multi_impl(fz_ctx *ctx, fz_seq *seq, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k,
-                          bool consolidated, fz_match **out, uint64_t **out_offs) {
+// fz_lev_ngrams_multi* (mode = FZ_MODE_LEV; reduced: fz_consolidate per pattern) and fz_subs_ngrams_multi* (FZ_MODE_SUBS;
+// reduced: fz_group_best per pattern).
+static int subs_plan(fz_ctx *ctx, fz_seq *seq, const uint8_t *p, uint32_t m, uint32_t k, Search &q, bool in_pipeline = false);
+
+static int multi_impl(fz_ctx *ctx, fz_seq *seq, uint32_t mode, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k,
+                      bool consolidated, fz_match **out, uint64_t **out_offs) {
+    const bool subs = mode == FZ_MODE_SUBS;
     if (!out || !out_offs) return fail(FZ_EINVAL, "null argument");
     *out = nullptr; *out_offs = nullptr;
     if (!ctx || !seq || seq->ctx != ctx) return fail(FZ_EINVAL, "bad ctx/seq handle");
@@ -2979,7 +3006,8 @@ static int lev_multi_impl(fz_ctx *ctx, fz_seq *seq, const uint8_t *pats, const u
         const uint64_t m = offs[i + 1] - offs[i];
         if (m > FZ_MAX_M_ANY) return fail(FZ_EUNSUPPORTED, "subsequence longer than %u bytes", FZ_MAX_M_ANY);
         Search q;
-        rc = lev_plan(ctx, seq, m ? pats + offs[i] : nullptr, (uint32_t)m, k, q);
+        rc = subs ? subs_plan(ctx, seq, m ? pats + offs[i] : nullptr, (uint32_t)m, k, q)
+                  : lev_plan(ctx, seq, m ? pats + offs[i] : nullptr, (uint32_t)m, k, q);
         if (rc) return rc;
     }
     std::vector<MpGroup> groups;
@@ -2987,7 +3015,7 @@ static int lev_multi_impl(fz_ctx *ctx, fz_seq *seq, const uint8_t *pats, const u
     // a context in a communicator searches collectively, pattern by pattern, through the existing collective search
     bool batched = !ctx->snapshot;
     for (const Shard &sh : seq->shards) batched = batched && sh.geom.seg_stride == 0;
-    if (batched) mp_plan(pats, offs, n_pats, k, groups, group_of);
+    if (batched) mp_plan(mode, pats, offs, n_pats, k, groups, group_of);
     else group_of.assign(n_pats, 0xffffffffu);
     std::vector<std::vector<fz_match>> rows(n_pats);
     MpTotals tot;
@@ -2996,7 +3024,9 @@ static int lev_multi_impl(fz_ctx *ctx, fz_seq *seq, const uint8_t *pats, const u
         if (group_of[i] != 0xffffffffu) continue;
         fz_match *one = nullptr;
         uint64_t n_one = 0;
-        rc = fz_lev_ngrams(ctx, seq, pats + offs[i], (uint32_t)(offs[i + 1] - offs[i]), k, &one, &n_one);
+        const uint32_t m = (uint32_t)(offs[i + 1] - offs[i]);
+        if (subs && seq->n < m) continue;                      // (fz_subs_ngrams answers before it searches: nothing to count)
+        rc = subs ? fz_subs_ngrams(ctx, seq, pats + offs[i], m, k, &one, &n_one) : fz_lev_ngrams(ctx, seq, pats + offs[i], m, k, &one, &n_one);
         if (rc) return rc;
         rows[i].assign(one, one + n_one);
         release_out(one);
@@ -3006,7 +3036,7 @@ static int lev_multi_impl(fz_ctx *ctx, fz_seq *seq, const uint8_t *pats, const u
     }
     ctx->view = nullptr; ctx->view_n = 0; ctx->rows_ready = false;
     for (const MpGroup &g : groups) {
-        rc = mp_run_group(ctx, seq, pats, offs, k, g, rows, tot);
+        rc = mp_run_group(ctx, seq, mode, pats, offs, k, g, rows, tot);
         if (rc) return rc;
         form = FZ_FORM_KERNEL;
     }
@@ -3015,7 +3045,7 @@ static int lev_multi_impl(fz_ctx *ctx, fz_seq *seq, const uint8_t *pats, const u
         for (uint32_t i = 0; i < n_pats; ++i) {
             fz_match *c = nullptr;
             uint64_t nc = 0;
-            rc = fz_consolidate(rows[i].data(), rows[i].size(), &c, &nc);
+            rc = subs ? fz_group_best(rows[i].data(), rows[i].size(), &c, &nc) : fz_consolidate(rows[i].data(), rows[i].size(), &c, &nc);
             if (rc) return rc;
             rows[i].assign(c, c + nc);
             release_out(c);
@@ -3053,15 +3083,31 @@ static int lev_multi_impl(fz_ctx *ctx, fz_seq *seq, const uint8_t *pats, const u
 
 int fz_lev_ngrams_multi(fz_ctx *ctx, fz_seq *seq, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k,
                         fz_match **out, uint64_t **out_offs) {
-    return lev_multi_impl(ctx, seq, pats, offs, n_pats, k, false, out, out_offs);
+    return multi_impl(ctx, seq, FZ_MODE_LEV, pats, offs, n_pats, k, false, out, out_offs);
 }
 
 int fz_lev_ngrams_multi_consolidated(fz_ctx *ctx, fz_seq *seq, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k,
                                      fz_match **out, uint64_t **out_offs) {
-    return lev_multi_impl(ctx, seq, pats, offs, n_pats, k, true, out, out_offs);
+    return multi_impl(ctx, seq, FZ_MODE_LEV, pats, offs, n_pats, k, true, out, out_offs);
+}
+
+int fz_subs_ngrams_multi(fz_ctx *ctx, fz_seq *seq, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k,
+                         fz_match **out, uint64_t **out_offs) {
+    return multi_impl(ctx, seq, FZ_MODE_SUBS, pats, offs, n_pats, k, false, out, out_offs);
+}
+
+int fz_subs_ngrams_multi_best(fz_ctx *ctx, fz_seq *seq, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k,
+                              fz_match **out, uint64_t **out_offs) {
+    return multi_impl(ctx, seq, FZ_MODE_SUBS, pats, offs, n_pats, k, true, out, out_offs);
 }
 
 int fz_debug_multi_plan(const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k, uint32_t *group_of, uint32_t *n_groups) {
+    return fz_debug_multi_plan_mode(FZ_MODE_LEV, pats, offs, n_pats, k, group_of, n_groups);
+}
+
+int fz_debug_multi_plan_mode(uint32_t mode, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k, uint32_t *group_of,
+                             uint32_t *n_groups) {
+    if (mode != FZ_MODE_LEV && mode != FZ_MODE_SUBS) return fail(FZ_EINVAL, "mode must be Levenshtein or substitutions-only");
     if (!group_of || !n_groups) return fail(FZ_EINVAL, "null argument");
     int rc = mp_check_lists(pats, offs, n_pats);
     if (rc) return rc;
@@ -3073,14 +3119,14 @@ int fz_debug_multi_plan(const uint8_t *pats, const uint64_t *offs, uint32_t n_pa
     }
     std::vector<MpGroup> groups;
     std::vector<uint32_t> of;
-    mp_plan(pats, offs, n_pats, k, groups, of);
+    mp_plan(mode, pats, offs, n_pats, k, groups, of);
     for (uint32_t i = 0; i < n_pats; ++i) group_of[i] = of[i];
     *n_groups = (uint32_t)groups.size();
     return FZ_OK;
 }
 
 // Argument checks and the block plan of the substitutions-only n-gram search (template :92-101).
-static int subs_plan(fz_ctx *ctx, fz_seq *seq, const uint8_t *p, uint32_t m, uint32_t k, Search &q, bool in_pipeline = false) {
+static int subs_plan(fz_ctx *ctx, fz_seq *seq, const uint8_t *p, uint32_t m, uint32_t k, Search &q, bool in_pipeline) {
     int rc = validate(ctx, seq, p, m, in_pipeline);
     if (rc) return rc;
     const uint32_t L = m / (k + 1);

@@ -1,11 +1,17 @@
 """find_near_matches_multi: many subsequences, one sequence, one call.
 
 The value (and any exception) is that of ``[find_near_matches(p, sequence, ...) for p in subsequences]``.  What is new
-is the cost: the sequence is prepared once (one residency-cache acquire, or one upload), and the patterns on the
-Levenshtein n-gram route go through ONE C-ABI call (fz_lev_ngrams_multi_consolidated) that tests every byte offset of the
-sequence against the n-gram blocks of up to 64 patterns per pass.  Everything else — other strategy classes, the exact and
-linear-programming routes, sequences whose coding depends on the subsequence — takes the per-pattern code inside the same
-call, with the results in input order.
+is the cost: the sequence is prepared once (one residency-cache acquire, or one upload), and the patterns on an n-gram
+route go through ONE C-ABI call that tests every byte offset of the sequence against the n-gram blocks of up to 64 patterns
+per pass:
+
+* the Levenshtein n-gram route (``max_l_dist`` alone, or limits that do not bind): fz_lev_ngrams_multi_consolidated;
+* the substitutions-only n-gram route (``max_insertions=0, max_deletions=0`` — mismatch lists such as guides, barcodes and
+  primers): fz_subs_ngrams_multi_best for bytes-like sequences (the best match of every overlap group), the raw
+  fz_subs_ngrams_multi for latin-1 ``str`` sequences, whose result is every window once, sorted by start.
+
+Everything else — the generic class, the exact and linear-programming routes, sequences whose coding depends on the
+subsequence — takes the per-pattern code inside the same call, with the results in input order.
 """
 from .common import LevenshteinSearchParams, matches_from_rows_multi
 from .engine import is_byteslike, prepare_shared
@@ -35,14 +41,17 @@ def find_near_matches_multi(subsequences, sequence,
 
     ``sequence`` may be a ``resident()`` handle.  The first subsequence that ``find_near_matches`` would refuse raises
     its exception before anything is searched."""
-    from . import find_near_matches, choose_search_class, LevenshteinSearch
+    from . import find_near_matches, choose_search_class, LevenshteinSearch, SubstitutionsOnlySearch
+    from .substitutions_only import _finish_ngrams
     subsequences = list(subsequences)
     if not subsequences:
         return []
     limits = (max_substitutions, max_insertions, max_deletions, max_l_dist)
     search_params = LevenshteinSearchParams(*limits)
-    k = search_params.max_l_dist
-    batched_class = choose_search_class(search_params) is LevenshteinSearch and k > 0
+    search_class = choose_search_class(search_params)
+    subs = search_class is SubstitutionsOnlySearch
+    k = min(search_params.max_l_dist, search_params.max_substitutions) if subs else search_params.max_l_dist
+    batched_class = (subs or search_class is LevenshteinSearch) and k > 0
     shared = prepare_shared(sequence) if all(len(p) for p in subsequences) else None
     if shared is None:
         # nothing to share (or an empty subsequence, which raises at its turn): today's code, pattern by pattern
@@ -61,8 +70,14 @@ def find_near_matches_multi(subsequences, sequence,
                 # (a subsequence of the wrong kind for the sequence meets the sequence itself: find_near_matches' own error)
                 fits = is_byteslike(p) if pr.byteslike else isinstance(p, str)
                 results[i] = find_near_matches(p, view if fits else sequence, *limits)
-        if batch:
-            rows, bounds = pr.engine.multi_rows_call(pr.handle, [pb for _, pb in batch], k)
+        if batch and subs and not pr.byteslike:
+            # str: every window once, sorted by start — from the raw streams, as the single call makes it
+            raws = pr.engine.subs_ngrams_multi(pr.handle, [pb for _, pb in batch], k, as_array=True)
+            for (i, _), raw in zip(batch, raws):
+                results[i] = _finish_ngrams(raw, pr.original, False)
+        elif batch:
+            fn = pr.engine._lib.fz_subs_ngrams_multi_best if subs else None
+            rows, bounds = pr.engine.multi_rows_call(pr.handle, [pb for _, pb in batch], k, fn)
             for (i, _), matches in zip(batch, matches_from_rows_multi(rows, bounds, pr.original)):
                 results[i] = matches
         return results

@@ -215,6 +215,21 @@ int fz_lev_ngrams_multi_consolidated(fz_ctx *ctx, fz_seq *seq, const uint8_t *pa
 int fz_debug_multi_plan(const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k,
                         uint32_t *group_of, uint32_t *n_groups);
 
+/* The same for n_pats substitutions-only n-gram searches (k substitutions, no insertions or deletions): slice i of *out
+ * = byte for byte what fz_subs_ngrams(ctx, seq, pats + offs[i], offs[i+1] - offs[i], k, ...) returns.  Same domain, same
+ * grouping, same filter launch; the verification launch counts mismatches around the confirmed n-gram instead of running
+ * the edit-distance expansion, and the planner's cost rule has constants of its own for it (measured).
+ * Every pattern passes fz_subs_ngrams' checks first (the first one's error is the call's); patterns outside a group run
+ * through fz_subs_ngrams inside the call; collective contexts and strided sequences loop.  fz_stats as above. */
+int fz_subs_ngrams_multi(fz_ctx *ctx, fz_seq *seq, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats,
+                         uint32_t k, fz_match **out, uint64_t **out_offs);
+/* ... with every pattern's slice reduced by fz_group_best: slice i = what fz_subs_ngrams_best returns for pattern i. */
+int fz_subs_ngrams_multi_best(fz_ctx *ctx, fz_seq *seq, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats,
+                              uint32_t k, fz_match **out, uint64_t **out_offs);
+/* fz_debug_multi_plan for either mode: 1 = Levenshtein (what fz_debug_multi_plan answers), 2 = substitutions only. */
+int fz_debug_multi_plan_mode(uint32_t mode, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k,
+                             uint32_t *group_of, uint32_t *n_groups);
+
 /* One pattern, many sequences, one pass.  fz_batch_upload makes n_seqs sequences resident, packed back to back without
  * separators: sequence j = bytes[offs[j] .. offs[j+1]) (offs has n_seqs + 1 entries, offs[0] == 0, non-decreasing; equal
  * neighbours = an empty sequence).  n_seqs < 2^32.  Next to the bytes two tables go to the device: the cumulative end
