@@ -11,7 +11,7 @@ include/fzhip.h; this package is plain Python + ctypes (no PyTorch) and has NO C
 Extra, MI355X-specific surface: ``resident(sequence)`` uploads a long sequence to HBM once so that
 many patterns can be searched without re-crossing PCIe; ``find_near_matches_multi`` searches many subsequences in one
 sequence and ``find_near_matches_batch`` one subsequence in many sequences (``resident_batch`` keeps them in HBM), each
-in one pass.
+in one pass; ``find_near_matches_multi_batch`` searches many subsequences in many sequences, a pass per group of up to 64.
 """
 import io
 
@@ -25,6 +25,7 @@ from .substitutions_only import SubstitutionsOnlySearch
 from . import _file_stream
 from .multi import find_near_matches_multi
 from .batch import find_near_matches_batch, resident_batch
+from .multi_batch import find_near_matches_multi_batch
 
 __version__ = '0.1.0'
 
@@ -33,6 +34,7 @@ __all__ = [
     'find_near_matches_in_file',
     'find_near_matches_multi',
     'find_near_matches_batch',
+    'find_near_matches_multi_batch',
     'Match',
     'resident',
     'resident_batch',

@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = (
     "fz_lev_ngrams_multi", "fz_lev_ngrams_multi_consolidated", "fz_debug_multi_plan",
     "fz_subs_ngrams_multi", "fz_subs_ngrams_multi_best", "fz_debug_multi_plan_mode",
     "fz_batch_upload", "fz_batch_search", "fz_debug_batch_segment",
+    "fz_batch_search_multi",
 )
 
 
@@ -170,6 +171,10 @@ def load_library():
         L.fz_batch_upload.argtypes = [vp, u8p, u64p, u64, ctypes.POINTER(vp)]
         L.fz_batch_search.restype = ci
         L.fz_batch_search.argtypes = [vp, vp, u32, u8p, u32, u32, ci, mpp, ctypes.POINTER(ctypes.POINTER(u32)), u64p]
+        if hasattr(L, "fz_batch_search_multi"):             # (absent from builds of earlier rounds named by FUZZYSEARCH_HIP_LIB for an A/B)
+            L.fz_batch_search_multi.restype = ci
+            L.fz_batch_search_multi.argtypes = [vp, vp, u32, u8p, u64p, u32, u32, ci, mpp, ctypes.POINTER(ctypes.POINTER(u32)),
+                                                ctypes.POINTER(u64p)]
         L.fz_debug_batch_segment.restype = ci
         L.fz_debug_batch_segment.argtypes = [u64p, u64, u64, u64p, u64p, u64p]
         L.fz_subs_ngrams_best.restype = ci
@@ -623,6 +628,39 @@ class Engine(object):
             ctypes.memmove(seq_of.ctypes.data, sptr, 4 * n)
         self._lib.fz_free(sptr)
         return OwnedRows(self._lib, ptr, n), seq_of
+
+    def _batch_multi_call(self, batch, mode, patterns, k, reduced):
+        """-> (rows pointer, seq_of array, per-pattern row offsets) of one fz_batch_search_multi call; the caller owns the pointer."""
+        import numpy as np
+        blob, offs = pack_patterns(patterns)
+        ptr = ctypes.POINTER(FzMatch)()
+        sptr = ctypes.POINTER(ctypes.c_uint32)()
+        optr = ctypes.POINTER(ctypes.c_uint64)()
+        with self._lock:
+            _check(self._lib.fz_batch_search_multi(self._h, batch._h, mode, blob, offs, len(patterns), k, 1 if reduced else 0,
+                                                   ctypes.byref(ptr), ctypes.byref(sptr), ctypes.byref(optr)))
+        bounds = optr[:len(patterns) + 1]
+        self._lib.fz_free(optr)
+        seq_of = np.empty(bounds[-1], dtype=np.uint32)
+        if bounds[-1]:
+            ctypes.memmove(seq_of.ctypes.data, sptr, 4 * bounds[-1])
+        self._lib.fz_free(sptr)
+        return ptr, seq_of, bounds
+
+    def batch_search_multi(self, batch, mode, patterns, k, reduced=False):
+        """[batch_search(batch, mode, p, k, reduced) for p in patterns] in as few passes over the batch as the patterns
+        allow (fz_batch_search_multi): a list of (rows, seq_of) per pattern."""
+        patterns = list(patterns)
+        ptr, seq_of, bounds = self._batch_multi_call(batch, mode, patterns, k, reduced)
+        rows = _take_matches_array(self._lib, ptr, bounds[-1])
+        return [(rows[bounds[i]:bounds[i + 1]], seq_of[bounds[i]:bounds[i + 1]]) for i in range(len(patterns))]
+
+    def batch_multi_rows_call(self, batch, mode, patterns, k, reduced=True):
+        """The same as (OwnedRows of all patterns' rows, seq_of array, row offsets per pattern), for callers that build Match
+        objects in C straight from the result buffer: P x S lists are not a form for millions of reads."""
+        patterns = list(patterns)
+        ptr, seq_of, bounds = self._batch_multi_call(batch, mode, patterns, k, reduced)
+        return OwnedRows(self._lib, ptr, bounds[-1]), seq_of, bounds
 
     def upload_shard(self, data, buf_global_off, own_lo, own_hi, global_n):
         addr, n, keep = _buffer_address(data)

@@ -1258,3 +1258,42 @@ FZ_HD bool fz_mp_verify_subs(const Win &t, uint32_t sh, const uint32_t *p4, uint
     rec.l = s; rec.r = m - s - L; rec.dist = nd; rec.aux = 0;
     return valid && nd <= k;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Multi-pattern search over a batch (fz_batch_search_multi; fz_kernels.h: fz_mp_batch_verify_kernel /
+// fz_mp_batch_verify_subs_kernel).  The filter streams the packed bytes as one sequence and may report n-grams that straddle
+// a seam; a candidate is accepted inside ITS sequence sg = fz_segment_ragged(idx) only — the block's hit range
+// (fz_block_range) against [sg.sa, sg.se) as fz_hit_in_range has it, ownership, residency — and its window is
+//     Levenshtein     [max(idx - s - k, sg.sa), min(idx - s + m + k, sg.se))   clipped to the buffer,
+//     substitutions   [idx - s, idx - s + m), whole, inside the sequence by the range test.
+// A sequence shorter than the n-gram, the pattern or the window (or an empty one, which holds no position) needs no case of
+// its own: the range test rejects its candidates.
+struct FzMpRagCand { uint64_t wlo, whi; };       // the bytes the candidate's verification may read (a rejected one: none)
+
+FZ_HD bool fz_mp_rag_accept(uint32_t mode, const FzGeom &g, const FzSeg &sg, uint32_t m, uint32_t k, uint32_t L, uint32_t s,
+                            uint64_t idx, FzMpRagCand &c) {
+    c.wlo = c.whi = g.buf_off;
+    uint32_t lo_rel, hi_sub;
+    fz_block_range(mode, m, k, L, s, lo_rel, hi_sub);
+    if (!sg.ok || idx < sg.sa + lo_rel) return false;
+    if (sg.se < hi_sub || idx + L > sg.se - hi_sub) return false;
+    if (idx < g.own_lo || idx >= g.own_hi) return false;
+    const uint64_t data_end = g.buf_off + g.buf_len;
+    if (mode == FZ_MODE_SUBS) {                            // lo_rel = s, hi_sub = m - s - L: the window's two ends
+        if (idx - lo_rel < g.buf_off || idx + L + hi_sub > data_end) return false;
+        c.wlo = idx - s;
+        c.whi = c.wlo + m;
+        return true;
+    }
+    if (idx < g.buf_off || idx + L > data_end) return false;
+    const uint64_t reach = (uint64_t)s + k;
+    uint64_t wlo = idx > reach ? idx - reach : 0ull;
+    if (wlo < sg.sa) wlo = sg.sa;
+    if (wlo < g.buf_off) wlo = g.buf_off;
+    uint64_t whi = idx + m + k - s;                        // (idx + k >= sa + s: no wrap)
+    if (whi > sg.se) whi = sg.se;
+    if (whi > data_end) whi = data_end;
+    c.wlo = wlo;
+    c.whi = whi;
+    return true;
+}

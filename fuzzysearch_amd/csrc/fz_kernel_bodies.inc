@@ -1,6 +1,6 @@
 // fz_kernel_bodies.inc — the statement lists of the kernels that exist twice: for the unsegmented / strided geometries
-// (fz_scan_kernel, fz_verify_kernel, fz_verify_wf_kernel, fz_verify_big_kernel) and for ragged segments, a batch of
-// sequences packed back to back (fz_batch_*_kernel; fz_device.h).  Included by fz_kernels.h inside each kernel, with
+// (fz_scan_kernel, fz_verify_kernel, fz_verify_wf_kernel, fz_verify_big_kernel, fz_mp_verify_kernel, fz_mp_verify_subs_kernel)
+// and for ragged segments, a batch of sequences packed back to back (fz_batch_*_kernel, fz_mp_batch_*_kernel; fz_device.h).  Included by fz_kernels.h inside each kernel, with
 // FZ_KERNEL_BODY naming the section and `constexpr bool RAG` (and the kernel's template parameters) in scope: one text,
 // two kernels — a shared inline function instead moved the register allocation of the existing instances.
 #if FZ_KERNEL_BODY == 1      // ---- fz_scan_kernel / fz_batch_scan_kernel
@@ -490,6 +490,205 @@
         }
     }
     fz_finish_launch(a, counters, &flag);
+#elif FZ_KERNEL_BODY == 5    // ---- fz_mp_verify_kernel / fz_mp_batch_verify_kernel
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    uint32_t *tab = reinterpret_cast<uint32_t *>(smem);
+    for (uint32_t i = threadIdx.x; i < FZ_MP_VERIFY_WORDS; i += FZ_FILTER_THREADS) tab[i] = desc[FZ_MP_DESC_ENT + i];
+    __syncthreads();
+    const uint32_t *ent = tab;
+    const uint32_t *pm = tab + (FZ_MP_DESC_M - FZ_MP_DESC_ENT);
+    const uint8_t *pats = reinterpret_cast<const uint8_t *>(tab + (FZ_MP_DESC_PAT - FZ_MP_DESC_ENT));
+    const uint32_t lane = fz_lane();
+    uint8_t *wbytes = smem + FZ_MP_VERIFY_WORDS * 4u + (threadIdx.x >> 6) * fz_mp_verify_wave_bytes(a.win_dwords);
+    uint32_t *win = reinterpret_cast<uint32_t *>(wbytes);
+    uint16_t *ring = reinterpret_cast<uint16_t *>(wbytes + a.win_dwords * 256u);
+    const uint64_t waves = (uint64_t)gridDim.x * FZ_WAVES_PER_BLOCK;
+    const uint64_t wave = (uint64_t)blockIdx.x * FZ_WAVES_PER_BLOCK + (threadIdx.x >> 6);
+    const uint64_t n = a.geom.n;
+    const uint64_t data_end = a.geom.buf_off + a.geom.buf_len;
+    uint32_t confirmed = 0;
+    for (uint32_t l = 0; l < FZ_MP_LISTS; ++l) {
+        unsigned long long nh = counters[FZ_MP_CTR_LIST(l)];
+        if (nh > a.hit_cap) nh = a.hit_cap;
+        const uint64_t *lh = hits + (uint64_t)l * a.hit_cap;
+        // (the lists start at different waves: a short list keeps other waves busy than its neighbour's)
+        for (uint64_t q0 = ((wave + 251u * l) % waves) * 64u; q0 < nh; q0 += waves * 64u) {
+            const uint64_t q = q0 + lane;
+            const bool have = q < nh;
+            const uint64_t hit = have ? lh[q] : 0ull;
+            const uint32_t e = ent[fz_hit_block(hit) & (FZ_MP_MAX_BLOCKS - 1u)];
+            const uint32_t pid = e & 0xffu, g = (e >> 8) & 0xffu, s = e >> 16;
+            const uint32_t m = pm[pid & (FZ_MP_MAX_PATS - 1u)];
+            const uint8_t *p = pats + (pid & (FZ_MP_MAX_PATS - 1u)) * FZ_MP_MAX_M;
+            const uint64_t idx = fz_hit_index(hit);
+            bool valid;
+            // the window staged, and the sequence the candidate is verified in.  (Initialised: left undefined until the branch
+            // below, they moved the SGPR allocation of the unsegmented kernel.)
+            uint64_t wlo = 0, whi = 0, wbase = 0, sa = 0, se = 0;
+            if constexpr (RAG) {
+                // the candidate's own sequence: one lookup per lane (a binary search bounded by the tile index, ~7 dependent
+                // loads for 150-byte reads), before anything is staged; then the block's range, ownership and the window's
+                // clamps inside [sg.sa, sg.se) (fz_mp_rag_accept).  An n-gram across a seam is rejected by the range test.
+                valid = have && fz_hit_block(hit) < a.nent && m != 0u;
+                FzSeg sg;
+                sg.sa = sg.se = 0; sg.j = 0; sg.ok = 0;
+                if (valid) sg = fz_segment_ragged(fz_ragged(a.geom), n, idx);
+                FzMpRagCand c;
+                valid = valid && fz_mp_rag_accept(FZ_MODE_LEV, a.geom, sg, m, a.k, a.L, s, idx, c);
+                if (!__ballot(valid)) continue;
+                wlo = c.wlo; whi = c.whi; sa = sg.sa; se = sg.se;
+                wbase = a.geom.buf_off + ((wlo - a.geom.buf_off) & ~(uint64_t)3);
+            } else {
+                // acceptance range of the block (levenshtein_ngram.py:171-176) in the whole sequence [0, n), and ownership
+                uint32_t lo_rel, hi_sub;
+                fz_block_range(FZ_MODE_LEV, m, a.k, a.L, s, lo_rel, hi_sub);
+                valid = have && fz_hit_block(hit) < a.nent && m != 0u && idx >= lo_rel && n >= hi_sub && idx + a.L <= n - hi_sub &&
+                        idx >= a.geom.own_lo && idx < a.geom.own_hi && idx >= a.geom.buf_off && idx + a.L <= data_end;
+                if (!__ballot(valid)) continue;
+                // the window [max(0, idx - s - k), min(n, idx - s + m + k)) clipped to the buffer, dword-aligned, into LDS
+                const uint64_t reach = (uint64_t)s + a.k;
+                wlo = idx > reach ? idx - reach : 0ull;
+                if (wlo < a.geom.buf_off) wlo = a.geom.buf_off;
+                wbase = a.geom.buf_off + ((wlo - a.geom.buf_off) & ~(uint64_t)3);
+                whi = idx - s + m + a.k;
+                if (whi > data_end) whi = data_end;
+                if (whi > n) whi = n;
+                sa = 0ull; se = n;
+            }
+            uint32_t nd = valid ? (uint32_t)((whi - wbase + 3) >> 2) : 0u;
+            if (nd > a.win_dwords) nd = a.win_dwords;
+            const int64_t lbase = (int64_t)(wbase - a.geom.buf_off);
+            for (uint32_t d0 = 0; d0 < a.win_dwords; d0 += 8) {
+                uint32_t x[8];
+#pragma unroll
+                for (uint32_t j = 0; j < 8; ++j)
+                    x[j] = (d0 + j < nd) ? *reinterpret_cast<const uint32_t *>(buf + lbase + (int64_t)(d0 + j) * 4) : 0u;
+#pragma unroll
+                for (uint32_t j = 0; j < 8; ++j)
+                    if (d0 + j < nd) win[(d0 + j) * 64u + lane] = x[j];
+            }
+            fz_wave_lds_sync();
+            const FzLdsWindow t{reinterpret_cast<const uint8_t *>(win + lane), wbase, 256u};
+            if (valid) {
+                const uint8_t *ng = p + s;
+                for (uint32_t b = 0; b < a.L; ++b)
+                    if (ng[b] != t.at(idx + b)) { valid = false; break; }
+            }
+            confirmed += (uint32_t)__popcll(__ballot(valid));
+            FzRec rec;
+            bool ok = false;
+            if (valid) {
+                FzLdsScores sc{ring + lane, 64u};
+                if constexpr (RAG) ok = fz_verify_lev<FZ_REG_BAND_MAX>(sc, t, sa, se, p, m, a.k, a.L, s, idx, rec);
+                else ok = fz_verify_lev<FZ_REG_BAND_MAX>(sc, t, 0ull, n, p, m, a.k, a.L, s, idx, rec);
+            }
+            const unsigned long long mask = __ballot(ok);
+            if (mask) {
+                unsigned long long base = 0;
+                if (lane == 0) base = atomicAdd(&counters[FZ_MP_CTR_RECS], (unsigned long long)__popcll(mask));
+                base = fz_bcast64(base);
+                if (ok) {
+                    rec.key = fz_hit_pack(g, idx);
+                    rec.aux = pid;
+                    const unsigned long long slot = base + fz_rank(mask);
+                    if (slot < a.rec_cap) recs[slot] = rec;
+                }
+            }
+            fz_wave_lds_sync();
+        }
+    }
+    if (lane == 0 && confirmed) atomicAdd(&counters[8u + (blockIdx.x & 63u)], (unsigned long long)confirmed);
+#elif FZ_KERNEL_BODY == 6    // ---- fz_mp_verify_subs_kernel / fz_mp_batch_verify_subs_kernel
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    uint32_t *tab = reinterpret_cast<uint32_t *>(smem);
+    constexpr uint32_t kPat = FZ_MP_DESC_PAT - FZ_MP_DESC_ENT, kRow = FZ_MP_MAX_M / 4u;
+    static_assert(FZ_MP_MAX_PATS == 64u, "the transposed pattern table has one column per pattern");
+    for (uint32_t i = threadIdx.x; i < FZ_MP_VERIFY_WORDS; i += FZ_FILTER_THREADS) {
+        const uint32_t v = desc[FZ_MP_DESC_ENT + i];
+        if (i < kPat) tab[i] = v;
+        else tab[kPat + ((i - kPat) % kRow) * FZ_MP_MAX_PATS + (i - kPat) / kRow] = v;
+    }
+    __syncthreads();
+    const uint32_t *ent = tab;
+    const uint32_t *pm = tab + (FZ_MP_DESC_M - FZ_MP_DESC_ENT);
+    const uint32_t *pat4 = tab + kPat;
+    const uint32_t lane = fz_lane();
+    uint32_t *win = reinterpret_cast<uint32_t *>(smem + FZ_MP_VERIFY_WORDS * 4u) + (threadIdx.x >> 6) * a.win_dwords * 64u;
+    const uint32_t m_max = (a.win_dwords - 1u) * 4u;       // (the longest pattern rounded up to dwords)
+    const uint64_t waves = (uint64_t)gridDim.x * FZ_WAVES_PER_BLOCK;
+    const uint64_t wave = (uint64_t)blockIdx.x * FZ_WAVES_PER_BLOCK + (threadIdx.x >> 6);
+    const uint64_t n = a.geom.n;
+    const uint64_t data_end = a.geom.buf_off + a.geom.buf_len;
+    uint32_t confirmed = 0;
+    for (uint32_t l = 0; l < FZ_MP_LISTS; ++l) {
+        unsigned long long nh = counters[FZ_MP_CTR_LIST(l)];
+        if (nh > a.hit_cap) nh = a.hit_cap;
+        const uint64_t *lh = hits + (uint64_t)l * a.hit_cap;
+        for (uint64_t q0 = ((wave + 251u * l) % waves) * 64u; q0 < nh; q0 += waves * 64u) {
+            const uint64_t q = q0 + lane;
+            const bool have = q < nh;
+            const uint64_t hit = have ? lh[q] : 0ull;
+            const uint32_t e = ent[fz_hit_block(hit) & (FZ_MP_MAX_BLOCKS - 1u)];
+            const uint32_t pid = e & (FZ_MP_MAX_PATS - 1u), g = (e >> 8) & 0xffu, s = e >> 16;
+            const uint32_t m = pm[pid];
+            const uint64_t idx = fz_hit_index(hit);
+            bool valid;
+            if constexpr (RAG) {
+                // the candidate's own sequence (one lookup per lane, before anything is staged), then the window
+                // [idx - s, idx - s + m) inside it, ownership, the whole window resident (fz_mp_rag_accept)
+                valid = have && fz_hit_block(hit) < a.nent && m != 0u && m <= m_max && s + a.L <= m;
+                FzSeg sg;
+                sg.sa = sg.se = 0; sg.j = 0; sg.ok = 0;
+                if (valid) sg = fz_segment_ragged(fz_ragged(a.geom), n, idx);
+                FzMpRagCand c;
+                valid = valid && fz_mp_rag_accept(FZ_MODE_SUBS, a.geom, sg, m, a.k, a.L, s, idx, c);
+            } else {
+                // the block's hit range (template.h:97-101): s <= idx and idx - s + m <= n; ownership; the whole window resident
+                uint32_t lo_rel, hi_sub;
+                fz_block_range(FZ_MODE_SUBS, m, a.k, a.L, s, lo_rel, hi_sub);
+                valid = have && fz_hit_block(hit) < a.nent && m != 0u && m <= m_max && s + a.L <= m &&
+                        idx >= lo_rel && n >= hi_sub && idx + a.L <= n - hi_sub &&
+                        idx >= a.geom.own_lo && idx < a.geom.own_hi && idx - lo_rel >= a.geom.buf_off && idx + a.L + hi_sub <= data_end;
+            }
+            if (!__ballot(valid)) continue;
+            const uint64_t i0 = valid ? idx - s : a.geom.buf_off;
+            const uint64_t wbase = a.geom.buf_off + ((i0 - a.geom.buf_off) & ~(uint64_t)3);
+            const uint32_t sh = (uint32_t)(i0 - wbase);
+            uint32_t nd = valid ? (uint32_t)((i0 + m - wbase + 3) >> 2) : 0u;      // <= (m + 6) / 4 <= win_dwords
+            if (nd > a.win_dwords) nd = a.win_dwords;
+            const int64_t lbase = (int64_t)(wbase - a.geom.buf_off);
+            for (uint32_t d0 = 0; d0 < a.win_dwords; d0 += 8) {
+                uint32_t x[8];
+#pragma unroll
+                for (uint32_t j = 0; j < 8; ++j)
+                    x[j] = (d0 + j < nd) ? *reinterpret_cast<const uint32_t *>(buf + lbase + (int64_t)(d0 + j) * 4) : 0u;
+#pragma unroll
+                for (uint32_t j = 0; j < 8; ++j)
+                    if (d0 + j < a.win_dwords) win[(d0 + j) * 64u + lane] = x[j];
+            }
+            fz_wave_lds_sync();
+            const FzLdsColumn t{win + lane};
+            const uint32_t *p4 = pat4 + pid;
+            valid = valid && fz_mp_block_equal(t, sh, p4, FZ_MP_MAX_PATS, a.L, valid ? s : 0u);
+            confirmed += (uint32_t)__popcll(__ballot(valid));
+            FzRec rec;
+            const bool ok = fz_mp_verify_subs(t, sh, p4, FZ_MP_MAX_PATS, m, m_max, a.k, a.L, s, valid, rec);
+            const unsigned long long mask = __ballot(ok);
+            if (mask) {
+                unsigned long long base = 0;
+                if (lane == 0) base = atomicAdd(&counters[FZ_MP_CTR_RECS], (unsigned long long)__popcll(mask));
+                base = fz_bcast64(base);
+                if (ok) {
+                    rec.key = fz_hit_pack(g, idx);
+                    rec.aux = pid;
+                    const unsigned long long slot = base + fz_rank(mask);
+                    if (slot < a.rec_cap) recs[slot] = rec;
+                }
+            }
+            fz_wave_lds_sync();
+        }
+    }
+    if (lane == 0 && confirmed) atomicAdd(&counters[8u + (blockIdx.x & 63u)], (unsigned long long)confirmed);
 #else
 #error "FZ_KERNEL_BODY names no section"
 #endif

@@ -2196,92 +2196,21 @@ __global__ __launch_bounds__(FZ_FILTER_THREADS) void fz_mp_filter_kernel(const u
 __global__ __launch_bounds__(FZ_FILTER_THREADS) void fz_mp_verify_kernel(const uint8_t *__restrict__ buf, const FzMpArgs a,
                                                                          const uint32_t *__restrict__ desc, const uint64_t *__restrict__ hits,
                                                                          FzRec *__restrict__ recs, unsigned long long *__restrict__ counters) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    uint32_t *tab = reinterpret_cast<uint32_t *>(smem);
-    for (uint32_t i = threadIdx.x; i < FZ_MP_VERIFY_WORDS; i += FZ_FILTER_THREADS) tab[i] = desc[FZ_MP_DESC_ENT + i];
-    __syncthreads();
-    const uint32_t *ent = tab;
-    const uint32_t *pm = tab + (FZ_MP_DESC_M - FZ_MP_DESC_ENT);
-    const uint8_t *pats = reinterpret_cast<const uint8_t *>(tab + (FZ_MP_DESC_PAT - FZ_MP_DESC_ENT));
-    const uint32_t lane = fz_lane();
-    uint8_t *wbytes = smem + FZ_MP_VERIFY_WORDS * 4u + (threadIdx.x >> 6) * fz_mp_verify_wave_bytes(a.win_dwords);
-    uint32_t *win = reinterpret_cast<uint32_t *>(wbytes);
-    uint16_t *ring = reinterpret_cast<uint16_t *>(wbytes + a.win_dwords * 256u);
-    const uint64_t waves = (uint64_t)gridDim.x * FZ_WAVES_PER_BLOCK;
-    const uint64_t wave = (uint64_t)blockIdx.x * FZ_WAVES_PER_BLOCK + (threadIdx.x >> 6);
-    const uint64_t n = a.geom.n;
-    const uint64_t data_end = a.geom.buf_off + a.geom.buf_len;
-    uint32_t confirmed = 0;
-    for (uint32_t l = 0; l < FZ_MP_LISTS; ++l) {
-        unsigned long long nh = counters[FZ_MP_CTR_LIST(l)];
-        if (nh > a.hit_cap) nh = a.hit_cap;
-        const uint64_t *lh = hits + (uint64_t)l * a.hit_cap;
-        // (the lists start at different waves: a short list keeps other waves busy than its neighbour's)
-        for (uint64_t q0 = ((wave + 251u * l) % waves) * 64u; q0 < nh; q0 += waves * 64u) {
-            const uint64_t q = q0 + lane;
-            const bool have = q < nh;
-            const uint64_t hit = have ? lh[q] : 0ull;
-            const uint32_t e = ent[fz_hit_block(hit) & (FZ_MP_MAX_BLOCKS - 1u)];
-            const uint32_t pid = e & 0xffu, g = (e >> 8) & 0xffu, s = e >> 16;
-            const uint32_t m = pm[pid & (FZ_MP_MAX_PATS - 1u)];
-            const uint8_t *p = pats + (pid & (FZ_MP_MAX_PATS - 1u)) * FZ_MP_MAX_M;
-            const uint64_t idx = fz_hit_index(hit);
-            // acceptance range of the block (levenshtein_ngram.py:171-176) in the whole sequence [0, n), and ownership
-            uint32_t lo_rel, hi_sub;
-            fz_block_range(FZ_MODE_LEV, m, a.k, a.L, s, lo_rel, hi_sub);
-            bool valid = have && fz_hit_block(hit) < a.nent && m != 0u && idx >= lo_rel && n >= hi_sub && idx + a.L <= n - hi_sub &&
-                         idx >= a.geom.own_lo && idx < a.geom.own_hi && idx >= a.geom.buf_off && idx + a.L <= data_end;
-            if (!__ballot(valid)) continue;
-            // the window [max(0, idx - s - k), min(n, idx - s + m + k)) clipped to the buffer, dword-aligned, into LDS
-            const uint64_t reach = (uint64_t)s + a.k;
-            uint64_t wlo = idx > reach ? idx - reach : 0ull;
-            if (wlo < a.geom.buf_off) wlo = a.geom.buf_off;
-            const uint64_t wbase = a.geom.buf_off + ((wlo - a.geom.buf_off) & ~(uint64_t)3);
-            uint64_t whi = idx - s + m + a.k;
-            if (whi > data_end) whi = data_end;
-            if (whi > n) whi = n;
-            uint32_t nd = valid ? (uint32_t)((whi - wbase + 3) >> 2) : 0u;
-            if (nd > a.win_dwords) nd = a.win_dwords;
-            const int64_t lbase = (int64_t)(wbase - a.geom.buf_off);
-            for (uint32_t d0 = 0; d0 < a.win_dwords; d0 += 8) {
-                uint32_t x[8];
-#pragma unroll
-                for (uint32_t j = 0; j < 8; ++j)
-                    x[j] = (d0 + j < nd) ? *reinterpret_cast<const uint32_t *>(buf + lbase + (int64_t)(d0 + j) * 4) : 0u;
-#pragma unroll
-                for (uint32_t j = 0; j < 8; ++j)
-                    if (d0 + j < nd) win[(d0 + j) * 64u + lane] = x[j];
-            }
-            fz_wave_lds_sync();
-            const FzLdsWindow t{reinterpret_cast<const uint8_t *>(win + lane), wbase, 256u};
-            if (valid) {
-                const uint8_t *ng = p + s;
-                for (uint32_t b = 0; b < a.L; ++b)
-                    if (ng[b] != t.at(idx + b)) { valid = false; break; }
-            }
-            confirmed += (uint32_t)__popcll(__ballot(valid));
-            FzRec rec;
-            bool ok = false;
-            if (valid) {
-                FzLdsScores sc{ring + lane, 64u};
-                ok = fz_verify_lev<FZ_REG_BAND_MAX>(sc, t, 0ull, n, p, m, a.k, a.L, s, idx, rec);
-            }
-            const unsigned long long mask = __ballot(ok);
-            if (mask) {
-                unsigned long long base = 0;
-                if (lane == 0) base = atomicAdd(&counters[FZ_MP_CTR_RECS], (unsigned long long)__popcll(mask));
-                base = fz_bcast64(base);
-                if (ok) {
-                    rec.key = fz_hit_pack(g, idx);
-                    rec.aux = pid;
-                    const unsigned long long slot = base + fz_rank(mask);
-                    if (slot < a.rec_cap) recs[slot] = rec;
-                }
-            }
-            fz_wave_lds_sync();
-        }
-    }
-    if (lane == 0 && confirmed) atomicAdd(&counters[8u + (blockIdx.x & 63u)], (unsigned long long)confirmed);
+    constexpr bool RAG = false;
+#define FZ_KERNEL_BODY 5
+#include "fz_kernel_bodies.inc"
+#undef FZ_KERNEL_BODY
+}
+// The same text over a batch (fz_batch_search_multi): the candidate's own sequence — one fz_segment_ragged lookup per lane,
+// after the entry checks and before anything is staged — takes the place of [0, n) in the block's range, the window's clamps
+// and fz_verify_lev (fz_device.h: fz_mp_rag_accept).  A kernel of its own, so fz_mp_verify_kernel's code does not move.
+__global__ __launch_bounds__(FZ_FILTER_THREADS) void fz_mp_batch_verify_kernel(const uint8_t *__restrict__ buf, const FzMpArgs a,
+                                                                               const uint32_t *__restrict__ desc, const uint64_t *__restrict__ hits,
+                                                                               FzRec *__restrict__ recs, unsigned long long *__restrict__ counters) {
+    constexpr bool RAG = true;
+#define FZ_KERNEL_BODY 5
+#include "fz_kernel_bodies.inc"
+#undef FZ_KERNEL_BODY
 }
 
 // fz_mp_verify_kernel's counterpart for substitutions-only groups (fz_subs_ngrams_multi): same launch shape, hit lists,
@@ -2309,82 +2238,19 @@ __host__ __device__ inline uint32_t fz_mp_verify_subs_lds(uint32_t win_dwords) {
 __global__ __launch_bounds__(FZ_FILTER_THREADS) void fz_mp_verify_subs_kernel(const uint8_t *__restrict__ buf, const FzMpArgs a,
                                                                               const uint32_t *__restrict__ desc, const uint64_t *__restrict__ hits,
                                                                               FzRec *__restrict__ recs, unsigned long long *__restrict__ counters) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    uint32_t *tab = reinterpret_cast<uint32_t *>(smem);
-    constexpr uint32_t kPat = FZ_MP_DESC_PAT - FZ_MP_DESC_ENT, kRow = FZ_MP_MAX_M / 4u;
-    static_assert(FZ_MP_MAX_PATS == 64u, "the transposed pattern table has one column per pattern");
-    for (uint32_t i = threadIdx.x; i < FZ_MP_VERIFY_WORDS; i += FZ_FILTER_THREADS) {
-        const uint32_t v = desc[FZ_MP_DESC_ENT + i];
-        if (i < kPat) tab[i] = v;
-        else tab[kPat + ((i - kPat) % kRow) * FZ_MP_MAX_PATS + (i - kPat) / kRow] = v;
-    }
-    __syncthreads();
-    const uint32_t *ent = tab;
-    const uint32_t *pm = tab + (FZ_MP_DESC_M - FZ_MP_DESC_ENT);
-    const uint32_t *pat4 = tab + kPat;
-    const uint32_t lane = fz_lane();
-    uint32_t *win = reinterpret_cast<uint32_t *>(smem + FZ_MP_VERIFY_WORDS * 4u) + (threadIdx.x >> 6) * a.win_dwords * 64u;
-    const uint32_t m_max = (a.win_dwords - 1u) * 4u;       // (the longest pattern rounded up to dwords)
-    const uint64_t waves = (uint64_t)gridDim.x * FZ_WAVES_PER_BLOCK;
-    const uint64_t wave = (uint64_t)blockIdx.x * FZ_WAVES_PER_BLOCK + (threadIdx.x >> 6);
-    const uint64_t n = a.geom.n;
-    const uint64_t data_end = a.geom.buf_off + a.geom.buf_len;
-    uint32_t confirmed = 0;
-    for (uint32_t l = 0; l < FZ_MP_LISTS; ++l) {
-        unsigned long long nh = counters[FZ_MP_CTR_LIST(l)];
-        if (nh > a.hit_cap) nh = a.hit_cap;
-        const uint64_t *lh = hits + (uint64_t)l * a.hit_cap;
-        for (uint64_t q0 = ((wave + 251u * l) % waves) * 64u; q0 < nh; q0 += waves * 64u) {
-            const uint64_t q = q0 + lane;
-            const bool have = q < nh;
-            const uint64_t hit = have ? lh[q] : 0ull;
-            const uint32_t e = ent[fz_hit_block(hit) & (FZ_MP_MAX_BLOCKS - 1u)];
-            const uint32_t pid = e & (FZ_MP_MAX_PATS - 1u), g = (e >> 8) & 0xffu, s = e >> 16;
-            const uint32_t m = pm[pid];
-            const uint64_t idx = fz_hit_index(hit);
-            // the block's hit range (template.h:97-101): s <= idx and idx - s + m <= n; ownership; the whole window resident
-            uint32_t lo_rel, hi_sub;
-            fz_block_range(FZ_MODE_SUBS, m, a.k, a.L, s, lo_rel, hi_sub);
-            bool valid = have && fz_hit_block(hit) < a.nent && m != 0u && m <= m_max && s + a.L <= m &&
-                         idx >= lo_rel && n >= hi_sub && idx + a.L <= n - hi_sub &&
-                         idx >= a.geom.own_lo && idx < a.geom.own_hi && idx - lo_rel >= a.geom.buf_off && idx + a.L + hi_sub <= data_end;
-            if (!__ballot(valid)) continue;
-            const uint64_t i0 = valid ? idx - s : a.geom.buf_off;
-            const uint64_t wbase = a.geom.buf_off + ((i0 - a.geom.buf_off) & ~(uint64_t)3);
-            const uint32_t sh = (uint32_t)(i0 - wbase);
-            uint32_t nd = valid ? (uint32_t)((i0 + m - wbase + 3) >> 2) : 0u;      // <= (m + 6) / 4 <= win_dwords
-            if (nd > a.win_dwords) nd = a.win_dwords;
-            const int64_t lbase = (int64_t)(wbase - a.geom.buf_off);
-            for (uint32_t d0 = 0; d0 < a.win_dwords; d0 += 8) {
-                uint32_t x[8];
-#pragma unroll
-                for (uint32_t j = 0; j < 8; ++j)
-                    x[j] = (d0 + j < nd) ? *reinterpret_cast<const uint32_t *>(buf + lbase + (int64_t)(d0 + j) * 4) : 0u;
-#pragma unroll
-                for (uint32_t j = 0; j < 8; ++j)
-                    if (d0 + j < a.win_dwords) win[(d0 + j) * 64u + lane] = x[j];
-            }
-            fz_wave_lds_sync();
-            const FzLdsColumn t{win + lane};
-            const uint32_t *p4 = pat4 + pid;
-            valid = valid && fz_mp_block_equal(t, sh, p4, FZ_MP_MAX_PATS, a.L, valid ? s : 0u);
-            confirmed += (uint32_t)__popcll(__ballot(valid));
-            FzRec rec;
-            const bool ok = fz_mp_verify_subs(t, sh, p4, FZ_MP_MAX_PATS, m, m_max, a.k, a.L, s, valid, rec);
-            const unsigned long long mask = __ballot(ok);
-            if (mask) {
-                unsigned long long base = 0;
-                if (lane == 0) base = atomicAdd(&counters[FZ_MP_CTR_RECS], (unsigned long long)__popcll(mask));
-                base = fz_bcast64(base);
-                if (ok) {
-                    rec.key = fz_hit_pack(g, idx);
-                    rec.aux = pid;
-                    const unsigned long long slot = base + fz_rank(mask);
-                    if (slot < a.rec_cap) recs[slot] = rec;
-                }
-            }
-            fz_wave_lds_sync();
-        }
-    }
-    if (lane == 0 && confirmed) atomicAdd(&counters[8u + (blockIdx.x & 63u)], (unsigned long long)confirmed);
+    constexpr bool RAG = false;
+#define FZ_KERNEL_BODY 6
+#include "fz_kernel_bodies.inc"
+#undef FZ_KERNEL_BODY
+}
+// ... and over a batch: the window [idx - s, idx - s + m) lies inside the candidate's own sequence (fz_mp_rag_accept).  The
+// dword-granular staging may bring up to 3 bytes of a neighbouring sequence or of the padding along; fz_mp_block_equal and
+// fz_mp_verify_subs mask them.
+__global__ __launch_bounds__(FZ_FILTER_THREADS) void fz_mp_batch_verify_subs_kernel(const uint8_t *__restrict__ buf, const FzMpArgs a,
+                                                                                    const uint32_t *__restrict__ desc, const uint64_t *__restrict__ hits,
+                                                                                    FzRec *__restrict__ recs, unsigned long long *__restrict__ counters) {
+    constexpr bool RAG = true;
+#define FZ_KERNEL_BODY 6
+#include "fz_kernel_bodies.inc"
+#undef FZ_KERNEL_BODY
 }

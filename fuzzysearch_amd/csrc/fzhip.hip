@@ -2865,7 +2865,7 @@ struct MpTotals { uint64_t bytes = 0, hits = 0, rows = 0; uint32_t launches = 0;
 // of the group's patterns), twice over and spread over the lists; a launch that overflows a list or the record buffer is
 // run again with what its counters ask for.
 static int mp_run_shard(fz_ctx *ctx, const Shard &sh, uint32_t mode, const uint32_t *desc, uint32_t nent, uint32_t k, uint32_t L, uint32_t max_m,
-                        uint32_t sigma, std::vector<FzRec> &recs, MpTotals &tot) {
+                        uint32_t sigma, std::vector<FzRec> &recs, MpTotals &tot, bool rag = false) {
     DevState &d = ctx->devs[sh.dev];
     const uint64_t ntiles = (sh.geom.buf_len + FZ_TILE_BYTES - 1) / FZ_TILE_BYTES;
     tot.bytes += sh.geom.buf_len;
@@ -2899,11 +2899,14 @@ static int mp_run_shard(fz_ctx *ctx, const Shard &sh, uint32_t mode, const uint3
                            reinterpret_cast<uint64_t *>(d.d_mp_hits), dctr);
         HIP_TRY(hipGetLastError());
         if (ctx->timing) HIP_TRY(hipEventRecord(d.ev[1], d.stream));
+        // (rag: the shard is a batch — the ragged instances look every candidate's sequence up in the geometry's tables)
         if (subs)
-            hipLaunchKernelGGL(fz_mp_verify_subs_kernel, dim3((uint32_t)d.n_cus * 4), dim3(FZ_FILTER_THREADS), fz_mp_verify_subs_lds(a.win_dwords), d.stream,
+            hipLaunchKernelGGL(rag ? fz_mp_batch_verify_subs_kernel : fz_mp_verify_subs_kernel, dim3((uint32_t)d.n_cus * 4), dim3(FZ_FILTER_THREADS),
+                               fz_mp_verify_subs_lds(a.win_dwords), d.stream,
                                sh.d_buf, a, ddesc, reinterpret_cast<const uint64_t *>(d.d_mp_hits), reinterpret_cast<FzRec *>(d.d_mp_recs), dctr);
         else
-            hipLaunchKernelGGL(fz_mp_verify_kernel, dim3((uint32_t)d.n_cus * 4), dim3(FZ_FILTER_THREADS), fz_mp_verify_lds(a.win_dwords), d.stream,
+            hipLaunchKernelGGL(rag ? fz_mp_batch_verify_kernel : fz_mp_verify_kernel, dim3((uint32_t)d.n_cus * 4), dim3(FZ_FILTER_THREADS),
+                               fz_mp_verify_lds(a.win_dwords), d.stream,
                                sh.d_buf, a, ddesc, reinterpret_cast<const uint64_t *>(d.d_mp_hits), reinterpret_cast<FzRec *>(d.d_mp_recs), dctr);
         HIP_TRY(hipGetLastError());
         if (ctx->timing) HIP_TRY(hipEventRecord(d.ev[2], d.stream));
@@ -2959,7 +2962,7 @@ static int mp_run_group(fz_ctx *ctx, fz_seq *seq, uint32_t mode, const uint8_t *
     if (nent == 0 || nent != g.blocks) return fail(FZ_EDEVICE, "internal: the group's block table does not match its plan");
     std::vector<FzRec> recs;
     for (const Shard &sh : seq->shards) {
-        int rc = mp_run_shard(ctx, sh, mode, desc.data(), nent, k, g.L, max_m, std::max(1u, sigma), recs, tot);
+        int rc = mp_run_shard(ctx, sh, mode, desc.data(), nent, k, g.L, max_m, std::max(1u, sigma), recs, tot, seq->is_batch);
         if (rc) return rc;
     }
     // per pattern: its records (aux = the pattern's number in the group) in the reference's order — block ascending, hit
@@ -3374,18 +3377,73 @@ int fz_subs_ngrams_any(fz_ctx *ctx, fz_seq *seq, const uint8_t *p, uint32_t m, u
     return subs_ngrams_impl(ctx, seq, p, m, k, nullptr, nullptr, found);
 }
 
-int fz_batch_search(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8_t *p, uint32_t m, uint32_t k,
-                    int reduced, fz_match **out, uint32_t **seq_of, uint64_t *n) {
-    if (!out || !seq_of || !n) return fail(FZ_EINVAL, "null argument");
-    *out = nullptr; *seq_of = nullptr; *n = 0;
+// validate() accepts a batch handle inside a batch call only.
+struct BatchScope {
+    fz_ctx *c;
+    explicit BatchScope(fz_ctx *c_) : c(c_) { c->batch_call = true; }
+    ~BatchScope() { c->batch_call = false; }
+};
+
+static int batch_single_device(fz_ctx *ctx, fz_seq *batch) {
+    if (ctx->devs.size() != 1 || ctx->snapshot || comm_multi_process(ctx) || (batch && batch->is_batch && batch->shards.size() != 1))
+        return fail(FZ_EUNSUPPORTED, "batches are searched by single-device, non-collective contexts");
+    return FZ_OK;
+}
+
+// Rows of the packed bytes in the in-memory order (block, index), global coordinates -> the batch's result: a row's
+// sequence = the sequence of its first byte (a match lies inside the sequence of its n-gram hit); rows are ordered the way
+// fz_stream_finish orders chunks: a stable sort by sequence of the in-memory order; local coordinates; `reduce`: every
+// sequence's slice through fz_consolidate (Levenshtein) or fz_group_best.
+static int batch_order(fz_seq *batch, uint32_t mode, bool reduce, const std::vector<fz_match> &rows, std::vector<fz_match> &fin,
+                       std::vector<uint32_t> &fin_seq) {
+    fin.clear();
+    fin_seq.clear();
+    const std::vector<uint64_t> &ends = batch->ends;
+    std::vector<std::pair<uint32_t, uint32_t>> order(rows.size());       // (sequence, row)
+    for (size_t i = 0; i < rows.size(); ++i) {
+        const size_t j = (size_t)(std::upper_bound(ends.begin(), ends.end(), (uint64_t)rows[i].start) - ends.begin());
+        if (j >= ends.size()) return fail(FZ_EDEVICE, "internal: a batch row outside every sequence");
+        order[i] = {(uint32_t)j, (uint32_t)i};
+    }
+    if (rows.size() >= (1ull << 32)) return fail(FZ_EUNSUPPORTED, "more than 2^32 - 1 rows in a batch search");
+    std::stable_sort(order.begin(), order.end(), [](const std::pair<uint32_t, uint32_t> &x, const std::pair<uint32_t, uint32_t> &y) { return x.first < y.first; });
+    fin.reserve(rows.size());
+    fin_seq.reserve(rows.size());
+    std::vector<fz_match> slice;
+    for (size_t a = 0; a < order.size();) {
+        size_t b = a;
+        const uint32_t j = order[a].first;
+        const int64_t base = (int64_t)(j ? ends[j - 1] : 0);
+        slice.clear();
+        for (; b < order.size() && order[b].first == j; ++b) {
+            fz_match r = rows[order[b].second];
+            r.start -= base; r.end -= base;
+            slice.push_back(r);
+        }
+        if (reduce) {
+            fz_match *ro = nullptr;
+            uint64_t rn = 0;
+            int rc = mode == FZ_MODE_LEV ? fz_consolidate(slice.data(), slice.size(), &ro, &rn) : fz_group_best(slice.data(), slice.size(), &ro, &rn);
+            if (rc) return rc;
+            fin.insert(fin.end(), ro, ro + rn);
+            fin_seq.insert(fin_seq.end(), rn, j);
+            release_out(ro);
+        } else {
+            fin.insert(fin.end(), slice.begin(), slice.end());
+            fin_seq.insert(fin_seq.end(), slice.size(), j);
+        }
+        a = b;
+    }
+    return FZ_OK;
+}
+
+// fz_batch_search without its result buffers: what fz_batch_search_multi runs for the patterns outside every group.
+static int batch_search_impl(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8_t *p, uint32_t m, uint32_t k, int reduced,
+                             std::vector<fz_match> &fin, std::vector<uint32_t> &fin_seq) {
     if (!ctx || !batch || batch->ctx != ctx) return fail(FZ_EINVAL, "bad ctx/seq handle");
     if (mode != FZ_MODE_EXACT && mode != FZ_MODE_LEV && mode != FZ_MODE_SUBS) return fail(FZ_EINVAL, "mode must be exact, Levenshtein or substitutions-only");
     if (mode == FZ_MODE_EXACT && k != 0) return fail(FZ_EINVAL, "an exact search has no budget");
-    struct Scope {                                         // validate() accepts a batch handle inside this call only
-        fz_ctx *c;
-        explicit Scope(fz_ctx *c_) : c(c_) { c->batch_call = true; }
-        ~Scope() { c->batch_call = false; }
-    } scope(ctx);
+    BatchScope scope(ctx);
     Search q;
     int rc;
     if (mode == FZ_MODE_LEV) rc = lev_plan(ctx, batch, p, m, k, q);
@@ -3400,8 +3458,8 @@ int fz_batch_search(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8_t *p,
         q.plan.abs_hi = batch->n;
     }
     if (rc) return rc;
-    if (ctx->devs.size() != 1 || ctx->snapshot || comm_multi_process(ctx) || batch->shards.size() != 1)
-        return fail(FZ_EUNSUPPORTED, "batches are searched by single-device, non-collective contexts");
+    rc = batch_single_device(ctx, batch);
+    if (rc) return rc;
     q.collective = false;
     // the rows of the packed bytes in the in-memory order (block, index), global coordinates
     std::vector<fz_match> rows;
@@ -3429,47 +3487,17 @@ int fz_batch_search(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8_t *p,
         }
     }
     ctx->stats.raw_matches = rows.size();
-    // a row's sequence = the sequence of its first byte (a match lies inside the sequence of its n-gram hit); rows are
-    // ordered the way fz_stream_finish orders chunks: a stable sort by sequence of the in-memory order
-    const std::vector<uint64_t> &ends = batch->ends;
-    std::vector<std::pair<uint32_t, uint32_t>> order(rows.size());       // (sequence, row)
-    for (size_t i = 0; i < rows.size(); ++i) {
-        const size_t j = (size_t)(std::upper_bound(ends.begin(), ends.end(), (uint64_t)rows[i].start) - ends.begin());
-        if (j >= ends.size()) return fail(FZ_EDEVICE, "internal: a batch row outside every sequence");
-        order[i] = {(uint32_t)j, (uint32_t)i};
-    }
-    if (rows.size() >= (1ull << 32)) return fail(FZ_EUNSUPPORTED, "more than 2^32 - 1 rows in a batch search");
-    std::stable_sort(order.begin(), order.end(), [](const std::pair<uint32_t, uint32_t> &x, const std::pair<uint32_t, uint32_t> &y) { return x.first < y.first; });
+    return batch_order(batch, mode, reduced != 0 && mode != FZ_MODE_EXACT, rows, fin, fin_seq);
+}
+
+int fz_batch_search(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8_t *p, uint32_t m, uint32_t k,
+                    int reduced, fz_match **out, uint32_t **seq_of, uint64_t *n) {
+    if (!out || !seq_of || !n) return fail(FZ_EINVAL, "null argument");
+    *out = nullptr; *seq_of = nullptr; *n = 0;
     std::vector<fz_match> fin;
     std::vector<uint32_t> fin_seq;
-    fin.reserve(rows.size());
-    fin_seq.reserve(rows.size());
-    std::vector<fz_match> slice;
-    const bool reduce = reduced != 0 && mode != FZ_MODE_EXACT;
-    for (size_t a = 0; a < order.size();) {
-        size_t b = a;
-        const uint32_t j = order[a].first;
-        const int64_t base = (int64_t)(j ? ends[j - 1] : 0);
-        slice.clear();
-        for (; b < order.size() && order[b].first == j; ++b) {
-            fz_match r = rows[order[b].second];
-            r.start -= base; r.end -= base;
-            slice.push_back(r);
-        }
-        if (reduce) {
-            fz_match *ro = nullptr;
-            uint64_t rn = 0;
-            rc = mode == FZ_MODE_LEV ? fz_consolidate(slice.data(), slice.size(), &ro, &rn) : fz_group_best(slice.data(), slice.size(), &ro, &rn);
-            if (rc) return rc;
-            fin.insert(fin.end(), ro, ro + rn);
-            fin_seq.insert(fin_seq.end(), rn, j);
-            release_out(ro);
-        } else {
-            fin.insert(fin.end(), slice.begin(), slice.end());
-            fin_seq.insert(fin_seq.end(), slice.size(), j);
-        }
-        a = b;
-    }
+    int rc = batch_search_impl(ctx, batch, mode, p, m, k, reduced, fin, fin_seq);
+    if (rc) return rc;
     void *mem = nullptr, *smem_ = nullptr;
     rc = alloc_out(fin.size(), sizeof(fz_match), &mem);
     if (rc) return rc;
@@ -3482,6 +3510,101 @@ int fz_batch_search(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8_t *p,
     *out = static_cast<fz_match *>(mem);
     *seq_of = static_cast<uint32_t *>(smem_);
     *n = fin.size();
+    return FZ_OK;
+}
+
+// Many patterns over a batch: the multi-pattern planner (mp_plan, unchanged: fz_debug_multi_plan_mode answers for this call
+// too), every group one filter launch over the packed bytes plus one RAGGED verification launch (fz_mp_batch_verify_kernel /
+// fz_mp_batch_verify_subs_kernel: every candidate inside its own sequence), every other pattern through batch_search_impl.
+// Per pattern the rows are then ordered, shifted and reduced exactly as fz_batch_search does it (batch_order).
+int fz_batch_search_multi(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k,
+                          int reduced, fz_match **out, uint32_t **seq_of, uint64_t **out_offs) {
+    if (!out || !seq_of || !out_offs) return fail(FZ_EINVAL, "null argument");
+    *out = nullptr; *seq_of = nullptr; *out_offs = nullptr;
+    if (!ctx || !batch || batch->ctx != ctx) return fail(FZ_EINVAL, "bad ctx/seq handle");
+    if (mode != FZ_MODE_LEV && mode != FZ_MODE_SUBS) return fail(FZ_EINVAL, "mode must be Levenshtein or substitutions-only");
+    int rc = batch_single_device(ctx, batch);
+    if (rc) return rc;
+    if (!batch->is_batch) return fail(FZ_EINVAL, "fz_batch_search_multi takes a batch handle (fz_batch_upload)");
+    if (ctx->npend) return fail(FZ_EINVAL, "a search started with fz_lev_ngrams_begin is still in flight");
+    if (ctx->stream_inflight) return fail(FZ_EINVAL, "a file stream of this context has a batch in flight (finish or close it first)");
+    rc = mp_check_lists(pats, offs, n_pats);
+    if (rc) return rc;
+    const bool subs = mode == FZ_MODE_SUBS;
+    {   // every pattern passes the single call's checks before anything is searched
+        BatchScope scope(ctx);
+        for (uint32_t i = 0; i < n_pats; ++i) {
+            const uint64_t m = offs[i + 1] - offs[i];
+            if (m > FZ_MAX_M_ANY) return fail(FZ_EUNSUPPORTED, "subsequence longer than %u bytes", FZ_MAX_M_ANY);
+            Search q;
+            rc = subs ? subs_plan(ctx, batch, m ? pats + offs[i] : nullptr, (uint32_t)m, k, q)
+                      : lev_plan(ctx, batch, m ? pats + offs[i] : nullptr, (uint32_t)m, k, q);
+            if (rc) return rc;
+        }
+    }
+    std::vector<MpGroup> groups;
+    std::vector<uint32_t> group_of;
+    mp_plan(mode, pats, offs, n_pats, k, groups, group_of);
+    std::vector<std::vector<fz_match>> fin(n_pats);
+    std::vector<std::vector<uint32_t>> fin_seq(n_pats);
+    MpTotals tot;
+    uint32_t form = FZ_FORM_NONE;
+    for (uint32_t i = 0; i < n_pats; ++i) {
+        if (group_of[i] != 0xffffffffu) continue;
+        rc = batch_search_impl(ctx, batch, mode, pats + offs[i], (uint32_t)(offs[i + 1] - offs[i]), k, reduced, fin[i], fin_seq[i]);
+        if (rc) return rc;
+        tot.bytes += ctx->stats.bytes_scanned; tot.hits += ctx->stats.ngram_hits; tot.rows += ctx->stats.raw_matches;
+        tot.launches += ctx->stats.filter_launches;
+        if (ctx->stats.verify_form != FZ_FORM_NONE) form = ctx->stats.verify_form;
+    }
+    ctx->view = nullptr; ctx->view_n = 0; ctx->rows_ready = false;
+    if (!groups.empty() && batch->n_seqs && batch->n) {
+        std::vector<std::vector<fz_match>> rows(n_pats);           // global coordinates, in-memory order
+        for (const MpGroup &g : groups) {
+            rc = mp_run_group(ctx, batch, mode, pats, offs, k, g, rows, tot);
+            if (rc) return rc;
+            form = FZ_FORM_KERNEL;
+            for (uint32_t i : g.pats) {
+                rc = batch_order(batch, mode, reduced != 0, rows[i], fin[i], fin_seq[i]);
+                if (rc) return rc;
+                std::vector<fz_match>().swap(rows[i]);
+            }
+        }
+    }
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n_pats; ++i) total += fin[i].size();
+    void *mem = nullptr, *smem_ = nullptr, *omem = nullptr;
+    rc = alloc_out(total, sizeof(fz_match), &mem);
+    if (rc) return rc;
+    rc = alloc_out(total, sizeof(uint32_t), &smem_);
+    if (rc) { release_out(mem); return rc; }
+    rc = alloc_out((uint64_t)n_pats + 1, sizeof(uint64_t), &omem);
+    if (rc) { release_out(mem); release_out(smem_); return rc; }
+    fz_match *mo = static_cast<fz_match *>(mem);
+    uint32_t *so = static_cast<uint32_t *>(smem_);
+    uint64_t *oo = static_cast<uint64_t *>(omem);
+    uint64_t at = 0;
+    for (uint32_t i = 0; i < n_pats; ++i) {
+        oo[i] = at;
+        if (!fin[i].empty()) {
+            memcpy(mo + at, fin[i].data(), fin[i].size() * sizeof(fz_match));
+            memcpy(so + at, fin_seq[i].data(), fin_seq[i].size() * sizeof(uint32_t));
+        }
+        at += fin[i].size();
+    }
+    oo[n_pats] = at;
+    *out = mo; *seq_of = so; *out_offs = oo;
+    memset(&ctx->stats, 0, sizeof ctx->stats);
+    ctx->tref.clear();
+    ctx->stats.n_devices = (uint32_t)ctx->devs.size();
+    ctx->stats.filter_launches = tot.launches;
+    ctx->stats.bytes_scanned = tot.bytes;
+    ctx->stats.ngram_hits = tot.hits;
+    ctx->stats.raw_matches = tot.rows;
+    ctx->stats.filter_ms = tot.filter_ms;
+    ctx->stats.verify_ms = tot.verify_ms;
+    ctx->stats.device_ms = tot.filter_ms + tot.verify_ms;
+    ctx->stats.verify_form = form;
     return FZ_OK;
 }
 

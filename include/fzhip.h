@@ -235,8 +235,8 @@ int fz_debug_multi_plan_mode(uint32_t mode, const uint8_t *pats, const uint64_t 
  * neighbours = an empty sequence).  n_seqs < 2^32.  Next to the bytes two tables go to the device: the cumulative end
  * offsets (u64 per sequence) and, per 16 KiB tile, the first sequence that touches it (u32), which bounds the search for
  * a position's sequence.  Single-device, non-collective contexts (else FZ_EUNSUPPORTED).  The handle is a batch handle:
- * fz_batch_search takes it, every other search function answers FZ_EINVAL for it (and fz_batch_search answers FZ_EINVAL
- * for a plain sequence); fz_seq_len = the packed length; fz_seq_release / fz_destroy free bytes and tables. */
+ * fz_batch_search and fz_batch_search_multi take it, every other search function answers FZ_EINVAL for it (and those two
+ * answer FZ_EINVAL for a plain sequence); fz_seq_len = the packed length; fz_seq_release / fz_destroy free bytes and tables. */
 int fz_batch_upload(fz_ctx *ctx, const uint8_t *bytes, const uint64_t *offs, uint64_t n_seqs, fz_seq **out);
 
 /* mode: FZ_MODE_EXACT / _LEV / _SUBS = 0 / 1 / 2 (k = 0 / max_l_dist / max_substitutions).
@@ -252,6 +252,22 @@ int fz_batch_upload(fz_ctx *ctx, const uint8_t *bytes, const uint64_t *offs, uin
  * fz_stats afterwards as for any search (raw_matches = rows before the reduction). */
 int fz_batch_search(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8_t *p, uint32_t m, uint32_t k,
                     int reduced, fz_match **out, uint32_t **seq_of, uint64_t *n);
+
+/* Many patterns, many sequences: fz_batch_search for every pattern of a list (packed as fz_lev_ngrams_multi takes them;
+ * mode FZ_MODE_LEV or FZ_MODE_SUBS, one budget k) in as few passes over the packed bytes as the patterns allow.  The rows of
+ * pattern i are (*out)[(*out_offs)[i] .. (*out_offs)[i+1]) with their sequences at the same positions of *seq_of; that slice
+ * is byte for byte what fz_batch_search(ctx, batch, mode, pats + offs[i], m_i, k, reduced, ...) returns.  out_offs has
+ * n_pats + 1 entries (n_pats = 0: the single entry 0); an empty batch gives empty slices.  All three outputs are released
+ * with fz_free.
+ * The patterns are planned as fz_debug_multi_plan_mode reports (same domain, groups and cost rule as fz_lev_ngrams_multi /
+ * fz_subs_ngrams_multi): a group is one filter launch plus one verification launch that looks every candidate's sequence up
+ * and verifies it inside that sequence alone; the patterns outside every group run, inside the same call, the code of
+ * fz_batch_search.  Every pattern passes the single call's checks before anything is searched: the first refusal is the
+ * call's, with its code.  FZ_EINVAL for a plain sequence handle, a search of the context still in flight or a file stream
+ * in flight; FZ_EUNSUPPORTED for contexts of several devices or in a communicator.
+ * fz_stats afterwards: the sums over the call; verify_form = FZ_FORM_KERNEL when a group rode a pass. */
+int fz_batch_search_multi(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats,
+                          uint32_t k, int reduced, fz_match **out, uint32_t **seq_of, uint64_t **out_offs);
 
 /* Test hook, no device needed: the sequence of position idx of a batch with the offsets `offs` — the lookup the kernels
  * run (fz_device.h: fz_segment_ragged, the per-tile bound included), on the host.  *j = its number, [*sa, *se) its bytes.
