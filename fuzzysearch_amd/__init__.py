@@ -26,6 +26,7 @@ from . import _file_stream
 from .multi import find_near_matches_multi
 from .batch import find_near_matches_batch, resident_batch
 from .multi_batch import find_near_matches_multi_batch
+from .assign import find_best_matches_batch, BestMatches
 
 __version__ = '0.1.0'
 
@@ -35,6 +36,8 @@ __all__ = [
     'find_near_matches_multi',
     'find_near_matches_batch',
     'find_near_matches_multi_batch',
+    'find_best_matches_batch',
+    'BestMatches',
     'Match',
     'resident',
     'resident_batch',

@@ -31,6 +31,7 @@ EXPORTED_SYMBOLS = (
     "fz_subs_ngrams_multi", "fz_subs_ngrams_multi_best", "fz_debug_multi_plan_mode",
     "fz_batch_upload", "fz_batch_search", "fz_debug_batch_segment",
     "fz_batch_search_multi",
+    "fz_batch_assign", "fz_debug_assign_fold",
 )
 
 
@@ -175,6 +176,11 @@ def load_library():
             L.fz_batch_search_multi.restype = ci
             L.fz_batch_search_multi.argtypes = [vp, vp, u32, u8p, u64p, u32, u32, ci, mpp, ctypes.POINTER(ctypes.POINTER(u32)),
                                                 ctypes.POINTER(u64p)]
+        if hasattr(L, "fz_batch_assign"):                   # (absent from builds of earlier rounds named by FUZZYSEARCH_HIP_LIB for an A/B)
+            L.fz_batch_assign.restype = ci
+            L.fz_batch_assign.argtypes = [vp, vp, u32, u8p, u64p, u32, u32, ctypes.POINTER(vp)]
+            L.fz_debug_assign_fold.restype = ci
+            L.fz_debug_assign_fold.argtypes = [vp, u64, vp, u64, u32, vp, u32, vp, u32, u32, vp]
         L.fz_debug_batch_segment.restype = ci
         L.fz_debug_batch_segment.argtypes = [u64p, u64, u64, u64p, u64p, u64p]
         L.fz_subs_ngrams_best.restype = ci
@@ -424,6 +430,52 @@ def batch_segment(offs, idx):
     return j.value, sa.value, se.value
 
 
+_ASSIGN_DTYPE = None
+
+
+def assign_dtype():
+    """The numpy dtype of an fz_assign row (include/fzhip.h): pattern (-1: nothing matched), dist, tied, start, end."""
+    global _ASSIGN_DTYPE
+    if _ASSIGN_DTYPE is None:
+        import numpy as np
+        _ASSIGN_DTYPE = np.dtype([("pattern", "<i4"), ("dist", "<u2"), ("tied", "<u2"), ("start", "<u4"), ("end", "<u4")])
+    return _ASSIGN_DTYPE
+
+
+def _take_assign_array(L, addr, n):
+    """-> numpy structured array of fz_assign rows: viewed in place over the library's buffer when large (handed back when
+    the last view dies), copied and freed when small — as _take_matches_array does for fz_match rows."""
+    import numpy as np
+    nbytes = n * assign_dtype().itemsize
+    if nbytes >= (256 << 10):
+        raw = (ctypes.c_char * nbytes).from_address(addr)
+        raw._owner = _ResultBuffer(L, addr)
+        return np.frombuffer(raw, dtype=assign_dtype(), count=n)
+    arr = np.empty(n, dtype=assign_dtype())
+    if n:
+        ctypes.memmove(arr.ctypes.data, addr, nbytes)
+    L.fz_free(ctypes.c_void_p(addr))
+    return arr
+
+
+def assign_fold(offs, recs, L, pat_table, pat_m, k):
+    """fz_debug_assign_fold (no device): the fold of fz_batch_assign on the host, through the functions its kernels run.
+    offs: numpy uint64 offsets (n_seqs + 1); recs: numpy array of 24-byte records (u64 key, u32 l, r, dist, aux);
+    pat_table: numpy uint32 array of shape (n, 2) = {pattern index, m} per aux; pat_m: the patterns' lengths.
+    -> fz_assign structured array of n_seqs rows."""
+    import numpy as np
+    lib = load_library()
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    recs = np.ascontiguousarray(recs)
+    assert recs.dtype.itemsize == 24
+    pat_table = np.ascontiguousarray(pat_table, dtype=np.uint32).reshape(-1, 2)
+    pat_m = np.ascontiguousarray(pat_m, dtype=np.uint32)
+    out = np.empty(len(offs) - 1, dtype=assign_dtype())
+    _check(lib.fz_debug_assign_fold(offs.ctypes.data, len(offs) - 1, recs.ctypes.data, len(recs), L, pat_table.ctypes.data,
+                                    len(pat_table), pat_m.ctypes.data, len(pat_m), k, out.ctypes.data))
+    return out
+
+
 class OwnedRows(object):
     """A C-ABI result buffer (fz_match rows) that has not been copied anywhere: address, n, and fz_free on release."""
     __slots__ = ('_lib', '_ptr', 'n')
@@ -593,7 +645,9 @@ class Engine(object):
             _check(self._lib.fz_batch_upload(self._h, addr, offs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
                                              len(offs) - 1, ctypes.byref(h)))
         del keep
-        return ResidentSequence(self, h, n)
+        seq = ResidentSequence(self, h, n)
+        seq.n_seqs = len(offs) - 1
+        return seq
 
     def _batch_call(self, batch, mode, pattern, k, reduced):
         if type(pattern) is bytes:
@@ -661,6 +715,16 @@ class Engine(object):
         patterns = list(patterns)
         ptr, seq_of, bounds = self._batch_multi_call(batch, mode, patterns, k, reduced)
         return OwnedRows(self._lib, ptr, bounds[-1]), seq_of, bounds
+
+    def batch_assign(self, batch, mode, patterns, k):
+        """fz_batch_assign: the best pattern of the list per sequence of the batch -> a structured array (assign_dtype) of
+        one row per sequence over the library's buffer: pattern (-1: none), dist, tied, start, end (local coordinates)."""
+        patterns = list(patterns)
+        blob, offs = pack_patterns(patterns)
+        ptr = ctypes.c_void_p()
+        with self._lock:
+            _check(self._lib.fz_batch_assign(self._h, batch._h, mode, blob, offs, len(patterns), k, ctypes.byref(ptr)))
+        return _take_assign_array(self._lib, ptr.value, batch.n_seqs)     # (a plain handle was refused above)
 
     def upload_shard(self, data, buf_global_off, own_lo, own_hi, global_n):
         addr, n, keep = _buffer_address(data)

@@ -1297,3 +1297,65 @@ FZ_HD bool fz_mp_rag_accept(uint32_t mode, const FzGeom &g, const FzSeg &sg, uin
     c.whi = whi;
     return true;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Best-pattern assignment per sequence (fz_batch_assign; fz_kernels.h: fz_assign_reduce_kernel / fz_assign_finish_kernel).
+// Every record of a verification launch becomes two keys, and the answer for a sequence is an unsigned minimum over its
+// records' keys — two atomics per record that improves its sequence, no per-pattern state:
+//     lo = dist << 56 | pattern << 40 | start_local << 8 | (m + k - len)     min: (dist, lowest pattern, smallest start, longest)
+//     hi = dist << 16 | (0xffff - pattern)                                   min: (dist, HIGHEST pattern)
+// `tied` = the pattern of hi differs from the pattern of lo: some other list position reaches the same distance.  (m - k <=
+// len <= m + k, so the last field is 0 .. 2k.)  The bit fields give the domain: k <= FZ_ASSIGN_MAX_K (the all-ones initial
+// value is no key), at most FZ_ASSIGN_MAX_PATS patterns, every sequence shorter than 2^32 bytes.
+#define FZ_ASSIGN_MAX_K 127u
+#define FZ_ASSIGN_MAX_PATS 65535u
+#define FZ_ASSIGN_NONE_LO 0xffffffffffffffffull
+#define FZ_ASSIGN_NONE_HI 0xffffffffu
+
+FZ_HD uint64_t fz_assign_key(uint32_t dist, uint32_t pattern, uint32_t start_local, uint32_t len, uint32_t m, uint32_t k) {
+    return ((uint64_t)dist << 56) | ((uint64_t)pattern << 40) | ((uint64_t)start_local << 8) | (uint64_t)((m + k - len) & 0xffu);
+}
+FZ_HD uint32_t fz_assign_key_hi(uint32_t dist, uint32_t pattern) { return (dist << 16) | (0xffffu - pattern); }
+
+FZ_HD uint32_t fz_assign_key_dist(uint64_t key) { return (uint32_t)(key >> 56); }
+FZ_HD uint32_t fz_assign_key_pattern(uint64_t key) { return (uint32_t)(key >> 40) & 0xffffu; }
+FZ_HD uint32_t fz_assign_key_start(uint64_t key) { return (uint32_t)(key >> 8); }
+FZ_HD uint32_t fz_assign_key_len(uint64_t key, uint32_t m, uint32_t k) { return m + k - (uint32_t)(key & 0xffu); }
+FZ_HD uint32_t fz_assign_hi_dist(uint32_t hi) { return hi >> 16; }
+FZ_HD uint32_t fz_assign_hi_pattern(uint32_t hi) { return 0xffffu - (hi & 0xffffu); }
+
+// aux of a record -> {the pattern's position in the caller's list, its length}: 64 entries for a group, one entry (aux
+// ignored) for a pattern searched on its own.
+struct FzAssignPat { uint32_t pattern, m; };
+
+// One output row (= fz_assign of include/fzhip.h): pattern = -1 and the rest 0 where nothing matched.
+struct FzAssignRow { int32_t pattern; uint16_t dist, tied; uint32_t start, end; };
+
+// What one record asks of its sequence's table entries: -> false when it does not count (no match, beyond the budget,
+// outside every sequence).  start = idx - l, len = l + L + r, in the coordinates of the sequence that holds idx.
+FZ_HD bool fz_assign_keys(const FzRagged &t, uint64_t n, const FzRec &r, uint32_t L, const FzAssignPat *pat, uint32_t npat, uint32_t k,
+                          uint32_t &seq, uint64_t &lo, uint32_t &hi) {
+    if (r.dist == FZ_REC_NONE || r.dist > k) return false;
+    const uint64_t idx = fz_hit_index(r.key);
+    const FzSeg sg = fz_segment_ragged(t, n, idx);
+    if (!sg.ok || idx < sg.sa + r.l) return false;
+    const FzAssignPat p = pat[npat > 1u ? (r.aux < npat ? r.aux : 0u) : 0u];
+    seq = sg.j;
+    lo = fz_assign_key(r.dist, p.pattern, (uint32_t)(idx - r.l - sg.sa), r.l + L + r.r, p.m, k);
+    hi = fz_assign_key_hi(r.dist, p.pattern);
+    return true;
+}
+
+// A sequence's two table entries -> its output row.  pm = the lengths of the caller's patterns (the key holds m + k - len).
+FZ_HD FzAssignRow fz_assign_row(uint64_t lo, uint32_t hi, const uint32_t *pm, uint32_t k) {
+    FzAssignRow o;
+    o.pattern = -1; o.dist = 0; o.tied = 0; o.start = 0; o.end = 0;
+    if (lo == FZ_ASSIGN_NONE_LO) return o;
+    const uint32_t p = fz_assign_key_pattern(lo);
+    o.pattern = (int32_t)p;
+    o.dist = (uint16_t)fz_assign_key_dist(lo);
+    o.tied = fz_assign_hi_pattern(hi) != p ? 1u : 0u;
+    o.start = fz_assign_key_start(lo);
+    o.end = o.start + fz_assign_key_len(lo, pm[p], k);
+    return o;
+}

@@ -2254,3 +2254,42 @@ __global__ __launch_bounds__(FZ_FILTER_THREADS) void fz_mp_batch_verify_subs_ker
 #include "fz_kernel_bodies.inc"
 #undef FZ_KERNEL_BODY
 }
+
+// ---------------------------------------------------------------------------------------------
+// Best-pattern assignment (fz_batch_assign; fz_device.h: fz_assign_*).  Behind a verification launch the records are in HBM
+// and the answer a demultiplexer wants is a minimum per sequence over them:
+//
+//   fz_assign_reduce_kernel  one record per lane, grid-strided: its sequence (the ragged lookup the verification ran), its two
+//       keys, then an unsigned atomic minimum on lo[seq] (u64) and on hi[seq] (u32), device scope, no return value.  Before
+//       each atomic the lane reads the entry with a relaxed device-scope load and skips the atomic when the entry is already
+//       <= its key: the tables only ever decrease, so a stale value can cost a superfluous atomic, never a wrong skip.  Records
+//       that concentrate in one sequence (one long read, periodic reads) would otherwise serialise on one word at the ~90
+//       atomics/us a single word sustains.  No LDS.
+//   fz_assign_finish_kernel  one lane per sequence: the two entries decoded into the 16-byte output row.
+#define FZ_ASSIGN_THREADS 256u
+
+__global__ __launch_bounds__(FZ_ASSIGN_THREADS) void fz_assign_reduce_kernel(const FzRec *__restrict__ recs, uint64_t n_recs, uint32_t L,
+                                                                             FzRagged rag, uint64_t n, const FzAssignPat *__restrict__ pat,
+                                                                             uint32_t npat, uint32_t k, unsigned long long *__restrict__ lo,
+                                                                             uint32_t *__restrict__ hi) {
+    const uint64_t stride = (uint64_t)gridDim.x * FZ_ASSIGN_THREADS;
+    for (uint64_t i = (uint64_t)blockIdx.x * FZ_ASSIGN_THREADS + threadIdx.x; i < n_recs; i += stride) {
+        const FzRec r = recs[i];
+        uint32_t seq, khi;
+        uint64_t klo;
+        if (!fz_assign_keys(rag, n, r, L, pat, npat, k, seq, klo, khi)) continue;
+        if (__hip_atomic_load(&lo[seq], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > klo)
+            (void)__hip_atomic_fetch_min(&lo[seq], (unsigned long long)klo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (__hip_atomic_load(&hi[seq], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > khi)
+            (void)__hip_atomic_fetch_min(&hi[seq], khi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+__global__ __launch_bounds__(FZ_ASSIGN_THREADS) void fz_assign_finish_kernel(const unsigned long long *__restrict__ lo,
+                                                                             const uint32_t *__restrict__ hi, uint64_t n_seqs,
+                                                                             const uint32_t *__restrict__ pm, uint32_t k,
+                                                                             FzAssignRow *__restrict__ out) {
+    const uint64_t stride = (uint64_t)gridDim.x * FZ_ASSIGN_THREADS;
+    for (uint64_t j = (uint64_t)blockIdx.x * FZ_ASSIGN_THREADS + threadIdx.x; j < n_seqs; j += stride)
+        out[j] = fz_assign_row(lo[j], hi[j], pm, k);
+}

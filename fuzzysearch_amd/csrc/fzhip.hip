@@ -209,6 +209,10 @@ struct DevState {
     // single-pattern searches keep between calls (zeroed headers, result slots, the direct mode) is touched
     uint8_t *d_mp_desc = nullptr, *d_mp_ctr = nullptr, *d_mp_hits = nullptr, *d_mp_recs = nullptr;
     uint64_t mp_hit_cap = 0, mp_rec_cap = 0;
+    // fz_batch_assign: the call's tables and output rows (lo, hi, rows, pattern lengths, aux table: assign_ensure), and the
+    // records of a pattern searched on its own on their way to the fold; both grow and stay, like the buffers above
+    uint8_t *d_assign = nullptr, *d_assign_recs = nullptr;
+    uint64_t assign_cap = 0, assign_rec_cap = 0;
     int slot_id = 0;                             // which of the two result slots is the current one
     uint32_t launches_used = 0;                  // scan launches of the last enqueue on this device
     // Two fused searches in flight: the younger one's scan on the stream the older one does not use, so that it starts
@@ -460,6 +464,7 @@ struct fz_seq {
     std::vector<uint64_t> ends;
     uint64_t *d_ends = nullptr;
     uint32_t *d_first = nullptr;
+    uint64_t max_seq_len = 0;                    // the longest sequence (fz_batch_assign: local starts are 32-bit key fields)
 };
 
 namespace {
@@ -2320,7 +2325,7 @@ static void devstate_destroy(DevState &d) {
     if (d.h_big) (void)hipHostFree(d.h_big);
     if (d.d_cand) (void)hipFree(d.d_cand);
     if (d.d_pat) (void)hipFree(d.d_pat);
-    for (uint8_t *mp : {d.d_mp_desc, d.d_mp_ctr, d.d_mp_hits, d.d_mp_recs}) if (mp) (void)hipFree(mp);
+    for (uint8_t *mp : {d.d_mp_desc, d.d_mp_ctr, d.d_mp_hits, d.d_mp_recs, d.d_assign, d.d_assign_recs}) if (mp) (void)hipFree(mp);
     if (d.d_gen_order) (void)hipFree(d.d_gen_order);
     if (d.d_gen_rows) (void)hipFree(d.d_gen_rows);
     if (d.d_gen_dedup) (void)hipFree(d.d_gen_dedup);
@@ -2597,6 +2602,8 @@ int fz_batch_upload(fz_ctx *ctx, const uint8_t *bytes, const uint64_t *offs, uin
     if (offs[0] != 0) return fail(FZ_EINVAL, "offs[0] must be 0");
     for (uint64_t j = 0; j < n_seqs; ++j)
         if (offs[j + 1] < offs[j]) return fail(FZ_EINVAL, "sequence offsets must not decrease");
+    uint64_t longest = 0;
+    for (uint64_t j = 0; j < n_seqs; ++j) longest = std::max(longest, offs[j + 1] - offs[j]);
     const uint64_t n = offs[n_seqs];
     if (!bytes && n) return fail(FZ_EINVAL, "null argument");
     if (n >= (1ull << FZ_IDX_BITS)) return fail(FZ_EUNSUPPORTED, "sequence too long");
@@ -2609,6 +2616,7 @@ int fz_batch_upload(fz_ctx *ctx, const uint8_t *bytes, const uint64_t *offs, uin
     seq->n = n;
     seq->is_batch = true;
     seq->n_seqs = n_seqs;
+    seq->max_seq_len = longest;
     FzGeom g{};
     g.n = n;
     g.buf_off = 0;
@@ -2864,9 +2872,11 @@ struct MpTotals { uint64_t bytes = 0, hits = 0, rows = 0; uint32_t launches = 0;
 // arguments — the project's estimate of expected candidates, sequence bytes x blocks / sigma^L (sigma = distinct symbols
 // of the group's patterns), twice over and spread over the lists; a launch that overflows a list or the record buffer is
 // run again with what its counters ask for.
-static int mp_run_shard(fz_ctx *ctx, const Shard &sh, uint32_t mode, const uint32_t *desc, uint32_t nent, uint32_t k, uint32_t L, uint32_t max_m,
-                        uint32_t sigma, std::vector<FzRec> &recs, MpTotals &tot, bool rag = false) {
+// -> *n_recs records in d.d_mp_recs (the attempt that did not overflow), the stream idle.
+static int mp_launch_shard(fz_ctx *ctx, const Shard &sh, uint32_t mode, const uint32_t *desc, uint32_t nent, uint32_t k, uint32_t L, uint32_t max_m,
+                           uint32_t sigma, uint64_t *n_recs, MpTotals &tot, bool rag = false) {
     DevState &d = ctx->devs[sh.dev];
+    *n_recs = 0;
     const uint64_t ntiles = (sh.geom.buf_len + FZ_TILE_BYTES - 1) / FZ_TILE_BYTES;
     tot.bytes += sh.geom.buf_len;
     if (ntiles == 0) return FZ_OK;
@@ -2929,9 +2939,7 @@ static int mp_run_shard(fz_ctx *ctx, const Shard &sh, uint32_t mode, const uint3
             rec_cap = std::max(rec_cap, need_hits > a.hit_cap ? 2 * nr : nr);
             continue;
         }
-        const size_t at = recs.size();
-        recs.resize(at + nr);
-        if (nr) HIP_TRY(hipMemcpy(recs.data() + at, d.d_mp_recs, nr * sizeof(FzRec), hipMemcpyDeviceToHost));
+        *n_recs = nr;
         uint64_t confirmed = 0, appended = 0;
         for (uint32_t i = 0; i < 64; ++i) confirmed += ctr[8 + i];
         for (uint32_t l = 0; l < FZ_MP_LISTS; ++l) appended += ctr[FZ_MP_CTR_LIST(l)];
@@ -2944,8 +2952,21 @@ static int mp_run_shard(fz_ctx *ctx, const Shard &sh, uint32_t mode, const uint3
     return fail(FZ_EDEVICE, "result buffers kept overflowing");
 }
 
-static int mp_run_group(fz_ctx *ctx, fz_seq *seq, uint32_t mode, const uint8_t *pats, const uint64_t *offs, uint32_t k, const MpGroup &g,
-                        std::vector<std::vector<fz_match>> &rows, MpTotals &tot) {
+// ... and the records appended to `recs` on the host.
+static int mp_run_shard(fz_ctx *ctx, const Shard &sh, uint32_t mode, const uint32_t *desc, uint32_t nent, uint32_t k, uint32_t L, uint32_t max_m,
+                        uint32_t sigma, std::vector<FzRec> &recs, MpTotals &tot, bool rag = false) {
+    uint64_t nr = 0;
+    int rc = mp_launch_shard(ctx, sh, mode, desc, nent, k, L, max_m, sigma, &nr, tot, rag);
+    if (rc) return rc;
+    const size_t at = recs.size();
+    recs.resize(at + nr);
+    if (nr) HIP_TRY(hipMemcpy(recs.data() + at, ctx->devs[sh.dev].d_mp_recs, nr * sizeof(FzRec), hipMemcpyDeviceToHost));
+    return FZ_OK;
+}
+
+// The descriptor of a group: -> its entries (0: failed), the longest pattern and the number of distinct symbols.
+static int mp_describe_group(const uint8_t *pats, const uint64_t *offs, const MpGroup &g, std::vector<uint32_t> &desc, uint32_t *nent_out,
+                             uint32_t *max_m_out, uint32_t *sigma_out) {
     const uint32_t np = (uint32_t)g.pats.size();
     const uint8_t *pp[FZ_MP_MAX_PATS];
     uint32_t pm[FZ_MP_MAX_PATS], max_m = 0;
@@ -2957,12 +2978,23 @@ static int mp_run_group(fz_ctx *ctx, fz_seq *seq, uint32_t mode, const uint8_t *
         max_m = std::max(max_m, pm[j]);
         for (uint32_t q = 0; q < pm[j]; ++q) if (!seen[pp[j][q]]) { seen[pp[j][q]] = true; ++sigma; }
     }
-    std::vector<uint32_t> desc(FZ_MP_DESC_WORDS);
+    desc.assign(FZ_MP_DESC_WORDS, 0u);
     const uint32_t nent = fz_mp_build(desc.data(), pp, pm, np, g.L);
     if (nent == 0 || nent != g.blocks) return fail(FZ_EDEVICE, "internal: the group's block table does not match its plan");
+    *nent_out = nent; *max_m_out = max_m; *sigma_out = std::max(1u, sigma);
+    return FZ_OK;
+}
+
+static int mp_run_group(fz_ctx *ctx, fz_seq *seq, uint32_t mode, const uint8_t *pats, const uint64_t *offs, uint32_t k, const MpGroup &g,
+                        std::vector<std::vector<fz_match>> &rows, MpTotals &tot) {
+    const uint32_t np = (uint32_t)g.pats.size();
+    std::vector<uint32_t> desc;
+    uint32_t nent = 0, max_m = 0, sigma = 0;
+    int drc = mp_describe_group(pats, offs, g, desc, &nent, &max_m, &sigma);
+    if (drc) return drc;
     std::vector<FzRec> recs;
     for (const Shard &sh : seq->shards) {
-        int rc = mp_run_shard(ctx, sh, mode, desc.data(), nent, k, g.L, max_m, std::max(1u, sigma), recs, tot, seq->is_batch);
+        int rc = mp_run_shard(ctx, sh, mode, desc.data(), nent, k, g.L, max_m, sigma, recs, tot, seq->is_batch);
         if (rc) return rc;
     }
     // per pattern: its records (aux = the pattern's number in the group) in the reference's order — block ascending, hit
@@ -3437,9 +3469,63 @@ static int batch_order(fz_seq *batch, uint32_t mode, bool reduce, const std::vec
     return FZ_OK;
 }
 
+// fz_batch_assign: the call's device state, and the fold of one launch's records into its tables.
+struct AssignCall {
+    DevState *d = nullptr;
+    FzRagged rag{};
+    uint64_t n = 0, n_seqs = 0;
+    uint32_t k = 0;
+    unsigned long long *d_lo = nullptr;
+    uint32_t *d_hi = nullptr, *d_pm = nullptr;
+    FzAssignRow *d_rows = nullptr;
+    FzAssignPat *d_pat = nullptr;
+    uint64_t folded = 0;
+    double fold_ms = 0;
+};
+
+// recs: n device records; table: npat entries of the call's aux table (one entry: aux ignored).  Stream-ordered, no wait.
+static int assign_fold_device(fz_ctx *ctx, AssignCall &ac, const FzRec *d_recs, uint64_t n, uint32_t L, const FzAssignPat *table, uint32_t npat) {
+    if (!n) return FZ_OK;
+    DevState &d = *ac.d;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((n + FZ_ASSIGN_THREADS - 1) / FZ_ASSIGN_THREADS, (uint64_t)d.n_cus * 8);
+    if (ctx->timing) HIP_TRY(hipEventRecord(d.ev[2], d.stream));
+    hipLaunchKernelGGL(fz_assign_reduce_kernel, dim3(grid), dim3(FZ_ASSIGN_THREADS), 0, d.stream, d_recs, n, L, ac.rag, ac.n, table, npat,
+                       ac.k, ac.d_lo, ac.d_hi);
+    HIP_TRY(hipGetLastError());
+    if (ctx->timing) {
+        HIP_TRY(hipEventRecord(d.ev[3], d.stream));
+        HIP_TRY(hipEventSynchronize(d.ev[3]));
+        float v = 0;
+        if (hipEventElapsedTime(&v, d.ev[2], d.ev[3]) == hipSuccess) ac.fold_ms += v;
+        (void)hipGetLastError();
+    }
+    return FZ_OK;
+}
+
+// The records of a pattern searched on its own (host memory, empty slots included) -> the device -> the same fold.
+static int assign_fold_host(fz_ctx *ctx, AssignCall &ac, const FzRec *recs, uint64_t n, uint32_t L, const FzAssignPat *table) {
+    if (!n) return FZ_OK;
+    DevState &d = *ac.d;
+    HIP_TRY(hipSetDevice(d.device));
+    if (d.assign_rec_cap < n) {
+        if (d.d_assign_recs) { HIP_TRY(hipFree(d.d_assign_recs)); d.d_assign_recs = nullptr; d.assign_rec_cap = 0; }
+        const uint64_t cap = std::max<uint64_t>(n + n / 2, 4096);
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d.d_assign_recs), (size_t)cap * sizeof(FzRec)));
+        d.assign_rec_cap = cap;
+    }
+    for (uint64_t i = 0; i < n; ++i) ac.folded += recs[i].dist != FZ_REC_NONE && recs[i].dist <= ac.k;
+    HIP_TRY(hipMemcpyAsync(d.d_assign_recs, recs, (size_t)n * sizeof(FzRec), hipMemcpyHostToDevice, d.stream));
+    int rc = assign_fold_device(ctx, ac, reinterpret_cast<const FzRec *>(d.d_assign_recs), n, L, table, 1u);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(d.stream));               // (the records are the search's own buffer, reused by the next one)
+    return FZ_OK;
+}
+
 // fz_batch_search without its result buffers: what fz_batch_search_multi runs for the patterns outside every group.
+// (assign / assign_table: fz_batch_assign — the search's records are folded where fz_batch_search would order them.)
 static int batch_search_impl(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8_t *p, uint32_t m, uint32_t k, int reduced,
-                             std::vector<fz_match> &fin, std::vector<uint32_t> &fin_seq) {
+                             std::vector<fz_match> &fin, std::vector<uint32_t> &fin_seq, AssignCall *assign = nullptr,
+                             const FzAssignPat *assign_table = nullptr) {
     if (!ctx || !batch || batch->ctx != ctx) return fail(FZ_EINVAL, "bad ctx/seq handle");
     if (mode != FZ_MODE_EXACT && mode != FZ_MODE_LEV && mode != FZ_MODE_SUBS) return fail(FZ_EINVAL, "mode must be exact, Levenshtein or substitutions-only");
     if (mode == FZ_MODE_EXACT && k != 0) return fail(FZ_EINVAL, "an exact search has no budget");
@@ -3470,6 +3556,11 @@ static int batch_search_impl(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const ui
         std::vector<uint64_t> hits;
         rc = run_search(ctx, batch, q, mode != FZ_MODE_EXACT, recs, hits);
         if (rc) return rc;
+        if (assign) {
+            if (mode == FZ_MODE_EXACT || ctx->rows_ready) return fail(FZ_EDEVICE, "internal: no records to fold");
+            return ctx->view ? assign_fold_host(ctx, *assign, ctx->view, ctx->view_n, q.plan.L, assign_table)
+                             : assign_fold_host(ctx, *assign, recs.data(), recs.size(), q.plan.L, assign_table);
+        }
         if (mode == FZ_MODE_EXACT) {
             std::sort(hits.begin(), hits.end());
             rows.resize(hits.size());
@@ -3605,6 +3696,194 @@ int fz_batch_search_multi(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8
     ctx->stats.verify_ms = tot.verify_ms;
     ctx->stats.device_ms = tot.filter_ms + tot.verify_ms;
     ctx->stats.verify_form = form;
+    return FZ_OK;
+}
+
+// Best pattern per sequence.  The checks, the plan and the launches of fz_batch_search_multi; behind every verification
+// launch fz_assign_reduce_kernel folds the records where they lie into the call's tables (lo: u64, hi: u32 per sequence),
+// fz_assign_finish_kernel decodes them and ONE copy brings the rows to the host: no record copy, no ordering, no rows.
+int fz_batch_assign(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k,
+                    fz_assign **out) {
+    static_assert(sizeof(fz_assign) == sizeof(FzAssignRow) && sizeof(fz_assign) == 16, "the kernel writes the C-ABI's rows");
+    if (!out) return fail(FZ_EINVAL, "null argument");
+    *out = nullptr;
+    if (!ctx || !batch || batch->ctx != ctx) return fail(FZ_EINVAL, "bad ctx/seq handle");
+    if (mode != FZ_MODE_LEV && mode != FZ_MODE_SUBS) return fail(FZ_EINVAL, "mode must be Levenshtein or substitutions-only");
+    int rc = batch_single_device(ctx, batch);
+    if (rc) return rc;
+    if (!batch->is_batch) return fail(FZ_EINVAL, "fz_batch_assign takes a batch handle (fz_batch_upload)");
+    if (ctx->npend) return fail(FZ_EINVAL, "a search started with fz_lev_ngrams_begin is still in flight");
+    if (ctx->stream_inflight) return fail(FZ_EINVAL, "a file stream of this context has a batch in flight (finish or close it first)");
+    rc = mp_check_lists(pats, offs, n_pats);
+    if (rc) return rc;
+    const bool subs = mode == FZ_MODE_SUBS;
+    {   // every pattern passes the single call's checks before anything is searched
+        BatchScope scope(ctx);
+        for (uint32_t i = 0; i < n_pats; ++i) {
+            const uint64_t m = offs[i + 1] - offs[i];
+            if (m > FZ_MAX_M_ANY) return fail(FZ_EUNSUPPORTED, "subsequence longer than %u bytes", FZ_MAX_M_ANY);
+            Search q;
+            rc = subs ? subs_plan(ctx, batch, m ? pats + offs[i] : nullptr, (uint32_t)m, k, q)
+                      : lev_plan(ctx, batch, m ? pats + offs[i] : nullptr, (uint32_t)m, k, q);
+            if (rc) return rc;
+        }
+    }
+    // the domain of the tables' keys (fz_device.h: fz_assign_key)
+    if (k > FZ_ASSIGN_MAX_K) return fail(FZ_EUNSUPPORTED, "best-pattern assignment takes budgets up to %u", FZ_ASSIGN_MAX_K);
+    if (n_pats > FZ_ASSIGN_MAX_PATS) return fail(FZ_EUNSUPPORTED, "best-pattern assignment takes at most %u patterns", FZ_ASSIGN_MAX_PATS);
+    if (batch->max_seq_len >= (1ull << 32)) return fail(FZ_EUNSUPPORTED, "best-pattern assignment takes sequences shorter than 2^32 bytes");
+    const uint64_t n_seqs = batch->n_seqs;
+    void *mem = nullptr;
+    rc = alloc_out(n_seqs, sizeof(fz_assign), &mem);
+    if (rc) return rc;
+    struct Guard { void *p; ~Guard() { if (p) release_out(p); } } guard{mem};
+    fz_assign *rows = static_cast<fz_assign *>(mem);
+    ctx->view = nullptr; ctx->view_n = 0; ctx->rows_ready = false;
+    memset(&ctx->stats, 0, sizeof ctx->stats);
+    ctx->tref.clear();
+    ctx->stats.n_devices = (uint32_t)ctx->devs.size();
+    if (n_pats == 0 || n_seqs == 0 || batch->n == 0) {         // nothing can match: nothing is launched
+        for (uint64_t j = 0; j < n_seqs; ++j) { rows[j].pattern = -1; rows[j].dist = 0; rows[j].tied = 0; rows[j].start = 0; rows[j].end = 0; }
+        guard.p = nullptr;
+        *out = rows;
+        return FZ_OK;
+    }
+    std::vector<MpGroup> groups;
+    std::vector<uint32_t> group_of;
+    mp_plan(mode, pats, offs, n_pats, k, groups, group_of);
+    // the aux tables of the whole call: 64 entries per group, then one entry per pattern searched on its own
+    std::vector<FzAssignPat> table(groups.size() * FZ_MP_MAX_PATS + n_pats);
+    std::vector<uint32_t> pm(n_pats);
+    for (uint32_t i = 0; i < n_pats; ++i) {
+        pm[i] = (uint32_t)(offs[i + 1] - offs[i]);
+        table[groups.size() * FZ_MP_MAX_PATS + i] = FzAssignPat{i, pm[i]};
+    }
+    for (size_t gi = 0; gi < groups.size(); ++gi)
+        for (uint32_t j = 0; j < FZ_MP_MAX_PATS; ++j) {
+            const uint32_t i = groups[gi].pats[j < groups[gi].pats.size() ? j : 0];
+            table[gi * FZ_MP_MAX_PATS + j] = FzAssignPat{i, pm[i]};
+        }
+    const Shard &sh = batch->shards[0];
+    DevState &d = ctx->devs[sh.dev];
+    HIP_TRY(hipSetDevice(d.device));
+    // lo | hi | rows | pattern lengths | aux tables (8-, 4-, 4-, 4-, 4-byte alignment; lo and hi are filled by one memset)
+    const uint64_t o_hi = n_seqs * 8, o_rows = o_hi + n_seqs * 4, o_pm = o_rows + n_seqs * sizeof(FzAssignRow);
+    const uint64_t o_pat = o_pm + (uint64_t)n_pats * 4, need = o_pat + table.size() * sizeof(FzAssignPat);
+    if (d.assign_cap < need) {
+        if (d.d_assign) { HIP_TRY(hipFree(d.d_assign)); d.d_assign = nullptr; d.assign_cap = 0; }
+        hipError_t e = hipMalloc(reinterpret_cast<void **>(&d.d_assign), (size_t)need);
+        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? FZ_ENOMEM : FZ_EDEVICE, "assignment tables: %s", hipGetErrorString(e));
+        d.assign_cap = need;
+    }
+    AssignCall ac;
+    ac.d = &d;
+    ac.rag = fz_ragged(sh.geom);
+    ac.n = sh.geom.n;
+    ac.n_seqs = n_seqs;
+    ac.k = k;
+    ac.d_lo = reinterpret_cast<unsigned long long *>(d.d_assign);
+    ac.d_hi = reinterpret_cast<uint32_t *>(d.d_assign + o_hi);
+    ac.d_rows = reinterpret_cast<FzAssignRow *>(d.d_assign + o_rows);
+    ac.d_pm = reinterpret_cast<uint32_t *>(d.d_assign + o_pm);
+    ac.d_pat = reinterpret_cast<FzAssignPat *>(d.d_assign + o_pat);
+    HIP_TRY(hipMemsetAsync(d.d_assign, 0xff, (size_t)o_rows, d.stream));
+    HIP_TRY(hipMemcpyAsync(ac.d_pm, pm.data(), (size_t)n_pats * 4, hipMemcpyHostToDevice, d.stream));
+    HIP_TRY(hipMemcpyAsync(ac.d_pat, table.data(), table.size() * sizeof(FzAssignPat), hipMemcpyHostToDevice, d.stream));
+    HIP_TRY(hipStreamSynchronize(d.stream));               // (the searches below may run on the context's other stream)
+    MpTotals tot;
+    uint32_t form = FZ_FORM_NONE;
+    std::vector<fz_match> no_rows;
+    std::vector<uint32_t> no_seq;
+    for (uint32_t i = 0; i < n_pats; ++i) {
+        if (group_of[i] != 0xffffffffu) continue;
+        rc = batch_search_impl(ctx, batch, mode, pats + offs[i], pm[i], k, 0, no_rows, no_seq, &ac,
+                               ac.d_pat + groups.size() * FZ_MP_MAX_PATS + i);
+        if (rc) return rc;
+        tot.bytes += ctx->stats.bytes_scanned; tot.hits += ctx->stats.ngram_hits;
+        tot.launches += ctx->stats.filter_launches;
+        if (ctx->stats.verify_form != FZ_FORM_NONE) form = ctx->stats.verify_form;
+    }
+    ctx->view = nullptr; ctx->view_n = 0; ctx->rows_ready = false;
+    std::vector<uint32_t> desc;
+    for (size_t gi = 0; gi < groups.size(); ++gi) {
+        const MpGroup &g = groups[gi];
+        uint32_t nent = 0, max_m = 0, sigma = 0;
+        rc = mp_describe_group(pats, offs, g, desc, &nent, &max_m, &sigma);
+        if (rc) return rc;
+        uint64_t nr = 0;
+        rc = mp_launch_shard(ctx, sh, mode, desc.data(), nent, k, g.L, max_m, sigma, &nr, tot, true);
+        if (rc) return rc;
+        // the attempt that did not overflow: its records, where they lie
+        rc = assign_fold_device(ctx, ac, reinterpret_cast<const FzRec *>(d.d_mp_recs), nr, g.L, ac.d_pat + gi * FZ_MP_MAX_PATS, FZ_MP_MAX_PATS);
+        if (rc) return rc;
+        ac.folded += nr;
+        form = FZ_FORM_KERNEL;
+    }
+    {
+        const uint32_t grid = (uint32_t)std::min<uint64_t>((n_seqs + FZ_ASSIGN_THREADS - 1) / FZ_ASSIGN_THREADS, (uint64_t)d.n_cus * 8);
+        if (ctx->timing) HIP_TRY(hipEventRecord(d.ev[2], d.stream));
+        hipLaunchKernelGGL(fz_assign_finish_kernel, dim3(grid), dim3(FZ_ASSIGN_THREADS), 0, d.stream, ac.d_lo, ac.d_hi, n_seqs, ac.d_pm, k, ac.d_rows);
+        HIP_TRY(hipGetLastError());
+        if (ctx->timing) HIP_TRY(hipEventRecord(d.ev[3], d.stream));
+        HIP_TRY(hipMemcpyAsync(rows, ac.d_rows, (size_t)n_seqs * sizeof(fz_assign), hipMemcpyDeviceToHost, d.stream));
+        HIP_TRY(hipStreamSynchronize(d.stream));
+        if (ctx->timing) {
+            float v = 0;
+            if (hipEventElapsedTime(&v, d.ev[2], d.ev[3]) == hipSuccess) ac.fold_ms += v;
+            (void)hipGetLastError();
+        }
+    }
+    guard.p = nullptr;
+    *out = rows;
+    memset(&ctx->stats, 0, sizeof ctx->stats);
+    ctx->tref.clear();
+    ctx->stats.n_devices = (uint32_t)ctx->devs.size();
+    ctx->stats.filter_launches = tot.launches;
+    ctx->stats.bytes_scanned = tot.bytes;
+    ctx->stats.ngram_hits = tot.hits;
+    ctx->stats.raw_matches = ac.folded;
+    ctx->stats.filter_ms = tot.filter_ms;
+    ctx->stats.verify_ms = tot.verify_ms + ac.fold_ms;
+    ctx->stats.device_ms = tot.filter_ms + tot.verify_ms + ac.fold_ms;
+    ctx->stats.verify_form = form;
+    return FZ_OK;
+}
+
+int fz_debug_assign_fold(const uint64_t *offs, uint64_t n_seqs, const void *recs, uint64_t n, uint32_t L, const uint32_t *pat_table,
+                         uint32_t n_table, const uint32_t *pat_m, uint32_t n_pats, uint32_t k, fz_assign *out) {
+    if (!offs || !out || (n && !recs) || !pat_table || !n_table || (n_pats && !pat_m)) return fail(FZ_EINVAL, "null argument");
+    if (n_seqs >= (1ull << 32)) return fail(FZ_EUNSUPPORTED, "more than 2^32 - 1 sequences in a batch");
+    if (k > FZ_ASSIGN_MAX_K) return fail(FZ_EUNSUPPORTED, "best-pattern assignment takes budgets up to %u", FZ_ASSIGN_MAX_K);
+    if (n_pats > FZ_ASSIGN_MAX_PATS) return fail(FZ_EUNSUPPORTED, "best-pattern assignment takes at most %u patterns", FZ_ASSIGN_MAX_PATS);
+    for (uint64_t j = 0; j < n_seqs; ++j) {
+        if (offs[j + 1] < offs[j]) return fail(FZ_EINVAL, "sequence offsets must not decrease");
+        if (offs[j + 1] - offs[j] >= (1ull << 32)) return fail(FZ_EUNSUPPORTED, "best-pattern assignment takes sequences shorter than 2^32 bytes");
+    }
+    const FzAssignPat *table = reinterpret_cast<const FzAssignPat *>(pat_table);
+    for (uint32_t i = 0; i < n_table; ++i)
+        if (table[i].pattern >= n_pats) return fail(FZ_EINVAL, "the pattern table names pattern %u of %u", table[i].pattern, n_pats);
+    const uint64_t total = offs[n_seqs];
+    const uint64_t ntiles = (total + FZ_TILE_BYTES - 1) / FZ_TILE_BYTES;
+    std::vector<uint32_t> first(ntiles + 1);
+    fz_ragged_first(offs + 1, n_seqs, ntiles, first.data());
+    FzRagged t;
+    t.ends = offs + 1; t.first = first.data(); t.n_seqs = n_seqs;
+    std::vector<uint64_t> lo(n_seqs, FZ_ASSIGN_NONE_LO);
+    std::vector<uint32_t> hi(n_seqs, FZ_ASSIGN_NONE_HI);
+    const uint8_t *rb = static_cast<const uint8_t *>(recs);
+    for (uint64_t i = 0; i < n; ++i) {                        // the reduce kernel's lane, one record at a time
+        FzRec r;
+        memcpy(&r, rb + i * sizeof(FzRec), sizeof r);
+        uint32_t seq, khi;
+        uint64_t klo;
+        if (!fz_assign_keys(t, total, r, L, table, n_table, k, seq, klo, khi)) continue;
+        if (lo[seq] > klo) lo[seq] = klo;
+        if (hi[seq] > khi) hi[seq] = khi;
+    }
+    for (uint64_t j = 0; j < n_seqs; ++j) {                   // the finish kernel's lane
+        const FzAssignRow r = fz_assign_row(lo[j], hi[j], pat_m, k);
+        memcpy(&out[j], &r, sizeof r);
+    }
     return FZ_OK;
 }
 

@@ -269,6 +269,44 @@ int fz_batch_search(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8_t *p,
 int fz_batch_search_multi(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats,
                           uint32_t k, int reduced, fz_match **out, uint32_t **seq_of, uint64_t **out_offs);
 
+/* Best-pattern assignment: one answer per sequence instead of P x S row lists (demultiplexing reads against a barcode
+ * list, adapter and primer panels, guide counting).  Row j of *out (n_seqs rows, released with fz_free):
+ *   pattern  the lowest index among the patterns whose smallest distance in sequence j is the smallest of all; -1 when no
+ *            pattern matches (then every other field is 0)
+ *   dist     that distance
+ *   tied     1 when at least one OTHER list position reaches the same dist in this sequence (a pattern listed twice ties
+ *            with itself), else 0: every other pattern is at least one edit worse or absent
+ *   start, end   local coordinates of one occurrence of `pattern` at `dist`: among that pattern's rows at that distance in
+ *            that sequence — the rows of fz_batch_search(..., reduced = 0) — the one with the smallest start, then the
+ *            largest end.  (pattern, dist and tied are also what the reduced rows give: a consolidation group keeps its
+ *            minimum distance.  Only the position is defined on the raw stream: overlap groups are not a device-side notion.)
+ * Nothing is ordered and no record is copied to the host: behind every verification launch one more kernel folds the
+ * records, where they lie, into two tables of n_seqs entries by atomic minimum (fz_assign_reduce_kernel), and the tables
+ * are decoded into the rows that are copied back (fz_assign_finish_kernel).
+ * Checks, planning (fz_debug_multi_plan_mode answers for this call too), launches and fz_stats as fz_batch_search_multi;
+ * raw_matches = records folded, verify_ms includes the fold.  Patterns outside every group are searched one by one as
+ * fz_batch_search does and their rows go through the same fold.  In addition FZ_EUNSUPPORTED, before anything is searched,
+ * for k > 127, more than 65 535 patterns, or a sequence of 2^32 bytes or more: the tables' keys have no room for them.
+ * n_pats = 0, an empty batch and a batch of empty sequences give n_seqs rows of -1 and launch nothing. */
+typedef struct {
+    int32_t  pattern;
+    uint16_t dist;
+    uint16_t tied;
+    uint32_t start, end;
+} fz_assign;
+
+int fz_batch_assign(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats,
+                    uint32_t k, fz_assign **out);
+
+/* Test hook, no device needed: the fold of fz_batch_assign on the host, through the very functions the two kernels run
+ * (fz_device.h: fz_assign_keys, fz_assign_row).  offs = the batch's n_seqs + 1 offsets; recs = n records of 24 bytes
+ * {u64 key (low 48 bits: global index of the n-gram hit), u32 l, u32 r, u32 dist, u32 aux} with start = index - l and
+ * end = index + L + r; pat_table = n_table pairs {u32 pattern index, u32 m} indexed by aux (one pair: aux ignored);
+ * pat_m = the lengths of the n_pats patterns.  out = n_seqs rows. */
+int fz_debug_assign_fold(const uint64_t *offs, uint64_t n_seqs, const void *recs, uint64_t n, uint32_t L,
+                         const uint32_t *pat_table, uint32_t n_table, const uint32_t *pat_m, uint32_t n_pats, uint32_t k,
+                         fz_assign *out);
+
 /* Test hook, no device needed: the sequence of position idx of a batch with the offsets `offs` — the lookup the kernels
  * run (fz_device.h: fz_segment_ragged, the per-tile bound included), on the host.  *j = its number, [*sa, *se) its bytes.
  * FZ_EINVAL for idx >= offs[n_seqs].  The tables are built on the first call for an offset array and kept for the next
