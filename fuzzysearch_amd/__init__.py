@@ -11,7 +11,8 @@ include/fzhip.h; this package is plain Python + ctypes (no PyTorch) and has NO C
 Extra, MI355X-specific surface: ``resident(sequence)`` uploads a long sequence to HBM once so that
 many patterns can be searched without re-crossing PCIe; ``find_near_matches_multi`` searches many subsequences in one
 sequence and ``find_near_matches_batch`` one subsequence in many sequences (``resident_batch`` keeps them in HBM), each
-in one pass; ``find_near_matches_multi_batch`` searches many subsequences in many sequences, a pass per group of up to 64.
+in one pass; ``find_near_matches_multi_batch`` searches many subsequences in many sequences, a pass per group of up to 64;
+``resident_records`` makes such a batch from a FASTQ file or a file of lines, split on the device.
 """
 import io
 
@@ -27,6 +28,7 @@ from .multi import find_near_matches_multi
 from .batch import find_near_matches_batch, resident_batch
 from .multi_batch import find_near_matches_multi_batch
 from .assign import find_best_matches_batch, BestMatches
+from .records import resident_records, RecordBatch
 
 __version__ = '0.1.0'
 
@@ -41,6 +43,8 @@ __all__ = [
     'Match',
     'resident',
     'resident_batch',
+    'resident_records',
+    'RecordBatch',
     'cache_info',
     'cache_clear',
     'UnsupportedSearch',

@@ -32,12 +32,19 @@ EXPORTED_SYMBOLS = (
     "fz_batch_upload", "fz_batch_search", "fz_debug_batch_segment",
     "fz_batch_search_multi",
     "fz_batch_assign", "fz_debug_assign_fold",
+    "fz_batch_upload_records", "fz_batch_tables", "fz_debug_batch_bytes", "fz_debug_records_split", "fz_debug_scan_items",
+    "fz_debug_records_ms",
 )
 
 
 class FzMatch(ctypes.Structure):
     _fields_ = [("start", ctypes.c_int64), ("end", ctypes.c_int64),
                 ("dist", ctypes.c_int32), ("block", ctypes.c_int32)]
+
+
+class FzRecordsInfo(ctypes.Structure):
+    _fields_ = [("n_lines", ctypes.c_uint64), ("n_seqs", ctypes.c_uint64), ("packed_bytes", ctypes.c_uint64),
+                ("bad_record", ctypes.c_uint64), ("bad_reason", ctypes.c_uint32)]
 
 
 class FzStats(ctypes.Structure):
@@ -183,6 +190,20 @@ def load_library():
             L.fz_debug_assign_fold.argtypes = [vp, u64, vp, u64, u32, vp, u32, vp, u32, u32, vp]
         L.fz_debug_batch_segment.restype = ci
         L.fz_debug_batch_segment.argtypes = [u64p, u64, u64, u64p, u64p, u64p]
+        if hasattr(L, "fz_batch_upload_records"):           # (absent from builds of earlier rounds named by FUZZYSEARCH_HIP_LIB for an A/B)
+            rip = ctypes.POINTER(FzRecordsInfo)
+            L.fz_batch_upload_records.restype = ci
+            L.fz_batch_upload_records.argtypes = [vp, vp, u64, u32, u32, u32, ctypes.POINTER(vp), rip]
+            L.fz_batch_tables.restype = ci
+            L.fz_batch_tables.argtypes = [vp, vp, vp]
+            L.fz_debug_batch_bytes.restype = ci
+            L.fz_debug_batch_bytes.argtypes = [vp, vp, u64]
+            L.fz_debug_records_split.restype = ci
+            L.fz_debug_records_split.argtypes = [vp, u64, u32, u32, u32, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), rip]
+            L.fz_debug_scan_items.restype = u32
+            L.fz_debug_scan_items.argtypes = []
+            L.fz_debug_records_ms.restype = ci
+            L.fz_debug_records_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
         L.fz_subs_ngrams_best.restype = ci
         L.fz_subs_ngrams_best.argtypes = [vp, vp, u8p, u32, u32, mpp, u64p]
         L.fz_generic_ngrams_consolidated.restype = ci
@@ -433,6 +454,53 @@ def batch_segment(offs, idx):
 _ASSIGN_DTYPE = None
 
 
+REC_FASTQ_CHECKS = 1                              # FZ_REC_FASTQ_CHECKS
+# format -> (lines per record, the sequence's line, flags) of fz_batch_upload_records
+RECORD_FORMATS = {'fastq': (4, 1, REC_FASTQ_CHECKS), 'lines': (1, 0, 0)}
+
+
+def scan_items():
+    """fz_debug_scan_items: the items one workgroup of the device's exclusive scan handles."""
+    return int(load_library().fz_debug_scan_items())
+
+
+def records_split(text, lines_per_record, sequence_line, flags):
+    """fz_debug_records_split (no device): the split of fz_batch_upload_records on the host, through the functions its
+    kernels run -> (src_starts, ends, packed bytes, info dict).  A malformed text raises ValueError as the upload does;
+    the exception carries the info dict as ``.info``."""
+    import numpy as np
+    L = load_library()
+    addr, n, keep = _buffer_address(text)
+    ps, pe, pp = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+    info = FzRecordsInfo()
+    rc = L.fz_debug_records_split(addr, n, lines_per_record, sequence_line, flags, ctypes.byref(ps), ctypes.byref(pe),
+                                  ctypes.byref(pp), ctypes.byref(info))
+    del keep
+    d = _records_info(info)
+    if rc != FZ_OK:
+        _raise_records(rc, d)
+    ns = d['n_seqs']
+    starts = np.ctypeslib.as_array(ctypes.cast(ps, ctypes.POINTER(ctypes.c_uint64)), shape=(ns,)).copy() if ns else np.zeros(0, np.uint64)
+    ends = np.ctypeslib.as_array(ctypes.cast(pe, ctypes.POINTER(ctypes.c_uint64)), shape=(ns,)).copy() if ns else np.zeros(0, np.uint64)
+    packed = ctypes.string_at(pp, d['packed_bytes'])
+    for p in (ps, pe, pp):
+        L.fz_free(p)
+    return starts, ends, packed, d
+
+
+def _records_info(info):
+    return {'n_lines': int(info.n_lines), 'n_seqs': int(info.n_seqs), 'packed_bytes': int(info.packed_bytes),
+            'bad_record': int(info.bad_record), 'bad_reason': int(info.bad_reason)}
+
+
+def _raise_records(rc, info):
+    try:
+        _raise(rc)
+    except ValueError as e:
+        e.info = info
+        raise
+
+
 def assign_dtype():
     """The numpy dtype of an fz_assign row (include/fzhip.h): pattern (-1: nothing matched), dist, tied, start, end."""
     global _ASSIGN_DTYPE
@@ -648,6 +716,49 @@ class Engine(object):
         seq = ResidentSequence(self, h, n)
         seq.n_seqs = len(offs) - 1
         return seq
+
+    def upload_records(self, text, lines_per_record=4, sequence_line=1, flags=REC_FASTQ_CHECKS):
+        """fz_batch_upload_records: `text` (bytes-like: a FASTQ file, a file of lines) is copied to the device once and split
+        there into a batch -> a ResidentSequence like upload_batch's, with `.n_seqs` and `.info` (n_lines, n_seqs,
+        packed_bytes).  A malformed text raises ValueError naming the record (`.info` on the exception: bad_record, bad_reason)."""
+        addr, n, keep = _buffer_address(text)
+        h = ctypes.c_void_p()
+        info = FzRecordsInfo()
+        with self._lock:
+            rc = self._lib.fz_batch_upload_records(self._h, addr, n, lines_per_record, sequence_line, flags, ctypes.byref(h),
+                                                   ctypes.byref(info))
+        del keep
+        d = _records_info(info)
+        if rc != FZ_OK:
+            _raise_records(rc, d)
+        seq = ResidentSequence(self, h, d['packed_bytes'])
+        seq.n_seqs = d['n_seqs']
+        seq.info = d
+        return seq
+
+    def batch_tables(self, batch):
+        """fz_batch_tables -> (src_starts, ends): numpy uint64 arrays of the batch's n_seqs sequences — where each one starts
+        in the text it was cut from (upload_batch: its offset in the packed bytes) and where it ends in the packed bytes."""
+        import numpy as np
+        starts = np.zeros(batch.n_seqs, dtype=np.uint64)
+        ends = np.zeros(batch.n_seqs, dtype=np.uint64)
+        with self._lock:
+            _check(self._lib.fz_batch_tables(batch._h, starts.ctypes.data, ends.ctypes.data))
+        return starts, ends
+
+    def batch_bytes(self, batch):
+        """fz_debug_batch_bytes: the packed bytes of a batch handle, back from the device."""
+        buf = ctypes.create_string_buffer(max(1, batch.nbytes))
+        with self._lock:
+            _check(self._lib.fz_debug_batch_bytes(batch._h, buf, batch.nbytes))
+        return buf.raw[:batch.nbytes]
+
+    def records_ms(self):
+        """fz_debug_records_ms: {h2d, kernels, ends_d2h, call} milliseconds of this engine's last upload_records."""
+        ms = (ctypes.c_double * 4)()
+        with self._lock:
+            _check(self._lib.fz_debug_records_ms(self._h, ms))
+        return {'h2d': ms[0], 'kernels': ms[1], 'ends_d2h': ms[2], 'call': ms[3]}
 
     def _batch_call(self, batch, mode, pattern, k, reduced):
         if type(pattern) is bytes:

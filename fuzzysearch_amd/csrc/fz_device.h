@@ -1359,3 +1359,87 @@ FZ_HD FzAssignRow fz_assign_row(uint64_t lo, uint32_t hi, const uint32_t *pm, ui
     o.end = o.start + fz_assign_key_len(lo, pm[p], k);
     return o;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Records (fz_batch_upload_records; fz_kernels.h: fz_rec_*_kernel): a text of lines becomes a batch on the device.
+// A line ends at a '\n' or, the last one, at the end of the text; one '\r' in front of that end is not content.  The
+// line table nl[] holds the positions of the n_nl newlines in ascending order; the text has n_nl lines, plus one when its
+// last byte is no newline.  Record r is the lines r * period .. r * period + period - 1 and its sequence is line
+// r * period + phase.  With FZ_REC_FASTQ_CHECKS (period 4, phase 1) a record is checked, and the smallest error key
+// (record << 8 | reason) of the text is the one reported:
+//     1 the line count is no multiple of 4 (record = n_lines / 4)      2 line 0 does not start with '@'
+//     3 line 2 does not start with '+'                                  4 line 3 is not as long as line 1
+#define FZ_REC_CHECKS 1u               // = FZ_REC_FASTQ_CHECKS (include/fzhip.h)
+#define FZ_REC_OK 0u
+#define FZ_REC_E_COUNT 1u
+#define FZ_REC_E_AT 2u
+#define FZ_REC_E_PLUS 3u
+#define FZ_REC_E_QUAL 4u
+#define FZ_REC_NO_ERROR 0xffffffffffffffffull
+
+// 0x80 in every byte of w that is a '\n' (exact: no borrow crosses a byte), so popcount = the newlines of the word.
+FZ_HD uint32_t fz_rec_nl_mask(uint32_t w) {
+    const uint32_t x = w ^ 0x0a0a0a0au;
+    return ~(((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x | 0x7f7f7f7fu);
+}
+
+FZ_HD uint64_t fz_rec_n_lines(const uint8_t *text, uint64_t n, uint64_t n_nl) { return n_nl + ((n && text[n - 1] != '\n') ? 1u : 0u); }
+
+// rank -> line: the content [start, end) of line i (i < fz_rec_n_lines), the '\r' in front of its end left out.
+struct FzRecLine { uint64_t start, end; };
+FZ_HD FzRecLine fz_rec_line(const uint8_t *text, uint64_t n, const uint64_t *nl, uint64_t n_nl, uint64_t i) {
+    FzRecLine l;
+    l.start = i ? nl[i - 1] + 1u : 0u;
+    l.end = i < n_nl ? nl[i] : n;
+    if (l.end > l.start && text[l.end - 1] == '\r') --l.end;
+    return l;
+}
+
+FZ_HD uint64_t fz_rec_err_key(uint64_t record, uint32_t reason) { return (record << 8) | reason; }
+FZ_HD uint64_t fz_rec_err_record(uint64_t key) { return key >> 8; }
+FZ_HD uint32_t fz_rec_err_reason(uint64_t key) { return (uint32_t)(key & 0xffu); }
+
+// How many sequences a text of n_lines lines holds: the records whose sequence line exists.
+FZ_HD uint64_t fz_rec_n_seqs(uint64_t n_lines, uint32_t period, uint32_t phase) {
+    return n_lines > phase ? (n_lines - phase + period - 1u) / period : 0u;
+}
+
+// record -> (start, len, verdict).  A record whose check lines do not all exist is not checked (FZ_REC_E_COUNT is the
+// text's, not a record's: fz_rec_count_key).
+struct FzRecOut { uint64_t start, len; uint32_t reason; };
+FZ_HD FzRecOut fz_rec_measure(const uint8_t *text, uint64_t n, const uint64_t *nl, uint64_t n_nl, uint64_t n_lines, uint32_t period,
+                              uint32_t phase, uint32_t flags, uint64_t r) {
+    FzRecOut o;
+    const uint64_t l0 = r * period;
+    const FzRecLine s = fz_rec_line(text, n, nl, n_nl, l0 + phase);
+    o.start = s.start; o.len = s.end - s.start; o.reason = FZ_REC_OK;
+    if ((flags & FZ_REC_CHECKS) && l0 + 3u < n_lines) {
+        const FzRecLine h = fz_rec_line(text, n, nl, n_nl, l0);
+        const FzRecLine p = fz_rec_line(text, n, nl, n_nl, l0 + 2u);
+        const FzRecLine q = fz_rec_line(text, n, nl, n_nl, l0 + 3u);
+        if (h.end == h.start || text[h.start] != '@') o.reason = FZ_REC_E_AT;
+        else if (p.end == p.start || text[p.start] != '+') o.reason = FZ_REC_E_PLUS;
+        else if (q.end - q.start != o.len) o.reason = FZ_REC_E_QUAL;
+    }
+    return o;
+}
+
+// The text's own error key (FZ_REC_NO_ERROR: none).
+FZ_HD uint64_t fz_rec_count_key(uint64_t n_lines, uint32_t period, uint32_t flags) {
+    return ((flags & FZ_REC_CHECKS) && n_lines % period) ? fz_rec_err_key(n_lines / period, FZ_REC_E_COUNT) : FZ_REC_NO_ERROR;
+}
+
+// Exclusive scan of u64 in workgroups of FZ_RSCAN_ITEMS items: reduce per workgroup, scan the sums (the same scan, a
+// level up), add them back.  fz_rscan_levels: the workgroup counts of the levels above `n` items, top last; -> their number.
+#define FZ_RSCAN_THREADS 256u
+#define FZ_RSCAN_PER_THREAD 4u
+#define FZ_RSCAN_ITEMS (FZ_RSCAN_THREADS * FZ_RSCAN_PER_THREAD)
+#define FZ_RSCAN_MAX_LEVELS 8
+FZ_HD int fz_rscan_levels(uint64_t n, uint64_t *blocks) {
+    int l = 0;
+    while (n > FZ_RSCAN_ITEMS && l < FZ_RSCAN_MAX_LEVELS) {
+        n = (n + FZ_RSCAN_ITEMS - 1u) / FZ_RSCAN_ITEMS;
+        blocks[l++] = n;
+    }
+    return l;
+}

@@ -2293,3 +2293,226 @@ __global__ __launch_bounds__(FZ_ASSIGN_THREADS) void fz_assign_finish_kernel(con
     for (uint64_t j = (uint64_t)blockIdx.x * FZ_ASSIGN_THREADS + threadIdx.x; j < n_seqs; j += stride)
         out[j] = fz_assign_row(lo[j], hi[j], pm, k);
 }
+
+// ---------------------------------------------------------------------------------------------
+// Records (fz_batch_upload_records; fz_device.h: fz_rec_*): a text of lines is split into a batch where it lies, in HBM.
+// Every step is a launch of its own on the context's stream and the launch boundaries are the only ordering between
+// workgroups: nothing here waits for another workgroup inside a launch.
+//
+//   fz_rec_count_kernel        one workgroup per 16 KiB tile: newlines of the tile (16-byte loads, popcount of the byte mask)
+//   fz_rec_scan_reduce_kernel  sum of FZ_RSCAN_ITEMS u64 per workgroup                  } exclusive scan of u64, any length:
+//   fz_rec_scan_down_kernel    exclusive scan inside the workgroup + the scanned sum     } reduce, scan the sums, add back
+//   fz_rec_lines_kernel        every newline's position at its global rank (tile base + rank inside the tile)
+//   fz_rec_measure_kernel      one lane per record: start and length of its sequence, the FASTQ checks, the longest length
+//   fz_rec_gather_kernel       packed[] by 16-byte pieces of the DESTINATION: a piece inside one sequence is one unaligned
+//                              16-byte load and one aligned 16-byte store, whatever the sequence's length or alignment; a
+//                              piece across a sequence end (1 in 9 for 150-byte reads) goes byte by byte
+#define FZ_REC_THREADS 256u
+
+// Exclusive scan of one value per thread over the FZ_REC_THREADS threads of a workgroup; total = the workgroup's sum.
+__device__ __forceinline__ uint64_t fz_rec_block_scan(uint64_t v, uint64_t *wsum, uint64_t &total) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    unsigned long long inc = v;
+#pragma unroll
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+        const unsigned long long o = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += o;
+    }
+    if (lane == 63u) wsum[wave] = inc;
+    __syncthreads();
+    uint64_t base = 0;
+    total = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < FZ_REC_THREADS / 64u; ++w) {
+        const uint64_t s = wsum[w];
+        if (w < wave) base += s;
+        total += s;
+    }
+    __syncthreads();                                       // wsum is free for the next call
+    return base + inc - v;
+}
+
+__device__ __forceinline__ uint32_t fz_rec_nl_count(const uint4 &v) {
+    return (uint32_t)(__builtin_popcount(fz_rec_nl_mask(v.x)) + __builtin_popcount(fz_rec_nl_mask(v.y)) +
+                      __builtin_popcount(fz_rec_nl_mask(v.z)) + __builtin_popcount(fz_rec_nl_mask(v.w)));
+}
+
+// raw: whole tiles (the bytes behind the text are zero).  counts[t] = newlines of tile t.
+__global__ __launch_bounds__(FZ_REC_THREADS) void fz_rec_count_kernel(const uint8_t *__restrict__ raw, uint64_t ntiles,
+                                                                      uint64_t *__restrict__ counts) {
+    __shared__ uint32_t acc;
+    for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        if (threadIdx.x == 0) acc = 0;
+        __syncthreads();
+        const uint4 *src = reinterpret_cast<const uint4 *>(raw + t * (uint64_t)FZ_TILE_BYTES);
+        uint32_t c = 0;
+#pragma unroll
+        for (uint32_t q = 0; q < FZ_TILE_BYTES / 16u / FZ_REC_THREADS; ++q) c += fz_rec_nl_count(src[q * FZ_REC_THREADS + threadIdx.x]);
+#pragma unroll
+        for (uint32_t d = 32; d; d >>= 1) c += __shfl_xor(c, d, 64);
+        if ((threadIdx.x & 63u) == 0) atomicAdd(&acc, c);
+        __syncthreads();
+        if (threadIdx.x == 0) counts[t] = acc;
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(FZ_RSCAN_THREADS) void fz_rec_scan_reduce_kernel(const uint64_t *__restrict__ in, uint64_t n,
+                                                                             uint64_t *__restrict__ sums) {
+    __shared__ uint64_t wsum[FZ_RSCAN_THREADS / 64u];
+    const uint64_t nb = (n + FZ_RSCAN_ITEMS - 1u) / FZ_RSCAN_ITEMS;
+    for (uint64_t b = blockIdx.x; b < nb; b += gridDim.x) {
+        const uint64_t i0 = b * FZ_RSCAN_ITEMS + threadIdx.x * FZ_RSCAN_PER_THREAD;
+        uint64_t s = 0;
+#pragma unroll
+        for (uint32_t q = 0; q < FZ_RSCAN_PER_THREAD; ++q) s += i0 + q < n ? in[i0 + q] : 0;
+        uint64_t total;
+        (void)fz_rec_block_scan(s, wsum, total);
+        if (threadIdx.x == 0) sums[b] = total;
+    }
+}
+
+// In place.  sums: the workgroups' sums after their own exclusive scan (null: one workgroup, nothing to add).
+__global__ __launch_bounds__(FZ_RSCAN_THREADS) void fz_rec_scan_down_kernel(uint64_t *__restrict__ data, uint64_t n,
+                                                                           const uint64_t *__restrict__ sums) {
+    __shared__ uint64_t wsum[FZ_RSCAN_THREADS / 64u];
+    const uint64_t nb = (n + FZ_RSCAN_ITEMS - 1u) / FZ_RSCAN_ITEMS;
+    for (uint64_t b = blockIdx.x; b < nb; b += gridDim.x) {
+        const uint64_t i0 = b * FZ_RSCAN_ITEMS + threadIdx.x * FZ_RSCAN_PER_THREAD;
+        uint64_t x0 = i0 < n ? data[i0] : 0, x1 = i0 + 1u < n ? data[i0 + 1u] : 0, x2 = i0 + 2u < n ? data[i0 + 2u] : 0,
+                 x3 = i0 + 3u < n ? data[i0 + 3u] : 0;
+        static_assert(FZ_RSCAN_PER_THREAD == 4u, "four items per thread");
+        uint64_t total;
+        uint64_t run = fz_rec_block_scan(x0 + x1 + x2 + x3, wsum, total) + (sums ? sums[b] : 0);
+        if (i0 < n) data[i0] = run;
+        run += x0;
+        if (i0 + 1u < n) data[i0 + 1u] = run;
+        run += x1;
+        if (i0 + 2u < n) data[i0 + 2u] = run;
+        run += x2;
+        if (i0 + 3u < n) data[i0 + 3u] = run;
+    }
+}
+
+__device__ __forceinline__ void fz_rec_emit_word(uint32_t w, uint64_t pos, uint64_t *__restrict__ nl, uint64_t &at) {
+    uint32_t m = fz_rec_nl_mask(w);
+    while (m) {
+        nl[at++] = pos + ((uint32_t)__builtin_ctz(m) >> 3);
+        m &= m - 1u;
+    }
+}
+
+// tile_base[t] = newlines in front of tile t (the exclusive scan of fz_rec_count_kernel's counts).  The pieces of a tile
+// are taken in the order of the count kernel's loads (piece q * 256 + thread), which is the order of their positions.
+__global__ __launch_bounds__(FZ_REC_THREADS) void fz_rec_lines_kernel(const uint8_t *__restrict__ raw, uint64_t ntiles,
+                                                                      const uint64_t *__restrict__ tile_base, uint64_t *__restrict__ nl) {
+    __shared__ uint64_t wsum[FZ_REC_THREADS / 64u];
+    constexpr uint32_t Q = FZ_TILE_BYTES / 16u / FZ_REC_THREADS;
+    static_assert(Q == 4u, "four 16-bit counters in one scanned word (a counter holds at most 16 * 256 * 4)");
+    for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const uint64_t tpos = t * (uint64_t)FZ_TILE_BYTES;
+        const uint4 *src = reinterpret_cast<const uint4 *>(raw + tpos);
+        const uint4 v0 = src[threadIdx.x], v1 = src[FZ_REC_THREADS + threadIdx.x], v2 = src[2u * FZ_REC_THREADS + threadIdx.x],
+                    v3 = src[3u * FZ_REC_THREADS + threadIdx.x];
+        const uint64_t mine = (uint64_t)fz_rec_nl_count(v0) | ((uint64_t)fz_rec_nl_count(v1) << 16) | ((uint64_t)fz_rec_nl_count(v2) << 32) |
+                              ((uint64_t)fz_rec_nl_count(v3) << 48);
+        uint64_t total;
+        const uint64_t ex = fz_rec_block_scan(mine, wsum, total);
+        if (total == 0) continue;                          // (uniform over the workgroup)
+        const uint64_t base = tile_base[t];
+        const uint64_t t0 = total & 0xffffu, t1 = (total >> 16) & 0xffffu, t2 = (total >> 32) & 0xffffu;
+        uint64_t at;
+        uint64_t pos = tpos + (uint64_t)threadIdx.x * 16u;
+        at = base + (ex & 0xffffu);
+        fz_rec_emit_word(v0.x, pos, nl, at); fz_rec_emit_word(v0.y, pos + 4u, nl, at);
+        fz_rec_emit_word(v0.z, pos + 8u, nl, at); fz_rec_emit_word(v0.w, pos + 12u, nl, at);
+        pos += FZ_REC_THREADS * 16u;
+        at = base + t0 + ((ex >> 16) & 0xffffu);
+        fz_rec_emit_word(v1.x, pos, nl, at); fz_rec_emit_word(v1.y, pos + 4u, nl, at);
+        fz_rec_emit_word(v1.z, pos + 8u, nl, at); fz_rec_emit_word(v1.w, pos + 12u, nl, at);
+        pos += FZ_REC_THREADS * 16u;
+        at = base + t0 + t1 + ((ex >> 32) & 0xffffu);
+        fz_rec_emit_word(v2.x, pos, nl, at); fz_rec_emit_word(v2.y, pos + 4u, nl, at);
+        fz_rec_emit_word(v2.z, pos + 8u, nl, at); fz_rec_emit_word(v2.w, pos + 12u, nl, at);
+        pos += FZ_REC_THREADS * 16u;
+        at = base + t0 + t1 + t2 + ((ex >> 48) & 0xffffu);
+        fz_rec_emit_word(v3.x, pos, nl, at); fz_rec_emit_word(v3.y, pos + 4u, nl, at);
+        fz_rec_emit_word(v3.z, pos + 8u, nl, at); fz_rec_emit_word(v3.w, pos + 12u, nl, at);
+    }
+}
+
+// lens has n_seqs + 1 entries (the last one 0: its exclusive scan is the sequences' starts in packed[] and, one entry on,
+// their ends).  info[0] = the smallest error key (starts at FZ_REC_NO_ERROR), info[1] = the longest sequence (starts at 0).
+__global__ __launch_bounds__(FZ_REC_THREADS) void fz_rec_measure_kernel(const uint8_t *__restrict__ raw, uint64_t n,
+                                                                        const uint64_t *__restrict__ nl, uint64_t n_nl, uint64_t n_lines,
+                                                                        uint32_t period, uint32_t phase, uint32_t flags, uint64_t n_seqs,
+                                                                        uint64_t *__restrict__ starts, uint64_t *__restrict__ lens,
+                                                                        unsigned long long *__restrict__ info) {
+    const uint64_t stride = (uint64_t)gridDim.x * FZ_REC_THREADS;
+    unsigned long long longest = 0;
+    for (uint64_t r = (uint64_t)blockIdx.x * FZ_REC_THREADS + threadIdx.x; r < n_seqs; r += stride) {
+        const FzRecOut o = fz_rec_measure(raw, n, nl, n_nl, n_lines, period, phase, flags, r);
+        starts[r] = o.start;
+        lens[r] = o.len;
+        longest = o.len > longest ? o.len : longest;
+        if (o.reason != FZ_REC_OK) (void)atomicMin(&info[0], (unsigned long long)fz_rec_err_key(r, o.reason));
+    }
+#pragma unroll
+    for (uint32_t d = 32; d; d >>= 1) {
+        const unsigned long long o = __shfl_xor(longest, d, 64);
+        longest = o > longest ? o : longest;
+    }
+    if ((threadIdx.x & 63u) == 0 && longest > __hip_atomic_load(&info[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+        (void)atomicMax(&info[1], longest);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        lens[n_seqs] = 0;
+        const uint64_t key = fz_rec_count_key(n_lines, period, flags);
+        if (key != FZ_REC_NO_ERROR) (void)atomicMin(&info[0], (unsigned long long)key);
+    }
+}
+
+// at[j] = where sequence j starts in packed[] (n_seqs + 1 entries: at[j + 1] = its end, at[n_seqs] = total > 0).
+__global__ __launch_bounds__(FZ_REC_THREADS) void fz_rec_gather_kernel(const uint8_t *__restrict__ raw, const uint64_t *__restrict__ starts,
+                                                                       const uint64_t *__restrict__ at, uint64_t n_seqs, uint64_t total,
+                                                                       uint8_t *__restrict__ packed) {
+    __shared__ uint64_t bound[2];
+    const uint64_t *ends = at + 1;
+    const uint64_t ntiles = (total + FZ_TILE_BYTES - 1u) / FZ_TILE_BYTES;
+    for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const uint64_t p0 = t * (uint64_t)FZ_TILE_BYTES;
+        const uint64_t p1 = p0 + FZ_TILE_BYTES < total ? p0 + FZ_TILE_BYTES : total;
+        if (threadIdx.x < 2u) {                            // the sequences of the tile's first and last byte
+            const uint64_t target = threadIdx.x ? p1 - 1u : p0;
+            uint64_t lo = 0, hi = n_seqs - 1u;
+            while (lo < hi) {                              // first j with ends[j] > target (target < total = ends[n_seqs - 1])
+                const uint64_t mid = lo + ((hi - lo) >> 1);
+                if (ends[mid] > target) hi = mid; else lo = mid + 1u;
+            }
+            bound[threadIdx.x] = lo;
+        }
+        __syncthreads();
+        const uint64_t jlo = bound[0], jhi = bound[1];
+        for (uint32_t q = 0; q < FZ_TILE_BYTES / 16u / FZ_REC_THREADS; ++q) {
+            uint64_t p = p0 + (uint64_t)(q * FZ_REC_THREADS + threadIdx.x) * 16u;
+            if (p >= p1) continue;
+            uint64_t lo = jlo, hi = jhi;
+            while (lo < hi) {
+                const uint64_t mid = lo + ((hi - lo) >> 1);
+                if (ends[mid] > p) hi = mid; else lo = mid + 1u;
+            }
+            uint64_t j = lo;
+            if (p + 16u <= ends[j]) {                      // the piece lies inside sequence j
+                uint4 v;
+                __builtin_memcpy(&v, raw + starts[j] + (p - at[j]), 16);
+                *reinterpret_cast<uint4 *>(packed + p) = v;
+            } else {
+                const uint64_t pe = p + 16u < total ? p + 16u : total;
+                for (; p < pe; ++p) {
+                    while (ends[j] <= p) ++j;              // (p < total: such a j exists)
+                    packed[p] = raw[starts[j] + (p - at[j])];
+                }
+            }
+        }
+        __syncthreads();
+    }
+}

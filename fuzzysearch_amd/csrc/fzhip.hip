@@ -181,6 +181,7 @@ struct DevState {
     // hipMalloc + hipFree per chunk would dominate)
     uint8_t *spare_alloc = nullptr;
     uint64_t spare_bytes = 0;
+    hipEvent_t rec_ev[8] = {};                   // fz_batch_upload_records: the spans of its copy and kernels (created on first use)
     uint64_t first_copy = 512;                   // records fetched with the header (tracks the last count)
     bool header_zeroed = false;                  // the counters were already zeroed after the last D2H copy
     bool verify_launched = false;                // the last enqueue ran fz_verify_kernel (ev[2] recorded)
@@ -421,6 +422,7 @@ struct fz_ctx {
     // RCCL: number of ranks of the communicator this context joined (0: none) and whether its Levenshtein n-gram
     // searches are collective (every rank gets the merged global stream)
     bool any_found = false;                      // result of the last has_near_match_* (fz_*_any) search
+    double rec_ms[4] = {0, 0, 0, 0};             // fz_debug_records_ms: the last fz_batch_upload_records
     bool batch_call = false;                     // inside fz_batch_search: the one caller a batch handle is valid for (validate)
     // sharded searches: where every shard's (rank's) records end in the collected vector, and the shards in ascending
     // order of the index range they own (emit_matches orders shard by shard)
@@ -465,6 +467,10 @@ struct fz_seq {
     uint64_t *d_ends = nullptr;
     uint32_t *d_first = nullptr;
     uint64_t max_seq_len = 0;                    // the longest sequence (fz_batch_assign: local starts are 32-bit key fields)
+    // fz_batch_upload_records: d_ends is the second entry of the scanned length table (d_ends_base, the allocation), and
+    // the sequences' offsets in the text they were cut from stay on the device until somebody asks (fz_batch_tables)
+    uint64_t *d_ends_base = nullptr;
+    uint64_t *d_src_starts = nullptr;
 };
 
 namespace {
@@ -2319,6 +2325,7 @@ static void devstate_destroy(DevState &d) {
     if (d.d_hits) (void)hipFree(d.d_hits);
     if (d.d_out) (void)hipFree(d.d_out);
     if (d.spare_alloc) (void)hipFree(d.spare_alloc);
+    for (auto &ev : d.rec_ev) if (ev) (void)hipEventDestroy(ev);
     if (d.h_stage) (void)hipHostFree(d.h_stage);
     if (d.other.h_stage) (void)hipHostFree(d.other.h_stage);
     for (auto &ev : d.other.ev) if (ev) (void)hipEventDestroy(ev);
@@ -2420,7 +2427,9 @@ void fz_destroy(fz_ctx *ctx) {
     delete ctx;
 }
 
-static int upload_one(fz_ctx *ctx, int dev_index, const uint8_t *host_buf, const FzGeom &geom, Shard &sh) {
+// A shard's buffer: FZ_PAD_FRONT zero bytes, the body rounded up to whole tiles with everything behind geom.buf_len zeroed,
+// FZ_PAD_BACK zero bytes (the scan kernels rely on the guard bytes).  The body's bytes are the caller's to write, on d.stream.
+static int alloc_one(fz_ctx *ctx, int dev_index, const FzGeom &geom, Shard &sh) {
     DevState &d = ctx->devs[dev_index];
     HIP_TRY(hipSetDevice(d.device));
     const uint64_t tiles = (geom.buf_len + FZ_TILE_BYTES - 1) / FZ_TILE_BYTES;
@@ -2439,11 +2448,16 @@ static int upload_one(fz_ctx *ctx, int dev_index, const uint8_t *host_buf, const
     sh.d_buf = sh.d_alloc + FZ_PAD_FRONT;
     HIP_TRY(hipMemsetAsync(sh.d_alloc, 0, FZ_PAD_FRONT, d.stream));
     HIP_TRY(hipMemsetAsync(sh.d_buf + geom.buf_len, 0, sh.alloc_bytes - FZ_PAD_FRONT - geom.buf_len, d.stream));
+    return FZ_OK;
+}
+
+static int upload_one(fz_ctx *ctx, int dev_index, const uint8_t *host_buf, const FzGeom &geom, Shard &sh) {
+    int rc = alloc_one(ctx, dev_index, geom, sh);
+    if (rc) return rc;
+    DevState &d = ctx->devs[dev_index];
     if (geom.buf_len) HIP_TRY(hipMemcpyAsync(sh.d_buf, host_buf, geom.buf_len, hipMemcpyHostToDevice, d.stream));
     // grow the hit list with the sequence: n-gram hits on 4-letter text run at ~G * n / 4^L
-    int rc = ensure_hits(d, std::max<uint64_t>(1u << 20, geom.buf_len / 64));
-    if (rc) return rc;
-    return FZ_OK;
+    return ensure_hits(d, std::max<uint64_t>(1u << 20, geom.buf_len / 64));
 }
 
 int fz_seq_upload(fz_ctx *ctx, const uint8_t *host, uint64_t n, fz_seq **out) {
@@ -2587,10 +2601,15 @@ void fz_seq_release(fz_seq *seq) {
             }
         }
     }
-    if (seq->ctx && (seq->d_ends || seq->d_first)) {
+    if (seq->ctx && (seq->d_ends || seq->d_first || seq->d_ends_base)) {
         (void)hipSetDevice(seq->ctx->devs[0].device);
-        if (seq->d_ends) (void)hipFree(seq->d_ends);
+        if (seq->d_ends_base) (void)hipFree(seq->d_ends_base);
+        else if (seq->d_ends) (void)hipFree(seq->d_ends);
         if (seq->d_first) (void)hipFree(seq->d_first);
+    }
+    if (seq->ctx && seq->d_src_starts) {
+        (void)hipSetDevice(seq->ctx->devs[0].device);
+        (void)hipFree(seq->d_src_starts);
     }
     delete seq;
 }
@@ -2674,6 +2693,321 @@ int fz_debug_batch_segment(const uint64_t *offs, uint64_t n_seqs, uint64_t idx, 
     const FzSeg sg = fz_segment_ragged(t, n, idx);
     if (!sg.ok) return fail(FZ_EINVAL, "position outside the batch");
     *j = sg.j; *sa = sg.sa; *se = sg.se;
+    return FZ_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Records (fz_batch_upload_records): the text crosses PCIe once and is split where it lies (fz_kernels.h: fz_rec_*_kernel).
+
+namespace {
+const char *rec_reason_text(uint32_t reason) {
+    switch (reason) {
+    case FZ_REC_E_COUNT: return "the number of lines is not a multiple of 4 (truncated record)";
+    case FZ_REC_E_AT: return "the header line does not start with '@'";
+    case FZ_REC_E_PLUS: return "the separator line does not start with '+'";
+    case FZ_REC_E_QUAL: return "the quality line is not as long as the sequence line";
+    }
+    return "malformed";
+}
+
+int rec_check_args(const uint8_t *text, uint64_t n, uint32_t period, uint32_t phase, uint32_t flags) {
+    if (!text && n) return fail(FZ_EINVAL, "null argument");
+    if (flags & ~FZ_REC_FASTQ_CHECKS) return fail(FZ_EINVAL, "unknown record flags");
+    if (period == 0 || phase >= period) return fail(FZ_EINVAL, "sequence_line must be smaller than lines_per_record");
+    if ((flags & FZ_REC_FASTQ_CHECKS) && (period != 4 || phase != 1)) return fail(FZ_EINVAL, "the FASTQ checks take 4 lines per record, the sequence on line 1");
+    if (n >= (1ull << FZ_IDX_BITS)) return fail(FZ_EUNSUPPORTED, "sequence too long");
+    return FZ_OK;
+}
+
+// FASTQ: trailing empty lines are no lines.  -> the length of the text without them.
+uint64_t rec_trim(const uint8_t *text, uint64_t n) {
+    for (;;) {
+        if (n == 0) return 0;
+        if (text[n - 1] == '\n') {
+            if (n == 1 || text[n - 2] == '\n') { n -= 1; continue; }
+            if (text[n - 2] == '\r' && (n == 2 || text[n - 3] == '\n')) { n -= 2; continue; }
+            return n;
+        }
+        if (text[n - 1] == '\r' && (n == 1 || text[n - 2] == '\n')) { n -= 1; continue; }
+        return n;
+    }
+}
+
+int rec_report(const char *what, uint64_t key, fz_records_info *info) {
+    if (info) { info->bad_record = fz_rec_err_record(key); info->bad_reason = fz_rec_err_reason(key); }
+    return fail(FZ_EINVAL, "%s: record %llu: %s", what, (unsigned long long)fz_rec_err_record(key), rec_reason_text(fz_rec_err_reason(key)));
+}
+
+uint32_t rec_grid(const DevState &d, uint64_t items) { return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(items, (uint64_t)d.n_cus * 8)); }
+
+// Exclusive scan of data[0 .. n) in place on d.stream; scratch holds rec_scan_scratch(n) u64.
+uint64_t rec_scan_scratch(uint64_t n) {
+    uint64_t blocks[FZ_RSCAN_MAX_LEVELS], total = 0;
+    const int levels = fz_rscan_levels(n, blocks);
+    for (int l = 0; l < levels; ++l) total += blocks[l];
+    return total;
+}
+
+void rec_scan(DevState &d, uint64_t *data, uint64_t n, uint64_t *scratch) {
+    uint64_t blocks[FZ_RSCAN_MAX_LEVELS];
+    const int levels = fz_rscan_levels(n, blocks);
+    uint64_t *at[FZ_RSCAN_MAX_LEVELS + 1];
+    uint64_t cnt[FZ_RSCAN_MAX_LEVELS + 1];
+    at[0] = data; cnt[0] = n;
+    for (int l = 0; l < levels; ++l) { at[l + 1] = l ? at[l] + blocks[l - 1] : scratch; cnt[l + 1] = blocks[l]; }
+    for (int l = 0; l < levels; ++l)                      // up: every level's workgroup sums
+        hipLaunchKernelGGL(fz_rec_scan_reduce_kernel, dim3(rec_grid(d, cnt[l + 1])), dim3(FZ_RSCAN_THREADS), 0, d.stream, at[l], cnt[l], at[l + 1]);
+    for (int l = levels; l >= 0; --l)                     // down: the top level is one workgroup
+        hipLaunchKernelGGL(fz_rec_scan_down_kernel, dim3(rec_grid(d, (cnt[l] + FZ_RSCAN_ITEMS - 1) / FZ_RSCAN_ITEMS)), dim3(FZ_RSCAN_THREADS), 0,
+                           d.stream, at[l], cnt[l], l < levels ? at[l + 1] : (uint64_t *)nullptr);
+}
+
+struct RecTmp {                                           // the call's transient device memory
+    uint8_t *raw = nullptr;
+    uint64_t *counts = nullptr, *scratch = nullptr, *nl = nullptr, *starts = nullptr, *at = nullptr;
+    unsigned long long *info = nullptr;
+    ~RecTmp() {
+        for (void *p : {(void *)raw, (void *)counts, (void *)scratch, (void *)nl, (void *)starts, (void *)at, (void *)info})
+            if (p) (void)hipFree(p);
+    }
+};
+
+int rec_malloc_bytes(void **p, uint64_t bytes) {
+    hipError_t e = hipMalloc(p, bytes);
+    if (e != hipSuccess) { *p = nullptr; return fail(e == hipErrorOutOfMemory ? FZ_ENOMEM : FZ_EDEVICE, "records: %s", hipGetErrorString(e)); }
+    return FZ_OK;
+}
+#define rec_malloc(pp, count) rec_malloc_bytes(reinterpret_cast<void **>(pp), std::max<uint64_t>(1, (count)) * sizeof(**(pp)))
+
+double rec_span(hipEvent_t a, hipEvent_t b) {
+    float ms = 0;
+    return hipEventElapsedTime(&ms, a, b) == hipSuccess ? (double)ms : 0.0;
+}
+}  // namespace
+
+int fz_batch_upload_records(fz_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t lines_per_record, uint32_t sequence_line,
+                            uint32_t flags, fz_seq **out, fz_records_info *info) {
+    if (!ctx || !out) return fail(FZ_EINVAL, "null argument");
+    *out = nullptr;
+    if (info) *info = fz_records_info{};
+    int rc = rec_check_args(text, n, lines_per_record, sequence_line, flags);
+    if (rc) return rc;
+    if (ctx->devs.size() != 1 || ctx->snapshot || comm_multi_process(ctx))
+        return fail(FZ_EUNSUPPORTED, "batches are searched by single-device, non-collective contexts");
+    if (ctx->npend || ctx->stream_inflight) return fail(FZ_EINVAL, "a search of this context is in flight");
+    const auto t_call = std::chrono::steady_clock::now();
+    const char *what = (flags & FZ_REC_FASTQ_CHECKS) ? "fastq" : "lines";
+    if (flags & FZ_REC_FASTQ_CHECKS) n = rec_trim(text, n);
+    DevState &d = ctx->devs[0];
+    HIP_TRY(hipSetDevice(d.device));
+    const bool timed = ctx->timing;
+    if (timed) for (auto &ev : d.rec_ev) if (!ev) HIP_TRY(hipEventCreate(&ev));
+    auto mark = [&](int i) { if (timed) (void)hipEventRecord(d.rec_ev[i], d.stream); };
+    RecTmp tmp;
+    const uint64_t ntiles = (n + FZ_TILE_BYTES - 1) / FZ_TILE_BYTES;
+    uint64_t n_nl = 0;
+    // 1. the text, whole tiles (zeros behind it are no newlines); newlines per tile; their exclusive scan, the total behind it
+    mark(0);
+    if (n) {
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&tmp.raw), ntiles * FZ_TILE_BYTES));
+        if (ntiles * FZ_TILE_BYTES > n) HIP_TRY(hipMemsetAsync(tmp.raw + n, 0, ntiles * FZ_TILE_BYTES - n, d.stream));
+        HIP_TRY(hipMemcpyAsync(tmp.raw, text, n, hipMemcpyHostToDevice, d.stream));
+    }
+    mark(1);
+    if (n) {
+        if ((rc = rec_malloc(&tmp.counts, ntiles + 1))) return rc;
+        if ((rc = rec_malloc(&tmp.scratch, rec_scan_scratch(ntiles + 1)))) return rc;
+        HIP_TRY(hipMemsetAsync(tmp.counts + ntiles, 0, sizeof(uint64_t), d.stream));
+        hipLaunchKernelGGL(fz_rec_count_kernel, dim3(rec_grid(d, ntiles)), dim3(FZ_REC_THREADS), 0, d.stream, tmp.raw, ntiles, tmp.counts);
+        rec_scan(d, tmp.counts, ntiles + 1, tmp.scratch);
+    }
+    mark(2);
+    if (n) {
+        HIP_TRY(hipMemcpyAsync(&n_nl, tmp.counts + ntiles, sizeof(uint64_t), hipMemcpyDeviceToHost, d.stream));
+        HIP_TRY(hipStreamSynchronize(d.stream));
+        if (n_nl > n) return fail(FZ_EDEVICE, "records: the newline count is outside the text");
+    }
+    const uint64_t n_lines = fz_rec_n_lines(text, n, n_nl);
+    const uint64_t n_seqs = fz_rec_n_seqs(n_lines, lines_per_record, sequence_line);
+    if (info) { info->n_lines = n_lines; info->n_seqs = n_seqs; }
+    if (n_seqs >= (1ull << 32)) return fail(FZ_EUNSUPPORTED, "more than 2^32 - 1 sequences in a batch");
+    // 2. the line table; one lane per record; the scan of the lengths
+    uint64_t key = fz_rec_count_key(n_lines, lines_per_record, flags), total = 0, longest = 0;
+    mark(3);
+    if (n_seqs) {
+        if ((rc = rec_malloc(&tmp.nl, n_nl))) return rc;
+        if ((rc = rec_malloc(&tmp.starts, n_seqs))) return rc;
+        if ((rc = rec_malloc(&tmp.at, n_seqs + 1))) return rc;
+        if ((rc = rec_malloc(&tmp.info, 2))) return rc;
+        if (rec_scan_scratch(n_seqs + 1) > rec_scan_scratch(ntiles + 1)) {
+            (void)hipFree(tmp.scratch);
+            tmp.scratch = nullptr;
+            if ((rc = rec_malloc(&tmp.scratch, rec_scan_scratch(n_seqs + 1)))) return rc;
+        }
+        HIP_TRY(hipMemsetAsync(tmp.info, 0xff, sizeof(uint64_t), d.stream));
+        HIP_TRY(hipMemsetAsync(tmp.info + 1, 0, sizeof(uint64_t), d.stream));
+        if (n_nl) hipLaunchKernelGGL(fz_rec_lines_kernel, dim3(rec_grid(d, ntiles)), dim3(FZ_REC_THREADS), 0, d.stream, tmp.raw, ntiles, tmp.counts, tmp.nl);
+        hipLaunchKernelGGL(fz_rec_measure_kernel, dim3(rec_grid(d, (n_seqs + FZ_REC_THREADS - 1) / FZ_REC_THREADS)), dim3(FZ_REC_THREADS), 0, d.stream,
+                           tmp.raw, n, tmp.nl, n_nl, n_lines, lines_per_record, sequence_line, flags, n_seqs, tmp.starts, tmp.at, tmp.info);
+        rec_scan(d, tmp.at, n_seqs + 1, tmp.scratch);
+    }
+    mark(4);
+    if (n_seqs) {
+        unsigned long long got[2] = {0, 0};
+        HIP_TRY(hipMemcpyAsync(got, tmp.info, sizeof(got), hipMemcpyDeviceToHost, d.stream));
+        HIP_TRY(hipMemcpyAsync(&total, tmp.at + n_seqs, sizeof(uint64_t), hipMemcpyDeviceToHost, d.stream));
+        HIP_TRY(hipStreamSynchronize(d.stream));
+        key = got[0];
+        longest = got[1];
+        if (total > n || longest > total) return fail(FZ_EDEVICE, "records: the packed length is outside the text");
+    }
+    if (key != FZ_REC_NO_ERROR) return rec_report(what, key, info);
+    if (info) info->packed_bytes = total;
+    // 3. the handle of fz_batch_upload, its bytes gathered on the device
+    fz_seq *seq = new (std::nothrow) fz_seq();
+    if (!seq) return fail(FZ_ENOMEM, "out of memory");
+    seq->ctx = ctx;
+    seq->n = total;
+    seq->is_batch = true;
+    seq->n_seqs = n_seqs;
+    seq->max_seq_len = longest;
+    FzGeom g{};
+    g.n = total;
+    g.buf_off = 0;
+    g.buf_len = total;
+    g.own_lo = 0;
+    g.own_hi = total;
+    seq->shards.emplace_back();
+    rc = alloc_one(ctx, 0, g, seq->shards.back());
+    mark(5);
+    if (rc == FZ_OK && total)
+        hipLaunchKernelGGL(fz_rec_gather_kernel, dim3(rec_grid(d, (total + FZ_TILE_BYTES - 1) / FZ_TILE_BYTES)), dim3(FZ_REC_THREADS), 0, d.stream,
+                           tmp.raw, tmp.starts, tmp.at, n_seqs, total, seq->shards.back().d_buf);
+    mark(6);
+    if (rc == FZ_OK) rc = ensure_hits(d, std::max<uint64_t>(1u << 20, total / 64));
+    double d2h_ms = 0;
+    std::vector<uint32_t> first;
+    if (rc == FZ_OK && n_seqs) {
+        const auto t0 = std::chrono::steady_clock::now();
+        seq->ends.resize(n_seqs);
+        hipError_t e = hipMemcpyAsync(seq->ends.data(), tmp.at + 1, n_seqs * sizeof(uint64_t), hipMemcpyDeviceToHost, d.stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
+        d2h_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        const uint64_t nt = (total + FZ_TILE_BYTES - 1) / FZ_TILE_BYTES;
+        if (e == hipSuccess) {
+            first.resize(nt + 1);
+            fz_ragged_first(seq->ends.data(), n_seqs, nt, first.data());
+            e = hipMalloc(reinterpret_cast<void **>(&seq->d_first), first.size() * sizeof(uint32_t));
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(seq->d_first, first.data(), first.size() * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream);
+        if (e != hipSuccess) rc = fail(e == hipErrorOutOfMemory ? FZ_ENOMEM : FZ_EDEVICE, "batch tables: %s", hipGetErrorString(e));
+        seq->d_ends_base = tmp.at;                         // the handle owns the scanned table and the text offsets from here on
+        seq->d_ends = tmp.at + 1;
+        seq->d_src_starts = tmp.starts;
+        tmp.at = nullptr;
+        tmp.starts = nullptr;
+        FzGeom &sg = seq->shards.back().geom;
+        sg.seg_org = reinterpret_cast<uint64_t>(seq->d_ends);
+        sg.seg_j0 = reinterpret_cast<uint64_t>(seq->d_first);
+        sg.seg_j1 = n_seqs;
+    }
+    if (rc == FZ_OK) {
+        hipError_t e = hipStreamSynchronize(d.stream);    // the text and first[] are only borrowed; the transient buffers go
+        if (e != hipSuccess) rc = fail(FZ_EDEVICE, "upload failed: %s", hipGetErrorString(e));
+    }
+    if (rc) { fz_seq_release(seq); return rc; }
+    if (timed) {
+        ctx->rec_ms[0] = rec_span(d.rec_ev[0], d.rec_ev[1]);
+        ctx->rec_ms[1] = rec_span(d.rec_ev[1], d.rec_ev[2]) + rec_span(d.rec_ev[3], d.rec_ev[4]) + rec_span(d.rec_ev[5], d.rec_ev[6]);
+        ctx->rec_ms[2] = d2h_ms;
+    }
+    ctx->rec_ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+    ctx->live.push_back(seq);
+    *out = seq;
+    return FZ_OK;
+}
+
+int fz_debug_records_ms(fz_ctx *ctx, double *ms4) {
+    if (!ctx || !ms4) return fail(FZ_EINVAL, "null argument");
+    for (int i = 0; i < 4; ++i) ms4[i] = ctx->rec_ms[i];
+    return FZ_OK;
+}
+
+uint32_t fz_debug_scan_items(void) { return FZ_RSCAN_ITEMS; }
+
+int fz_batch_tables(const fz_seq *batch, uint64_t *src_starts, uint64_t *ends) {
+    if (!batch) return fail(FZ_EINVAL, "null argument");
+    if (!batch->is_batch) return fail(FZ_EINVAL, "fz_batch_tables takes a batch handle");
+    const uint64_t ns = batch->n_seqs;
+    if (ends && ns) memcpy(ends, batch->ends.data(), ns * sizeof(uint64_t));
+    if (src_starts && ns) {
+        if (batch->d_src_starts) {
+            HIP_TRY(hipSetDevice(batch->ctx->devs[0].device));
+            HIP_TRY(hipMemcpy(src_starts, batch->d_src_starts, ns * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        } else {
+            src_starts[0] = 0;
+            for (uint64_t j = 1; j < ns; ++j) src_starts[j] = batch->ends[j - 1];
+        }
+    }
+    return FZ_OK;
+}
+
+int fz_debug_batch_bytes(fz_seq *batch, uint8_t *out, uint64_t cap) {
+    if (!batch || (!out && cap)) return fail(FZ_EINVAL, "null argument");
+    if (!batch->is_batch || batch->shards.size() != 1) return fail(FZ_EINVAL, "fz_debug_batch_bytes takes a batch handle");
+    if (cap < batch->n) return fail(FZ_EINVAL, "the buffer is smaller than the batch");
+    if (batch->n == 0) return FZ_OK;
+    const Shard &sh = batch->shards[0];
+    DevState &d = batch->ctx->devs[sh.dev];
+    HIP_TRY(hipSetDevice(d.device));
+    HIP_TRY(hipMemcpyAsync(out, sh.d_buf, batch->n, hipMemcpyDeviceToHost, d.stream));
+    HIP_TRY(hipStreamSynchronize(d.stream));
+    return FZ_OK;
+}
+
+int fz_debug_records_split(const uint8_t *text, uint64_t n, uint32_t lines_per_record, uint32_t sequence_line, uint32_t flags,
+                           uint64_t **src_starts, uint64_t **ends, uint8_t **packed, fz_records_info *info) {
+    if (!src_starts || !ends || !packed) return fail(FZ_EINVAL, "null argument");
+    *src_starts = nullptr; *ends = nullptr; *packed = nullptr;
+    if (info) *info = fz_records_info{};
+    int rc = rec_check_args(text, n, lines_per_record, sequence_line, flags);
+    if (rc) return rc;
+    if (flags & FZ_REC_FASTQ_CHECKS) n = rec_trim(text, n);
+    std::vector<uint64_t> nl;                             // the line table, by the kernels' byte mask word by word
+    uint64_t i = 0;
+    for (; i + 4 <= n; i += 4) {
+        uint32_t w;
+        memcpy(&w, text + i, 4);
+        for (uint32_t m = fz_rec_nl_mask(w); m; m &= m - 1u) nl.push_back(i + ((uint32_t)__builtin_ctz(m) >> 3));
+    }
+    for (; i < n; ++i) if (text[i] == '\n') nl.push_back(i);
+    const uint64_t n_nl = nl.size();
+    const uint64_t n_lines = fz_rec_n_lines(text, n, n_nl);
+    const uint64_t n_seqs = fz_rec_n_seqs(n_lines, lines_per_record, sequence_line);
+    if (info) { info->n_lines = n_lines; info->n_seqs = n_seqs; }
+    if (n_seqs >= (1ull << 32)) return fail(FZ_EUNSUPPORTED, "more than 2^32 - 1 sequences in a batch");
+    uint64_t key = fz_rec_count_key(n_lines, lines_per_record, flags), total = 0;
+    std::vector<FzRecOut> recs(n_seqs);
+    for (uint64_t r = 0; r < n_seqs; ++r) {
+        recs[r] = fz_rec_measure(text, n, nl.data(), n_nl, n_lines, lines_per_record, sequence_line, flags, r);
+        if (recs[r].reason != FZ_REC_OK) key = std::min(key, fz_rec_err_key(r, recs[r].reason));
+        total += recs[r].len;
+    }
+    if (key != FZ_REC_NO_ERROR) return rec_report((flags & FZ_REC_FASTQ_CHECKS) ? "fastq" : "lines", key, info);
+    if (info) info->packed_bytes = total;
+    void *ms = nullptr, *me = nullptr, *mp = nullptr;
+    rc = alloc_out(n_seqs, sizeof(uint64_t), &ms);
+    if (rc == FZ_OK) rc = alloc_out(n_seqs, sizeof(uint64_t), &me);
+    if (rc == FZ_OK) rc = alloc_out(total, 1, &mp);
+    if (rc) { release_out(ms); release_out(me); release_out(mp); return rc; }
+    uint64_t at = 0;
+    for (uint64_t r = 0; r < n_seqs; ++r) {
+        static_cast<uint64_t *>(ms)[r] = recs[r].start;
+        if (recs[r].len) memcpy(static_cast<uint8_t *>(mp) + at, text + recs[r].start, recs[r].len);
+        at += recs[r].len;
+        static_cast<uint64_t *>(me)[r] = at;
+    }
+    *src_starts = static_cast<uint64_t *>(ms); *ends = static_cast<uint64_t *>(me); *packed = static_cast<uint8_t *>(mp);
     return FZ_OK;
 }
 

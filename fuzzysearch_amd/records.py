@@ -1,0 +1,140 @@
+"""resident_records: a FASTQ file, or a file with one read / barcode / guide per line, becomes a batch on the device.
+
+The text crosses PCIe once and is split where it lies (fz_batch_upload_records: newlines counted and ranked, one line kept
+per record, the lengths scanned, the sequences gathered), so no Python object per read is ever made.  The result is a
+``BatchSequences``: pass it as ``sequences`` to find_near_matches_batch, find_near_matches_multi_batch and
+find_best_matches_batch.
+
+What a line is: it ends at ``\\n`` or, the last one, at the end of the text; one ``\\r`` in front of that end is not content.
+
+``format='lines'``   every line is a sequence, empty lines included.
+``format='fastq'``   four lines per record, the sequence on the second; trailing empty lines are ignored.  Checked: the
+                     line count is a multiple of 4, the first line starts with ``@``, the third with ``+``, the fourth is as
+                     long as the second.  The first malformed record raises ``ValueError`` naming it.
+
+Not understood: FASTQ records whose sequence spans several lines, FASTA (newlines inside a sequence have to be removed,
+which is another gather) and compressed files — decompress and pass the bytes.
+"""
+import mmap
+import os
+
+import numpy as np
+
+from . import _native
+from .batch import BatchSequences, _single_device
+
+__all__ = ['resident_records', 'RecordBatch', 'split_records']
+
+_REASONS = {1: 'the number of lines is not a multiple of 4 (truncated record)',
+            2: "the header line does not start with '@'",
+            3: "the separator line does not start with '+'",
+            4: 'the quality line is not as long as the sequence line'}
+
+
+class RecordSequences(object):
+    """The sequences of a RecordBatch as a read-only sequence of ``bytes``, cut from the source on demand."""
+
+    def __init__(self, source, starts, lengths):
+        self._source, self._starts, self._lengths = source, starts, lengths
+
+    def __len__(self):
+        return len(self._starts)
+
+    def _one(self, j):
+        s = int(self._starts[j])
+        return bytes(self._source[s:s + int(self._lengths[j])])
+
+    def __getitem__(self, item):
+        if isinstance(item, slice):
+            return [self._one(j) for j in range(*item.indices(len(self)))]
+        j = item.__index__()
+        if j < 0:
+            j += len(self)
+        if not 0 <= j < len(self):
+            raise IndexError('sequence index out of range')
+        return self._one(j)
+
+    def __iter__(self):
+        return (self._one(j) for j in range(len(self)))
+
+
+class RecordBatch(BatchSequences):
+    """A BatchSequences made from a text of records.  ``starts[j]`` = offset of sequence j's first byte in the source,
+    ``lengths[j]`` its length (numpy uint64); ``sequences`` cuts ``bytes`` from the source, which is kept alive, on demand."""
+
+    def __init__(self, source, format='fastq', engine=None):
+        if format not in _native.RECORD_FORMATS:
+            raise ValueError('unknown record format %r (known: %s)' % (format, ', '.join(sorted(_native.RECORD_FORMATS))))
+        self.format = format
+        self.source = _open_source(source)
+        self.engine = engine or _native.default_engine()
+        self.handle = None
+        self.kind = None
+        if _single_device(self.engine):
+            self.handle = self.engine.upload_records(self.source, *_native.RECORD_FORMATS[format])
+            self.kind = 'bytes'
+            self.starts, ends = self.engine.batch_tables(self.handle)
+            self.lengths = ends.copy()
+            if len(ends) > 1:
+                self.lengths[1:] -= ends[:-1]
+            self.sequences = RecordSequences(self.source, self.starts, self.lengths)
+        else:                                       # the batched call does not serve this engine: every search loops
+            self.starts, self.lengths = split_records(self.source, format)
+            view = RecordSequences(self.source, self.starts, self.lengths)
+            self.sequences = list(view)
+
+
+def resident_records(source, format='fastq', engine=None):
+    """``source`` (bytes-like, or the path of a file, which is mapped read-only) -> a RecordBatch: its sequences resident in
+    device memory, usable as ``sequences`` of the batch searches.  ``format``: 'fastq' or 'lines' (module docstring)."""
+    return RecordBatch(source, format, engine)
+
+
+def _open_source(source):
+    if isinstance(source, str) and ('\n' in source or '\r' in source):
+        raise TypeError('the text of a file is passed as bytes, a str is a path')
+    if isinstance(source, (str, os.PathLike)):
+        with open(source, 'rb') as f:
+            if os.fstat(f.fileno()).st_size == 0:
+                return b''
+            return mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
+    mv = memoryview(source)                         # TypeError for anything that is not bytes-like
+    if mv.itemsize != 1 or mv.ndim != 1 or not mv.c_contiguous:
+        raise TypeError('only contiguous sequences of single-byte values are supported')
+    return source
+
+
+def split_records(source, format):
+    """The split on the host, in plain Python (engines the batched call does not serve) -> (starts, lengths)."""
+    period, phase, flags = _native.RECORD_FORMATS[format]
+    data = bytes(source)
+    lines = data.split(b'\n')
+    if lines[-1] == b'':
+        lines.pop()
+    spans, pos = [], 0
+    for ln in lines:
+        spans.append((pos, len(ln) - (1 if ln.endswith(b'\r') else 0)))
+        pos += len(ln) + 1
+    if flags & _native.REC_FASTQ_CHECKS:
+        while spans and spans[-1][1] == 0:
+            spans.pop()
+        bad = []
+        if len(spans) % 4:
+            bad.append((len(spans) // 4, 1))
+        for r in range(len(spans) // 4):
+            (h, hl), (s, sl), (p, pl), (q, ql) = spans[4 * r:4 * r + 4]
+            if not hl or data[h:h + 1] != b'@':
+                bad.append((r, 2))
+            elif not pl or data[p:p + 1] != b'+':
+                bad.append((r, 3))
+            elif ql != sl:
+                bad.append((r, 4))
+            if bad and bad[-1][0] == r:
+                break
+        if bad:
+            r, why = min(bad)
+            raise ValueError('%s: record %d: %s' % (format, r, _REASONS[why]))
+    kept = spans[phase::period]
+    starts = np.fromiter((s for s, _ in kept), dtype=np.uint64, count=len(kept))
+    lengths = np.fromiter((n for _, n in kept), dtype=np.uint64, count=len(kept))
+    return starts, lengths

@@ -313,6 +313,45 @@ int fz_debug_assign_fold(const uint64_t *offs, uint64_t n_seqs, const void *recs
  * calls with the same array (same address, length and total). */
 int fz_debug_batch_segment(const uint64_t *offs, uint64_t n_seqs, uint64_t idx, uint64_t *j, uint64_t *sa, uint64_t *se);
 
+/* Records: a text of lines (a FASTQ file, a file with one read per line) becomes a batch on the device.  The text is
+ * copied to the device once and split there (fz_kernels.h: fz_rec_*_kernel): newlines are counted per 16 KiB tile, the
+ * counts scanned, every newline's position written at its rank, one lane per record measures its sequence, the lengths
+ * are scanned and the sequences gathered into a buffer laid out as fz_batch_upload's.  No per-sequence work on the host.
+ *   Lines: a line ends at '\n' or, the last one, at the end of the text (an empty text has no lines); one '\r' in front of
+ *   that end is not content.  Record r = lines r * lines_per_record .. + lines_per_record - 1, its sequence = line
+ *   r * lines_per_record + sequence_line (sequence_line < lines_per_record), empty lines included.
+ *   FZ_REC_FASTQ_CHECKS (lines_per_record = 4, sequence_line = 1 only): trailing empty lines are dropped first, then the
+ *   smallest (record, reason) is an error: 1 the line count is no multiple of 4 (record = lines / 4), 2 line 0 does not
+ *   start with '@', 3 line 2 does not start with '+', 4 line 3 is not as long as line 1.  Then the call answers FZ_EINVAL
+ *   with *out = NULL, info->bad_record / bad_reason filled in and nothing left allocated.  (bad_reason = 0: no error.)
+ *   Multi-line FASTQ, FASTA and compressed input are not understood.
+ * The handle is a batch handle like fz_batch_upload's (same refusals: several devices or a communicator, a search in
+ * flight, a text of 2^48 bytes or more, 2^32 sequences or more); fz_batch_search, _multi and _assign cannot tell them apart. */
+#define FZ_REC_FASTQ_CHECKS 1u
+typedef struct {
+    uint64_t n_lines, n_seqs, packed_bytes, bad_record;
+    uint32_t bad_reason;
+} fz_records_info;
+
+int fz_batch_upload_records(fz_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t lines_per_record, uint32_t sequence_line,
+                            uint32_t flags, fz_seq **out, fz_records_info *info);
+
+/* The tables of a batch handle, n_seqs entries each (either may be NULL): src_starts[j] = offset of sequence j's first byte
+ * in the text it was cut from (a handle of fz_batch_upload: offs[j]), ends[j] = its end in the packed bytes. */
+int fz_batch_tables(const fz_seq *batch, uint64_t *src_starts, uint64_t *ends);
+
+/* Test hooks.  fz_debug_batch_bytes: the packed bytes of a batch handle back from the device (cap >= fz_seq_len).
+ * fz_debug_records_split: no device — the split of fz_batch_upload_records on the host through the functions its kernels
+ * run (fz_device.h: fz_rec_line, fz_rec_measure, fz_rec_err_key); *src_starts, *ends (n_seqs entries) and *packed are
+ * released with fz_free and are NULL after an error, which is reported as above.
+ * fz_debug_scan_items: the items one workgroup of the device scan handles (its seams).  fz_debug_records_ms: device and host
+ * spans of the context's last fz_batch_upload_records, milliseconds: {H2D copy, the kernels, the D2H of ends[], whole call}. */
+int fz_debug_batch_bytes(fz_seq *batch, uint8_t *out, uint64_t cap);
+int fz_debug_records_split(const uint8_t *text, uint64_t n, uint32_t lines_per_record, uint32_t sequence_line, uint32_t flags,
+                           uint64_t **src_starts, uint64_t **ends, uint8_t **packed, fz_records_info *info);
+uint32_t fz_debug_scan_items(void);
+int fz_debug_records_ms(fz_ctx *ctx, double *ms4);
+
 /* has_near_match_* (substitutions_only.py:139-145, :218-233; generic_search.py:240-253): *found = 1 iff the
  * corresponding search would return at least one record.  Nothing is ordered or copied, and device work that starts
  * after the first record has been counted is skipped (workgroups of the scan, hits of the automaton kernel). */
