@@ -773,30 +773,28 @@ class Engine(object):
                                              ctypes.byref(ptr), ctypes.byref(sptr), ctypes.byref(cnt)))
         return ptr, sptr, cnt.value
 
+    def _take_seq_of(self, sptr, n):
+        """The library's seq_of buffer of n rows -> a uint32 array of its own; the buffer is freed."""
+        import numpy as np
+        seq_of = np.empty(n, dtype=np.uint32)
+        if n:
+            ctypes.memmove(seq_of.ctypes.data, sptr, 4 * n)
+        self._lib.fz_free(sptr)
+        return seq_of
+
     def batch_search(self, batch, mode, pattern, k, reduced=False):
         """fz_batch_search -> (rows, seq_of): an fz_match structured array in the local coordinates of the rows' sequences,
         ordered by sequence, and the uint32 array of their sequence numbers."""
-        import numpy as np
         ptr, sptr, n = self._batch_call(batch, mode, pattern, k, reduced)
-        seq_of = np.empty(n, dtype=np.uint32)
-        if n:
-            ctypes.memmove(seq_of.ctypes.data, sptr, 4 * n)
-        self._lib.fz_free(sptr)
-        return _take_matches_array(self._lib, ptr, n), seq_of
+        return _take_matches_array(self._lib, ptr, n), self._take_seq_of(sptr, n)
 
     def batch_rows_call(self, batch, mode, pattern, k, reduced=True):
         """The same as (OwnedRows, seq_of array), for callers that build Match objects in C straight from the result buffer."""
-        import numpy as np
         ptr, sptr, n = self._batch_call(batch, mode, pattern, k, reduced)
-        seq_of = np.empty(n, dtype=np.uint32)
-        if n:
-            ctypes.memmove(seq_of.ctypes.data, sptr, 4 * n)
-        self._lib.fz_free(sptr)
-        return OwnedRows(self._lib, ptr, n), seq_of
+        return OwnedRows(self._lib, ptr, n), self._take_seq_of(sptr, n)
 
     def _batch_multi_call(self, batch, mode, patterns, k, reduced):
         """-> (rows pointer, seq_of array, per-pattern row offsets) of one fz_batch_search_multi call; the caller owns the pointer."""
-        import numpy as np
         blob, offs = pack_patterns(patterns)
         ptr = ctypes.POINTER(FzMatch)()
         sptr = ctypes.POINTER(ctypes.c_uint32)()
@@ -806,11 +804,7 @@ class Engine(object):
                                                    ctypes.byref(ptr), ctypes.byref(sptr), ctypes.byref(optr)))
         bounds = optr[:len(patterns) + 1]
         self._lib.fz_free(optr)
-        seq_of = np.empty(bounds[-1], dtype=np.uint32)
-        if bounds[-1]:
-            ctypes.memmove(seq_of.ctypes.data, sptr, 4 * bounds[-1])
-        self._lib.fz_free(sptr)
-        return ptr, seq_of, bounds
+        return ptr, self._take_seq_of(sptr, bounds[-1]), bounds
 
     def batch_search_multi(self, batch, mode, patterns, k, reduced=False):
         """[batch_search(batch, mode, p, k, reduced) for p in patterns] in as few passes over the batch as the patterns

@@ -497,14 +497,27 @@ void resolve_timing(fz_ctx *ctx) {
 
 namespace {
 
-int ensure_hits(DevState &d, uint64_t cap) {
-    if (d.hit_cap >= cap) return FZ_OK;
+// A device buffer that only grows: one that holds fewer than `cap` units is freed and allocated again with `bytes` bytes
+// (its contents are lost; a buffer that a kernel in flight may still use is synchronised by the caller).
+template <class T>
+int grow_device(DevState &d, T *&ptr, uint64_t &have, uint64_t cap, uint64_t bytes) {
+    if (have >= cap) return FZ_OK;
     HIP_TRY(hipSetDevice(d.device));
-    if (d.d_hits) { HIP_TRY(hipFree(d.d_hits)); d.d_hits = nullptr; d.hit_cap = 0; }
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d.d_hits), cap * sizeof(uint64_t)));
-    d.hit_cap = cap;
+    if (ptr) { HIP_TRY(hipFree(ptr)); ptr = nullptr; have = 0; }
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ptr), (size_t)bytes));
+    have = cap;
     return FZ_OK;
 }
+
+// The span between two recorded, completed events in ms; 0 (and no pending HIP error) if it cannot be read.
+double span_ms(hipEvent_t a, hipEvent_t b) {
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, a, b) != hipSuccess) ms = 0;
+    (void)hipGetLastError();
+    return (double)ms;
+}
+
+int ensure_hits(DevState &d, uint64_t cap) { return grow_device(d, d.d_hits, d.hit_cap, cap, cap * sizeof(uint64_t)); }
 
 constexpr uint32_t kCandLdsMax = 4096;            // candidate slots per list that still live in LDS
 constexpr uint32_t kCandMax = 1u << 18;           // ... and in the HBM fallback (4 MiB per workgroup)
@@ -520,12 +533,8 @@ int cand_lists(DevState &d, uint32_t cand_cap, size_t fixed_lds, size_t &lds, ui
     if (cand_cap > kCandMax) return fail(FZ_EUNSUPPORTED, "automaton candidate sets beyond %u entries", kCandMax);
     lds = fixed_lds;
     const uint64_t need = (uint64_t)kCandScratchGrid * 2 * cand_cap * sizeof(FzGCand);
-    if (d.cand_bytes < need) {
-        HIP_TRY(hipSetDevice(d.device));
-        if (d.d_cand) { HIP_TRY(hipFree(d.d_cand)); d.d_cand = nullptr; d.cand_bytes = 0; }
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d.d_cand), need));
-        d.cand_bytes = need;
-    }
+    int rc = grow_device(d, d.d_cand, d.cand_bytes, need, need);
+    if (rc) return rc;
     scratch = reinterpret_cast<uint64_t>(d.d_cand);
     return FZ_OK;
 }
@@ -543,11 +552,7 @@ int ensure_big(DevState &d, uint64_t cap) {
 int ensure_gen_rows(DevState &d) {
     HIP_TRY(hipSetDevice(d.device));
     if (!d.d_gen_order) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d.d_gen_order), (size_t)FZ_GEN_ORDER_MAX * 12));
-    if (d.gen_rows_cap >= d.rec_cap) return FZ_OK;
-    if (d.d_gen_rows) { HIP_TRY(hipFree(d.d_gen_rows)); d.d_gen_rows = nullptr; d.gen_rows_cap = 0; }
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d.d_gen_rows), d.rec_cap * sizeof(FzOutRow)));
-    d.gen_rows_cap = d.rec_cap;
-    return FZ_OK;
+    return grow_device(d, d.d_gen_rows, d.gen_rows_cap, d.rec_cap, d.rec_cap * sizeof(FzOutRow));
 }
 
 // Snapshot buffers of a communicator's device state: at least `cap` records each; contents are kept (a snapshot
@@ -573,10 +578,8 @@ int ensure_send(DevState &d, uint64_t cap) {
 
 int ensure_recs(DevState &d, uint64_t cap) {
     if (d.rec_cap >= cap) return FZ_OK;
-    HIP_TRY(hipSetDevice(d.device));
-    if (d.d_out) { HIP_TRY(hipFree(d.d_out)); d.d_out = nullptr; d.rec_cap = 0; }
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d.d_out), kHeaderBytes + cap * sizeof(FzRec)));
-    d.rec_cap = cap;
+    int rc = grow_device(d, d.d_out, d.rec_cap, cap, kHeaderBytes + cap * sizeof(FzRec));
+    if (rc) return rc;
     d.header_zeroed = false;
     return FZ_OK;
 }
@@ -810,10 +813,9 @@ int stage_pattern(DevState &d, FzScanArgs &fa, const uint8_t *p, uint32_t m, boo
     HIP_TRY(hipSetDevice(d.device));
     if (d.pat_cap < m) {
         HIP_TRY(hipStreamSynchronize(d.stream));
-        if (d.d_pat) { HIP_TRY(hipFree(d.d_pat)); d.d_pat = nullptr; d.pat_cap = 0; }
         const uint64_t cap = std::max<uint64_t>(4096, (uint64_t)m * 2);
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d.d_pat), cap));
-        d.pat_cap = cap;
+        int rc = grow_device(d, d.d_pat, d.pat_cap, cap, cap);
+        if (rc) return rc;
     }
     HIP_TRY(hipMemcpyAsync(d.d_pat, p, m, hipMemcpyHostToDevice, d.stream));
     fa.pat_g = reinterpret_cast<uint64_t>(d.d_pat);
@@ -2779,10 +2781,6 @@ int rec_malloc_bytes(void **p, uint64_t bytes) {
 }
 #define rec_malloc(pp, count) rec_malloc_bytes(reinterpret_cast<void **>(pp), std::max<uint64_t>(1, (count)) * sizeof(**(pp)))
 
-double rec_span(hipEvent_t a, hipEvent_t b) {
-    float ms = 0;
-    return hipEventElapsedTime(&ms, a, b) == hipSuccess ? (double)ms : 0.0;
-}
 }  // namespace
 
 int fz_batch_upload_records(fz_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t lines_per_record, uint32_t sequence_line,
@@ -2917,8 +2915,8 @@ int fz_batch_upload_records(fz_ctx *ctx, const uint8_t *text, uint64_t n, uint32
     }
     if (rc) { fz_seq_release(seq); return rc; }
     if (timed) {
-        ctx->rec_ms[0] = rec_span(d.rec_ev[0], d.rec_ev[1]);
-        ctx->rec_ms[1] = rec_span(d.rec_ev[1], d.rec_ev[2]) + rec_span(d.rec_ev[3], d.rec_ev[4]) + rec_span(d.rec_ev[5], d.rec_ev[6]);
+        ctx->rec_ms[0] = span_ms(d.rec_ev[0], d.rec_ev[1]);
+        ctx->rec_ms[1] = span_ms(d.rec_ev[1], d.rec_ev[2]) + span_ms(d.rec_ev[3], d.rec_ev[4]) + span_ms(d.rec_ev[5], d.rec_ev[6]);
         ctx->rec_ms[2] = d2h_ms;
     }
     ctx->rec_ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
@@ -3067,6 +3065,22 @@ static int lev_plan(fz_ctx *ctx, fz_seq *seq, const uint8_t *p, uint32_t m, uint
     return FZ_OK;
 }
 
+// Argument checks and the block plan of the substitutions-only n-gram search (template :92-101).
+static int subs_plan(fz_ctx *ctx, fz_seq *seq, const uint8_t *p, uint32_t m, uint32_t k, Search &q, bool in_pipeline = false) {
+    int rc = validate(ctx, seq, p, m, in_pipeline);
+    if (rc) return rc;
+    const uint32_t L = m / (k + 1);
+    if (L == 0) return fail(FZ_EUNSUPPORTED, "max_substitutions >= len(subsequence): every window matches; not a GPU path");
+    rc = check_halo(seq, m);
+    if (rc) return rc;
+    q.mode = FZ_MODE_SUBS; q.m = m; q.k = k; q.p = p;
+    q.collective = ctx->snapshot;
+    q.plan.L = L;
+    for (uint32_t s = 0; s + L <= m; s += L) q.plan.s.push_back(s);   // template :92-101 (ranges: fz_block_range)
+    if (q.plan.s.size() > FZ_MAX_BLOCKS) return fail(FZ_EUNSUPPORTED, "more than %u n-gram blocks", FZ_MAX_BLOCKS);
+    return FZ_OK;
+}
+
 int fz_lev_ngrams(fz_ctx *ctx, fz_seq *seq, const uint8_t *p, uint32_t m, uint32_t k, fz_match **out, uint64_t *n) {
     if (!out || !n) return fail(FZ_EINVAL, "null argument");
     *out = nullptr; *n = 0;
@@ -3139,12 +3153,18 @@ constexpr double kMpMargin = 0.9;
 constexpr double kMpSubsPerCand = 0.043;
 constexpr double kLoopSubsScan = 0.201, kLoopSubsPerCand = 0.031;
 
-static bool mp_worth_a_pass(uint32_t mode, const uint8_t *pats, const uint64_t *offs, const MpGroup &g) {
+// The distinct symbols of a group's patterns.
+static uint32_t mp_sigma(const uint8_t *pats, const uint64_t *offs, const MpGroup &g) {
     bool seen[256] = {false};
     uint32_t sigma = 0;
     for (uint32_t i : g.pats)
         for (uint64_t q = offs[i]; q < offs[i + 1]; ++q)
             if (!seen[pats[q]]) { seen[pats[q]] = true; ++sigma; }
+    return sigma;
+}
+
+static bool mp_worth_a_pass(uint32_t mode, const uint8_t *pats, const uint64_t *offs, const MpGroup &g) {
+    const uint32_t sigma = mp_sigma(pats, offs, g);
     double frac = (double)g.blocks;
     for (uint32_t i = 0; i < g.L && frac > 1e-12; ++i) frac /= (double)sigma;
     const double cand = std::min(frac, (double)g.blocks) * 1073.741824;      // millions per GiB
@@ -3187,20 +3207,35 @@ static int mp_ensure(DevState &d, uint64_t hit_cap, uint64_t rec_cap) {
     HIP_TRY(hipSetDevice(d.device));
     if (!d.d_mp_desc) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d.d_mp_desc), FZ_MP_DESC_WORDS * 4u));
     if (!d.d_mp_ctr) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d.d_mp_ctr), FZ_MP_CTR_WORDS * 8u));
-    if (d.mp_hit_cap < hit_cap) {
-        if (d.d_mp_hits) { HIP_TRY(hipFree(d.d_mp_hits)); d.d_mp_hits = nullptr; d.mp_hit_cap = 0; }
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d.d_mp_hits), (size_t)FZ_MP_LISTS * hit_cap * sizeof(uint64_t)));
-        d.mp_hit_cap = hit_cap;
-    }
-    if (d.mp_rec_cap < rec_cap) {
-        if (d.d_mp_recs) { HIP_TRY(hipFree(d.d_mp_recs)); d.d_mp_recs = nullptr; d.mp_rec_cap = 0; }
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d.d_mp_recs), (size_t)rec_cap * sizeof(FzRec)));
-        d.mp_rec_cap = rec_cap;
-    }
-    return FZ_OK;
+    int rc = grow_device(d, d.d_mp_hits, d.mp_hit_cap, hit_cap, (uint64_t)FZ_MP_LISTS * hit_cap * sizeof(uint64_t));
+    if (rc) return rc;
+    return grow_device(d, d.d_mp_recs, d.mp_rec_cap, rec_cap, rec_cap * sizeof(FzRec));
 }
 
-struct MpTotals { uint64_t bytes = 0, hits = 0, rows = 0; uint32_t launches = 0; double filter_ms = 0, verify_ms = 0; };
+// What a list-of-patterns call reports (fz_stats): summed over its group launches and its single searches.
+struct MpTotals {
+    uint64_t bytes = 0, hits = 0, rows = 0;
+    uint32_t launches = 0;
+    double filter_ms = 0, verify_ms = 0;
+    // a finished single search, from the stats it left (its rows are the caller's to count; its spans are not summed)
+    void add_search(const fz_stats_t &st) { bytes += st.bytes_scanned; hits += st.ngram_hits; launches += st.filter_launches; }
+};
+
+// The totals become the context's stats.  raw_matches: the rows (or, for an assignment, the records folded);
+// extra_verify_ms: kernels behind the verification that count with it (the assignment's fold).
+static void mp_publish(fz_ctx *ctx, const MpTotals &tot, uint64_t raw_matches, uint32_t form, double extra_verify_ms = 0) {
+    memset(&ctx->stats, 0, sizeof ctx->stats);
+    ctx->tref.clear();
+    ctx->stats.n_devices = (uint32_t)ctx->devs.size();
+    ctx->stats.filter_launches = tot.launches;
+    ctx->stats.bytes_scanned = tot.bytes;
+    ctx->stats.ngram_hits = tot.hits;
+    ctx->stats.raw_matches = raw_matches;
+    ctx->stats.filter_ms = tot.filter_ms;
+    ctx->stats.verify_ms = tot.verify_ms + extra_verify_ms;
+    ctx->stats.device_ms = tot.filter_ms + tot.verify_ms + extra_verify_ms;
+    ctx->stats.verify_form = form;
+}
 
 // One group over one shard: descriptor up, filter, verification, counters and records back.  Capacities come from the
 // arguments — the project's estimate of expected candidates, sequence bytes x blocks / sigma^L (sigma = distinct symbols
@@ -3259,10 +3294,8 @@ static int mp_launch_shard(fz_ctx *ctx, const Shard &sh, uint32_t mode, const ui
         HIP_TRY(hipStreamSynchronize(d.stream));
         ++tot.launches;
         if (ctx->timing) {
-            float f = 0, v = 0;
-            if (hipEventElapsedTime(&f, d.ev[0], d.ev[1]) == hipSuccess) tot.filter_ms += f;
-            if (hipEventElapsedTime(&v, d.ev[1], d.ev[2]) == hipSuccess) tot.verify_ms += v;
-            (void)hipGetLastError();
+            tot.filter_ms += span_ms(d.ev[0], d.ev[1]);
+            tot.verify_ms += span_ms(d.ev[1], d.ev[2]);
         }
         uint64_t need_hits = 0;
         for (uint32_t l = 0; l < FZ_MP_LISTS; ++l) need_hits = std::max<uint64_t>(need_hits, ctr[FZ_MP_CTR_LIST(l)]);
@@ -3286,50 +3319,36 @@ static int mp_launch_shard(fz_ctx *ctx, const Shard &sh, uint32_t mode, const ui
     return fail(FZ_EDEVICE, "result buffers kept overflowing");
 }
 
-// ... and the records appended to `recs` on the host.
-static int mp_run_shard(fz_ctx *ctx, const Shard &sh, uint32_t mode, const uint32_t *desc, uint32_t nent, uint32_t k, uint32_t L, uint32_t max_m,
-                        uint32_t sigma, std::vector<FzRec> &recs, MpTotals &tot, bool rag = false) {
-    uint64_t nr = 0;
-    int rc = mp_launch_shard(ctx, sh, mode, desc, nent, k, L, max_m, sigma, &nr, tot, rag);
-    if (rc) return rc;
-    const size_t at = recs.size();
-    recs.resize(at + nr);
-    if (nr) HIP_TRY(hipMemcpy(recs.data() + at, ctx->devs[sh.dev].d_mp_recs, nr * sizeof(FzRec), hipMemcpyDeviceToHost));
-    return FZ_OK;
-}
-
-// The descriptor of a group: -> its entries (0: failed), the longest pattern and the number of distinct symbols.
-static int mp_describe_group(const uint8_t *pats, const uint64_t *offs, const MpGroup &g, std::vector<uint32_t> &desc, uint32_t *nent_out,
-                             uint32_t *max_m_out, uint32_t *sigma_out) {
+// One group over one shard: its descriptor built (fz_mp_build), then mp_launch_shard.
+// -> *n_recs records in d.d_mp_recs (aux = the pattern's number in the group), the stream idle.
+static int mp_launch_group(fz_ctx *ctx, const Shard &sh, uint32_t mode, const uint8_t *pats, const uint64_t *offs, uint32_t k, const MpGroup &g,
+                           uint64_t *n_recs, MpTotals &tot, bool rag) {
     const uint32_t np = (uint32_t)g.pats.size();
     const uint8_t *pp[FZ_MP_MAX_PATS];
     uint32_t pm[FZ_MP_MAX_PATS], max_m = 0;
-    bool seen[256] = {false};
-    uint32_t sigma = 0;
     for (uint32_t j = 0; j < np; ++j) {
         pp[j] = pats + offs[g.pats[j]];
         pm[j] = (uint32_t)(offs[g.pats[j] + 1] - offs[g.pats[j]]);
         max_m = std::max(max_m, pm[j]);
-        for (uint32_t q = 0; q < pm[j]; ++q) if (!seen[pp[j][q]]) { seen[pp[j][q]] = true; ++sigma; }
     }
-    desc.assign(FZ_MP_DESC_WORDS, 0u);
+    std::vector<uint32_t> desc(FZ_MP_DESC_WORDS, 0u);
     const uint32_t nent = fz_mp_build(desc.data(), pp, pm, np, g.L);
     if (nent == 0 || nent != g.blocks) return fail(FZ_EDEVICE, "internal: the group's block table does not match its plan");
-    *nent_out = nent; *max_m_out = max_m; *sigma_out = std::max(1u, sigma);
-    return FZ_OK;
+    return mp_launch_shard(ctx, sh, mode, desc.data(), nent, k, g.L, max_m, std::max(1u, mp_sigma(pats, offs, g)), n_recs, tot, rag);
 }
 
+// One group over every shard of the sequence, the records copied back -> rows[i] of every pattern i of the group.
 static int mp_run_group(fz_ctx *ctx, fz_seq *seq, uint32_t mode, const uint8_t *pats, const uint64_t *offs, uint32_t k, const MpGroup &g,
                         std::vector<std::vector<fz_match>> &rows, MpTotals &tot) {
     const uint32_t np = (uint32_t)g.pats.size();
-    std::vector<uint32_t> desc;
-    uint32_t nent = 0, max_m = 0, sigma = 0;
-    int drc = mp_describe_group(pats, offs, g, desc, &nent, &max_m, &sigma);
-    if (drc) return drc;
     std::vector<FzRec> recs;
     for (const Shard &sh : seq->shards) {
-        int rc = mp_run_shard(ctx, sh, mode, desc.data(), nent, k, g.L, max_m, sigma, recs, tot, seq->is_batch);
+        uint64_t nr = 0;
+        int rc = mp_launch_group(ctx, sh, mode, pats, offs, k, g, &nr, tot, seq->is_batch);
         if (rc) return rc;
+        const size_t at = recs.size();
+        recs.resize(at + nr);
+        if (nr) HIP_TRY(hipMemcpy(recs.data() + at, ctx->devs[sh.dev].d_mp_recs, nr * sizeof(FzRec), hipMemcpyDeviceToHost));
     }
     // per pattern: its records (aux = the pattern's number in the group) in the reference's order — block ascending, hit
     // index ascending, by the host ordering every search uses.  Shards own disjoint index ranges in global coordinates,
@@ -3355,30 +3374,110 @@ static int mp_check_lists(const uint8_t *pats, const uint64_t *offs, uint32_t n_
     return FZ_OK;
 }
 
+// validate() accepts a batch handle inside a batch call only.
+struct BatchScope {
+    fz_ctx *c;
+    explicit BatchScope(fz_ctx *c_) : c(c_) { c->batch_call = true; }
+    ~BatchScope() { c->batch_call = false; }
+};
+
+static int batch_single_device(fz_ctx *ctx, fz_seq *batch) {
+    if (ctx->devs.size() != 1 || ctx->snapshot || comm_multi_process(ctx) || (batch && batch->is_batch && batch->shards.size() != 1))
+        return fail(FZ_EUNSUPPORTED, "batches are searched by single-device, non-collective contexts");
+    return FZ_OK;
+}
+
+// What every list-of-patterns call checks before anything is searched: the handles, the state of the context, the lists,
+// and every pattern through the single call's checks (lev_plan / subs_plan).  batch_call: the name of a call that takes a
+// batch handle (fz_batch_search_multi, fz_batch_assign), null for the calls of a whole sequence (fz_*_ngrams_multi*).
+static int mp_admit(fz_ctx *ctx, fz_seq *seq, uint32_t mode, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k,
+                    const char *batch_call) {
+    if (!ctx || !seq || seq->ctx != ctx) return fail(FZ_EINVAL, "bad ctx/seq handle");
+    if (batch_call) {
+        if (mode != FZ_MODE_LEV && mode != FZ_MODE_SUBS) return fail(FZ_EINVAL, "mode must be Levenshtein or substitutions-only");
+        int rc = batch_single_device(ctx, seq);
+        if (rc) return rc;
+        if (!seq->is_batch) return fail(FZ_EINVAL, "%s takes a batch handle (fz_batch_upload)", batch_call);
+    } else if (seq->is_batch) {
+        return fail(FZ_EINVAL, "a batch handle (fz_batch_upload) is searched with fz_batch_search only");
+    }
+    if (ctx->npend) return fail(FZ_EINVAL, "a search started with fz_lev_ngrams_begin is still in flight");
+    if (ctx->stream_inflight) return fail(FZ_EINVAL, "a file stream of this context has a batch in flight (finish or close it first)");
+    int rc = mp_check_lists(pats, offs, n_pats);
+    if (rc) return rc;
+    auto plans = [&]() {
+        for (uint32_t i = 0; i < n_pats; ++i) {
+            const uint64_t m = offs[i + 1] - offs[i];
+            if (m > FZ_MAX_M_ANY) return fail(FZ_EUNSUPPORTED, "subsequence longer than %u bytes", FZ_MAX_M_ANY);
+            Search q;
+            int prc = mode == FZ_MODE_SUBS ? subs_plan(ctx, seq, m ? pats + offs[i] : nullptr, (uint32_t)m, k, q)
+                                           : lev_plan(ctx, seq, m ? pats + offs[i] : nullptr, (uint32_t)m, k, q);
+            if (prc) return prc;
+        }
+        return (int)FZ_OK;
+    };
+    if (!batch_call) return plans();
+    BatchScope scope(ctx);
+    return plans();
+}
+
+// The patterns outside every group, one search each: search(i, ran) runs pattern i as a single call and keeps what it
+// found (ran = false: it had nothing to run); the stats that search left go into the totals, its verification form into
+// `form` (form_none_too: also when the search verified nothing).
+static int mp_run_solo(fz_ctx *ctx, const std::vector<uint32_t> &group_of, MpTotals &tot, uint32_t &form, bool form_none_too,
+                       const std::function<int(uint32_t, bool &)> &search) {
+    for (uint32_t i = 0; i < group_of.size(); ++i) {
+        if (group_of[i] != 0xffffffffu) continue;
+        bool ran = true;
+        int rc = search(i, ran);
+        if (rc) return rc;
+        if (!ran) continue;
+        tot.add_search(ctx->stats);
+        if (form_none_too || ctx->stats.verify_form != FZ_FORM_NONE) form = ctx->stats.verify_form;
+    }
+    ctx->view = nullptr; ctx->view_n = 0; ctx->rows_ready = false;
+    return FZ_OK;
+}
+
+// rows[i] (and, with seq_of, seq_in[i]: the sequence of every row) of n_pats patterns, back to back -> the call's result
+// buffers; out_offs (optional): pattern i's rows are [offs[i], offs[i + 1]).  Nothing is left allocated on failure.
+static int mp_pack(const std::vector<fz_match> *rows, const std::vector<uint32_t> *seq_in, uint32_t n_pats, fz_match **out, uint32_t **seq_of,
+                   uint64_t **out_offs) {
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n_pats; ++i) total += rows[i].size();
+    void *mem = nullptr, *smem_ = nullptr, *omem = nullptr;
+    int rc = alloc_out(total, sizeof(fz_match), &mem);
+    if (rc == FZ_OK && seq_of) rc = alloc_out(total, sizeof(uint32_t), &smem_);
+    if (rc == FZ_OK && out_offs) rc = alloc_out((uint64_t)n_pats + 1, sizeof(uint64_t), &omem);
+    if (rc) { release_out(mem); release_out(smem_); release_out(omem); return rc; }
+    fz_match *mo = static_cast<fz_match *>(mem);
+    uint32_t *so = static_cast<uint32_t *>(smem_);
+    uint64_t *oo = static_cast<uint64_t *>(omem);
+    uint64_t at = 0;
+    for (uint32_t i = 0; i < n_pats; ++i) {
+        if (oo) oo[i] = at;
+        if (!rows[i].empty()) {
+            memcpy(mo + at, rows[i].data(), rows[i].size() * sizeof(fz_match));
+            if (so) memcpy(so + at, seq_in[i].data(), rows[i].size() * sizeof(uint32_t));
+        }
+        at += rows[i].size();
+    }
+    if (oo) oo[n_pats] = at;
+    *out = mo;
+    if (seq_of) *seq_of = so;
+    if (out_offs) *out_offs = oo;
+    return FZ_OK;
+}
+
 // fz_lev_ngrams_multi* (mode = FZ_MODE_LEV; reduced: fz_consolidate per pattern) and fz_subs_ngrams_multi* (FZ_MODE_SUBS;
 // reduced: fz_group_best per pattern).
-static int subs_plan(fz_ctx *ctx, fz_seq *seq, const uint8_t *p, uint32_t m, uint32_t k, Search &q, bool in_pipeline = false);
-
 static int multi_impl(fz_ctx *ctx, fz_seq *seq, uint32_t mode, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k,
                       bool consolidated, fz_match **out, uint64_t **out_offs) {
     const bool subs = mode == FZ_MODE_SUBS;
     if (!out || !out_offs) return fail(FZ_EINVAL, "null argument");
     *out = nullptr; *out_offs = nullptr;
-    if (!ctx || !seq || seq->ctx != ctx) return fail(FZ_EINVAL, "bad ctx/seq handle");
-    if (seq->is_batch) return fail(FZ_EINVAL, "a batch handle (fz_batch_upload) is searched with fz_batch_search only");
-    if (ctx->npend) return fail(FZ_EINVAL, "a search started with fz_lev_ngrams_begin is still in flight");
-    if (ctx->stream_inflight) return fail(FZ_EINVAL, "a file stream of this context has a batch in flight (finish or close it first)");
-    int rc = mp_check_lists(pats, offs, n_pats);
+    int rc = mp_admit(ctx, seq, mode, pats, offs, n_pats, k, nullptr);
     if (rc) return rc;
-    // every pattern passes the single call's checks before anything is searched
-    for (uint32_t i = 0; i < n_pats; ++i) {
-        const uint64_t m = offs[i + 1] - offs[i];
-        if (m > FZ_MAX_M_ANY) return fail(FZ_EUNSUPPORTED, "subsequence longer than %u bytes", FZ_MAX_M_ANY);
-        Search q;
-        rc = subs ? subs_plan(ctx, seq, m ? pats + offs[i] : nullptr, (uint32_t)m, k, q)
-                  : lev_plan(ctx, seq, m ? pats + offs[i] : nullptr, (uint32_t)m, k, q);
-        if (rc) return rc;
-    }
     std::vector<MpGroup> groups;
     std::vector<uint32_t> group_of;
     // a context in a communicator searches collectively, pattern by pattern, through the existing collective search
@@ -3389,27 +3488,24 @@ static int multi_impl(fz_ctx *ctx, fz_seq *seq, uint32_t mode, const uint8_t *pa
     std::vector<std::vector<fz_match>> rows(n_pats);
     MpTotals tot;
     uint32_t form = FZ_FORM_NONE;
-    for (uint32_t i = 0; i < n_pats; ++i) {
-        if (group_of[i] != 0xffffffffu) continue;
+    rc = mp_run_solo(ctx, group_of, tot, form, /* form_none_too = */ true, [&](uint32_t i, bool &ran) {
         fz_match *one = nullptr;
         uint64_t n_one = 0;
         const uint32_t m = (uint32_t)(offs[i + 1] - offs[i]);
-        if (subs && seq->n < m) continue;                      // (fz_subs_ngrams answers before it searches: nothing to count)
-        rc = subs ? fz_subs_ngrams(ctx, seq, pats + offs[i], m, k, &one, &n_one) : fz_lev_ngrams(ctx, seq, pats + offs[i], m, k, &one, &n_one);
-        if (rc) return rc;
+        if (subs && seq->n < m) { ran = false; return (int)FZ_OK; }    // (fz_subs_ngrams answers before it searches: nothing to count)
+        int src = subs ? fz_subs_ngrams(ctx, seq, pats + offs[i], m, k, &one, &n_one) : fz_lev_ngrams(ctx, seq, pats + offs[i], m, k, &one, &n_one);
+        if (src) return src;
         rows[i].assign(one, one + n_one);
         release_out(one);
-        tot.bytes += ctx->stats.bytes_scanned; tot.hits += ctx->stats.ngram_hits; tot.rows += n_one;
-        tot.launches += ctx->stats.filter_launches;
-        form = ctx->stats.verify_form;
-    }
-    ctx->view = nullptr; ctx->view_n = 0; ctx->rows_ready = false;
+        tot.rows += n_one;
+        return (int)FZ_OK;
+    });
+    if (rc) return rc;
     for (const MpGroup &g : groups) {
         rc = mp_run_group(ctx, seq, mode, pats, offs, k, g, rows, tot);
         if (rc) return rc;
         form = FZ_FORM_KERNEL;
     }
-    uint64_t total = 0;
     if (consolidated) {
         for (uint32_t i = 0; i < n_pats; ++i) {
             fz_match *c = nullptr;
@@ -3420,33 +3516,9 @@ static int multi_impl(fz_ctx *ctx, fz_seq *seq, uint32_t mode, const uint8_t *pa
             release_out(c);
         }
     }
-    for (uint32_t i = 0; i < n_pats; ++i) total += rows[i].size();
-    void *mem = nullptr, *omem = nullptr;
-    rc = alloc_out(total, sizeof(fz_match), &mem);
+    rc = mp_pack(rows.data(), nullptr, n_pats, out, nullptr, out_offs);
     if (rc) return rc;
-    rc = alloc_out((uint64_t)n_pats + 1, sizeof(uint64_t), &omem);
-    if (rc) { release_out(mem); return rc; }
-    fz_match *mo = static_cast<fz_match *>(mem);
-    uint64_t *oo = static_cast<uint64_t *>(omem);
-    uint64_t at = 0;
-    for (uint32_t i = 0; i < n_pats; ++i) {
-        oo[i] = at;
-        if (!rows[i].empty()) memcpy(mo + at, rows[i].data(), rows[i].size() * sizeof(fz_match));
-        at += rows[i].size();
-    }
-    oo[n_pats] = at;
-    *out = mo; *out_offs = oo;
-    memset(&ctx->stats, 0, sizeof ctx->stats);
-    ctx->tref.clear();
-    ctx->stats.n_devices = (uint32_t)ctx->devs.size();
-    ctx->stats.filter_launches = tot.launches;
-    ctx->stats.bytes_scanned = tot.bytes;
-    ctx->stats.ngram_hits = tot.hits;
-    ctx->stats.raw_matches = tot.rows;
-    ctx->stats.filter_ms = tot.filter_ms;
-    ctx->stats.verify_ms = tot.verify_ms;
-    ctx->stats.device_ms = tot.filter_ms + tot.verify_ms;
-    ctx->stats.verify_form = form;
+    mp_publish(ctx, tot, tot.rows, form);
     return FZ_OK;
 }
 
@@ -3494,22 +3566,6 @@ int fz_debug_multi_plan_mode(uint32_t mode, const uint8_t *pats, const uint64_t 
     return FZ_OK;
 }
 
-// Argument checks and the block plan of the substitutions-only n-gram search (template :92-101).
-static int subs_plan(fz_ctx *ctx, fz_seq *seq, const uint8_t *p, uint32_t m, uint32_t k, Search &q, bool in_pipeline) {
-    int rc = validate(ctx, seq, p, m, in_pipeline);
-    if (rc) return rc;
-    const uint32_t L = m / (k + 1);
-    if (L == 0) return fail(FZ_EUNSUPPORTED, "max_substitutions >= len(subsequence): every window matches; not a GPU path");
-    rc = check_halo(seq, m);
-    if (rc) return rc;
-    q.mode = FZ_MODE_SUBS; q.m = m; q.k = k; q.p = p;
-    q.collective = ctx->snapshot;
-    q.plan.L = L;
-    for (uint32_t s = 0; s + L <= m; s += L) q.plan.s.push_back(s);   // template :92-101 (ranges: fz_block_range)
-    if (q.plan.s.size() > FZ_MAX_BLOCKS) return fail(FZ_EUNSUPPORTED, "more than %u n-gram blocks", FZ_MAX_BLOCKS);
-    return FZ_OK;
-}
-
 // ... and of find_near_matches_generic_ngrams (generic_search.py:198-228).
 static int generic_plan(fz_ctx *ctx, fz_seq *seq, const uint8_t *p, uint32_t m, uint32_t max_subs, uint32_t max_ins, uint32_t max_dels,
                         uint32_t max_l, Search &q, bool in_pipeline = false) {
@@ -3533,8 +3589,25 @@ static int generic_plan(fz_ctx *ctx, fz_seq *seq, const uint8_t *p, uint32_t m, 
     return FZ_OK;
 }
 
+// What a finished generic search hands over: the raw stream in the reference's order, or — consolidated — the device's
+// (hull, best match) pairs, one or a few per n-gram hit, through the second stage of the consolidation.
 static int emit_generic_result(fz_ctx *ctx, fz_seq *seq, const Search &q, const std::vector<FzGenRec> &recs_vec, bool consolidated,
-                               fz_match **out, uint64_t *n);
+                               fz_match **out, uint64_t *n) {
+    const uint32_t L = q.plan.L, k = q.k;
+    if (!consolidated) return emit_generic(ctx, seq, recs_vec, L, k, out, n, nullptr);
+    const FzGenRec *prs = ctx->gen_view ? ctx->gen_view : recs_vec.data();
+    const size_t npr = ctx->gen_view ? (size_t)ctx->gen_view_n : recs_vec.size();
+    static thread_local std::vector<Hull> hulls;
+    hulls.clear();
+    hulls.reserve(npr);
+    for (size_t i = 0; i < npr; ++i) {
+        const FzOutRow best = fz_gen_row(prs[i].key, L, k, 0, prs[i].se, prs[i].dist);
+        const FzOutRow hull = fz_gen_row(prs[i].key, L, k, 0, prs[i].win, 0);
+        hulls.push_back(Hull{hull.start, hull.end, fz_match{best.start, best.end, best.dist, best.block}});
+    }
+    ctx->stats.raw_matches = npr;
+    return consolidate_hulls(hulls, out, n);
+}
 
 // Exchange step of a generic search in a one-process-per-GPU job: the automaton records (or folded pairs) of every rank,
 // back to back; emit_generic / consolidate_hulls order them by their (block, index) keys, which are global.
@@ -3743,19 +3816,6 @@ int fz_subs_ngrams_any(fz_ctx *ctx, fz_seq *seq, const uint8_t *p, uint32_t m, u
     return subs_ngrams_impl(ctx, seq, p, m, k, nullptr, nullptr, found);
 }
 
-// validate() accepts a batch handle inside a batch call only.
-struct BatchScope {
-    fz_ctx *c;
-    explicit BatchScope(fz_ctx *c_) : c(c_) { c->batch_call = true; }
-    ~BatchScope() { c->batch_call = false; }
-};
-
-static int batch_single_device(fz_ctx *ctx, fz_seq *batch) {
-    if (ctx->devs.size() != 1 || ctx->snapshot || comm_multi_process(ctx) || (batch && batch->is_batch && batch->shards.size() != 1))
-        return fail(FZ_EUNSUPPORTED, "batches are searched by single-device, non-collective contexts");
-    return FZ_OK;
-}
-
 // Rows of the packed bytes in the in-memory order (block, index), global coordinates -> the batch's result: a row's
 // sequence = the sequence of its first byte (a match lies inside the sequence of its n-gram hit); rows are ordered the way
 // fz_stream_finish orders chunks: a stable sort by sequence of the in-memory order; local coordinates; `reduce`: every
@@ -3817,21 +3877,32 @@ struct AssignCall {
     double fold_ms = 0;
 };
 
+// The grid of the assignment's kernels: a lane per item, grid-stride beyond 8 workgroups per CU.
+static uint32_t assign_grid(const DevState &d, uint64_t items) {
+    return (uint32_t)std::min<uint64_t>((items + FZ_ASSIGN_THREADS - 1) / FZ_ASSIGN_THREADS, (uint64_t)d.n_cus * 8);
+}
+
+// launch() between ev[2] and ev[3] of a context that times its kernels; once ev[3] is complete the span goes to fold_ms.
+static int assign_launch(fz_ctx *ctx, DevState &d, const std::function<void()> &launch) {
+    if (ctx->timing) HIP_TRY(hipEventRecord(d.ev[2], d.stream));
+    launch();
+    HIP_TRY(hipGetLastError());
+    if (ctx->timing) HIP_TRY(hipEventRecord(d.ev[3], d.stream));
+    return FZ_OK;
+}
+
 // recs: n device records; table: npat entries of the call's aux table (one entry: aux ignored).  Stream-ordered, no wait.
 static int assign_fold_device(fz_ctx *ctx, AssignCall &ac, const FzRec *d_recs, uint64_t n, uint32_t L, const FzAssignPat *table, uint32_t npat) {
     if (!n) return FZ_OK;
     DevState &d = *ac.d;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((n + FZ_ASSIGN_THREADS - 1) / FZ_ASSIGN_THREADS, (uint64_t)d.n_cus * 8);
-    if (ctx->timing) HIP_TRY(hipEventRecord(d.ev[2], d.stream));
-    hipLaunchKernelGGL(fz_assign_reduce_kernel, dim3(grid), dim3(FZ_ASSIGN_THREADS), 0, d.stream, d_recs, n, L, ac.rag, ac.n, table, npat,
-                       ac.k, ac.d_lo, ac.d_hi);
-    HIP_TRY(hipGetLastError());
+    int rc = assign_launch(ctx, d, [&]() {
+        hipLaunchKernelGGL(fz_assign_reduce_kernel, dim3(assign_grid(d, n)), dim3(FZ_ASSIGN_THREADS), 0, d.stream, d_recs, n, L, ac.rag, ac.n,
+                           table, npat, ac.k, ac.d_lo, ac.d_hi);
+    });
+    if (rc) return rc;
     if (ctx->timing) {
-        HIP_TRY(hipEventRecord(d.ev[3], d.stream));
         HIP_TRY(hipEventSynchronize(d.ev[3]));
-        float v = 0;
-        if (hipEventElapsedTime(&v, d.ev[2], d.ev[3]) == hipSuccess) ac.fold_ms += v;
-        (void)hipGetLastError();
+        ac.fold_ms += span_ms(d.ev[2], d.ev[3]);
     }
     return FZ_OK;
 }
@@ -3842,10 +3913,9 @@ static int assign_fold_host(fz_ctx *ctx, AssignCall &ac, const FzRec *recs, uint
     DevState &d = *ac.d;
     HIP_TRY(hipSetDevice(d.device));
     if (d.assign_rec_cap < n) {
-        if (d.d_assign_recs) { HIP_TRY(hipFree(d.d_assign_recs)); d.d_assign_recs = nullptr; d.assign_rec_cap = 0; }
         const uint64_t cap = std::max<uint64_t>(n + n / 2, 4096);
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d.d_assign_recs), (size_t)cap * sizeof(FzRec)));
-        d.assign_rec_cap = cap;
+        int rc = grow_device(d, d.d_assign_recs, d.assign_rec_cap, cap, cap * sizeof(FzRec));
+        if (rc) return rc;
     }
     for (uint64_t i = 0; i < n; ++i) ac.folded += recs[i].dist != FZ_REC_NONE && recs[i].dist <= ac.k;
     HIP_TRY(hipMemcpyAsync(d.d_assign_recs, recs, (size_t)n * sizeof(FzRec), hipMemcpyHostToDevice, d.stream));
@@ -3923,17 +3993,8 @@ int fz_batch_search(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8_t *p,
     std::vector<uint32_t> fin_seq;
     int rc = batch_search_impl(ctx, batch, mode, p, m, k, reduced, fin, fin_seq);
     if (rc) return rc;
-    void *mem = nullptr, *smem_ = nullptr;
-    rc = alloc_out(fin.size(), sizeof(fz_match), &mem);
+    rc = mp_pack(&fin, &fin_seq, 1, out, seq_of, nullptr);
     if (rc) return rc;
-    rc = alloc_out(fin_seq.size(), sizeof(uint32_t), &smem_);
-    if (rc) { release_out(mem); return rc; }
-    if (!fin.empty()) {
-        memcpy(mem, fin.data(), fin.size() * sizeof(fz_match));
-        memcpy(smem_, fin_seq.data(), fin_seq.size() * sizeof(uint32_t));
-    }
-    *out = static_cast<fz_match *>(mem);
-    *seq_of = static_cast<uint32_t *>(smem_);
     *n = fin.size();
     return FZ_OK;
 }
@@ -3946,27 +4007,8 @@ int fz_batch_search_multi(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8
                           int reduced, fz_match **out, uint32_t **seq_of, uint64_t **out_offs) {
     if (!out || !seq_of || !out_offs) return fail(FZ_EINVAL, "null argument");
     *out = nullptr; *seq_of = nullptr; *out_offs = nullptr;
-    if (!ctx || !batch || batch->ctx != ctx) return fail(FZ_EINVAL, "bad ctx/seq handle");
-    if (mode != FZ_MODE_LEV && mode != FZ_MODE_SUBS) return fail(FZ_EINVAL, "mode must be Levenshtein or substitutions-only");
-    int rc = batch_single_device(ctx, batch);
+    int rc = mp_admit(ctx, batch, mode, pats, offs, n_pats, k, "fz_batch_search_multi");
     if (rc) return rc;
-    if (!batch->is_batch) return fail(FZ_EINVAL, "fz_batch_search_multi takes a batch handle (fz_batch_upload)");
-    if (ctx->npend) return fail(FZ_EINVAL, "a search started with fz_lev_ngrams_begin is still in flight");
-    if (ctx->stream_inflight) return fail(FZ_EINVAL, "a file stream of this context has a batch in flight (finish or close it first)");
-    rc = mp_check_lists(pats, offs, n_pats);
-    if (rc) return rc;
-    const bool subs = mode == FZ_MODE_SUBS;
-    {   // every pattern passes the single call's checks before anything is searched
-        BatchScope scope(ctx);
-        for (uint32_t i = 0; i < n_pats; ++i) {
-            const uint64_t m = offs[i + 1] - offs[i];
-            if (m > FZ_MAX_M_ANY) return fail(FZ_EUNSUPPORTED, "subsequence longer than %u bytes", FZ_MAX_M_ANY);
-            Search q;
-            rc = subs ? subs_plan(ctx, batch, m ? pats + offs[i] : nullptr, (uint32_t)m, k, q)
-                      : lev_plan(ctx, batch, m ? pats + offs[i] : nullptr, (uint32_t)m, k, q);
-            if (rc) return rc;
-        }
-    }
     std::vector<MpGroup> groups;
     std::vector<uint32_t> group_of;
     mp_plan(mode, pats, offs, n_pats, k, groups, group_of);
@@ -3974,15 +4016,12 @@ int fz_batch_search_multi(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8
     std::vector<std::vector<uint32_t>> fin_seq(n_pats);
     MpTotals tot;
     uint32_t form = FZ_FORM_NONE;
-    for (uint32_t i = 0; i < n_pats; ++i) {
-        if (group_of[i] != 0xffffffffu) continue;
-        rc = batch_search_impl(ctx, batch, mode, pats + offs[i], (uint32_t)(offs[i + 1] - offs[i]), k, reduced, fin[i], fin_seq[i]);
-        if (rc) return rc;
-        tot.bytes += ctx->stats.bytes_scanned; tot.hits += ctx->stats.ngram_hits; tot.rows += ctx->stats.raw_matches;
-        tot.launches += ctx->stats.filter_launches;
-        if (ctx->stats.verify_form != FZ_FORM_NONE) form = ctx->stats.verify_form;
-    }
-    ctx->view = nullptr; ctx->view_n = 0; ctx->rows_ready = false;
+    rc = mp_run_solo(ctx, group_of, tot, form, /* form_none_too = */ false, [&](uint32_t i, bool &) {
+        int src = batch_search_impl(ctx, batch, mode, pats + offs[i], (uint32_t)(offs[i + 1] - offs[i]), k, reduced, fin[i], fin_seq[i]);
+        if (src == FZ_OK) tot.rows += ctx->stats.raw_matches;
+        return src;
+    });
+    if (rc) return rc;
     if (!groups.empty() && batch->n_seqs && batch->n) {
         std::vector<std::vector<fz_match>> rows(n_pats);           // global coordinates, in-memory order
         for (const MpGroup &g : groups) {
@@ -3996,40 +4035,9 @@ int fz_batch_search_multi(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8
             }
         }
     }
-    uint64_t total = 0;
-    for (uint32_t i = 0; i < n_pats; ++i) total += fin[i].size();
-    void *mem = nullptr, *smem_ = nullptr, *omem = nullptr;
-    rc = alloc_out(total, sizeof(fz_match), &mem);
+    rc = mp_pack(fin.data(), fin_seq.data(), n_pats, out, seq_of, out_offs);
     if (rc) return rc;
-    rc = alloc_out(total, sizeof(uint32_t), &smem_);
-    if (rc) { release_out(mem); return rc; }
-    rc = alloc_out((uint64_t)n_pats + 1, sizeof(uint64_t), &omem);
-    if (rc) { release_out(mem); release_out(smem_); return rc; }
-    fz_match *mo = static_cast<fz_match *>(mem);
-    uint32_t *so = static_cast<uint32_t *>(smem_);
-    uint64_t *oo = static_cast<uint64_t *>(omem);
-    uint64_t at = 0;
-    for (uint32_t i = 0; i < n_pats; ++i) {
-        oo[i] = at;
-        if (!fin[i].empty()) {
-            memcpy(mo + at, fin[i].data(), fin[i].size() * sizeof(fz_match));
-            memcpy(so + at, fin_seq[i].data(), fin_seq[i].size() * sizeof(uint32_t));
-        }
-        at += fin[i].size();
-    }
-    oo[n_pats] = at;
-    *out = mo; *seq_of = so; *out_offs = oo;
-    memset(&ctx->stats, 0, sizeof ctx->stats);
-    ctx->tref.clear();
-    ctx->stats.n_devices = (uint32_t)ctx->devs.size();
-    ctx->stats.filter_launches = tot.launches;
-    ctx->stats.bytes_scanned = tot.bytes;
-    ctx->stats.ngram_hits = tot.hits;
-    ctx->stats.raw_matches = tot.rows;
-    ctx->stats.filter_ms = tot.filter_ms;
-    ctx->stats.verify_ms = tot.verify_ms;
-    ctx->stats.device_ms = tot.filter_ms + tot.verify_ms;
-    ctx->stats.verify_form = form;
+    mp_publish(ctx, tot, tot.rows, form);
     return FZ_OK;
 }
 
@@ -4041,27 +4049,8 @@ int fz_batch_assign(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8_t *pa
     static_assert(sizeof(fz_assign) == sizeof(FzAssignRow) && sizeof(fz_assign) == 16, "the kernel writes the C-ABI's rows");
     if (!out) return fail(FZ_EINVAL, "null argument");
     *out = nullptr;
-    if (!ctx || !batch || batch->ctx != ctx) return fail(FZ_EINVAL, "bad ctx/seq handle");
-    if (mode != FZ_MODE_LEV && mode != FZ_MODE_SUBS) return fail(FZ_EINVAL, "mode must be Levenshtein or substitutions-only");
-    int rc = batch_single_device(ctx, batch);
+    int rc = mp_admit(ctx, batch, mode, pats, offs, n_pats, k, "fz_batch_assign");
     if (rc) return rc;
-    if (!batch->is_batch) return fail(FZ_EINVAL, "fz_batch_assign takes a batch handle (fz_batch_upload)");
-    if (ctx->npend) return fail(FZ_EINVAL, "a search started with fz_lev_ngrams_begin is still in flight");
-    if (ctx->stream_inflight) return fail(FZ_EINVAL, "a file stream of this context has a batch in flight (finish or close it first)");
-    rc = mp_check_lists(pats, offs, n_pats);
-    if (rc) return rc;
-    const bool subs = mode == FZ_MODE_SUBS;
-    {   // every pattern passes the single call's checks before anything is searched
-        BatchScope scope(ctx);
-        for (uint32_t i = 0; i < n_pats; ++i) {
-            const uint64_t m = offs[i + 1] - offs[i];
-            if (m > FZ_MAX_M_ANY) return fail(FZ_EUNSUPPORTED, "subsequence longer than %u bytes", FZ_MAX_M_ANY);
-            Search q;
-            rc = subs ? subs_plan(ctx, batch, m ? pats + offs[i] : nullptr, (uint32_t)m, k, q)
-                      : lev_plan(ctx, batch, m ? pats + offs[i] : nullptr, (uint32_t)m, k, q);
-            if (rc) return rc;
-        }
-    }
     // the domain of the tables' keys (fz_device.h: fz_assign_key)
     if (k > FZ_ASSIGN_MAX_K) return fail(FZ_EUNSUPPORTED, "best-pattern assignment takes budgets up to %u", FZ_ASSIGN_MAX_K);
     if (n_pats > FZ_ASSIGN_MAX_PATS) return fail(FZ_EUNSUPPORTED, "best-pattern assignment takes at most %u patterns", FZ_ASSIGN_MAX_PATS);
@@ -4073,9 +4062,7 @@ int fz_batch_assign(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8_t *pa
     struct Guard { void *p; ~Guard() { if (p) release_out(p); } } guard{mem};
     fz_assign *rows = static_cast<fz_assign *>(mem);
     ctx->view = nullptr; ctx->view_n = 0; ctx->rows_ready = false;
-    memset(&ctx->stats, 0, sizeof ctx->stats);
-    ctx->tref.clear();
-    ctx->stats.n_devices = (uint32_t)ctx->devs.size();
+    mp_publish(ctx, MpTotals(), 0, FZ_FORM_NONE);
     if (n_pats == 0 || n_seqs == 0 || batch->n == 0) {         // nothing can match: nothing is launched
         for (uint64_t j = 0; j < n_seqs; ++j) { rows[j].pattern = -1; rows[j].dist = 0; rows[j].tied = 0; rows[j].start = 0; rows[j].end = 0; }
         guard.p = nullptr;
@@ -4103,12 +4090,8 @@ int fz_batch_assign(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8_t *pa
     // lo | hi | rows | pattern lengths | aux tables (8-, 4-, 4-, 4-, 4-byte alignment; lo and hi are filled by one memset)
     const uint64_t o_hi = n_seqs * 8, o_rows = o_hi + n_seqs * 4, o_pm = o_rows + n_seqs * sizeof(FzAssignRow);
     const uint64_t o_pat = o_pm + (uint64_t)n_pats * 4, need = o_pat + table.size() * sizeof(FzAssignPat);
-    if (d.assign_cap < need) {
-        if (d.d_assign) { HIP_TRY(hipFree(d.d_assign)); d.d_assign = nullptr; d.assign_cap = 0; }
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(&d.d_assign), (size_t)need);
-        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? FZ_ENOMEM : FZ_EDEVICE, "assignment tables: %s", hipGetErrorString(e));
-        d.assign_cap = need;
-    }
+    rc = grow_device(d, d.d_assign, d.assign_cap, need, need);
+    if (rc) return rc;
     AssignCall ac;
     ac.d = &d;
     ac.rag = fz_ragged(sh.geom);
@@ -4128,24 +4111,14 @@ int fz_batch_assign(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8_t *pa
     uint32_t form = FZ_FORM_NONE;
     std::vector<fz_match> no_rows;
     std::vector<uint32_t> no_seq;
-    for (uint32_t i = 0; i < n_pats; ++i) {
-        if (group_of[i] != 0xffffffffu) continue;
-        rc = batch_search_impl(ctx, batch, mode, pats + offs[i], pm[i], k, 0, no_rows, no_seq, &ac,
-                               ac.d_pat + groups.size() * FZ_MP_MAX_PATS + i);
-        if (rc) return rc;
-        tot.bytes += ctx->stats.bytes_scanned; tot.hits += ctx->stats.ngram_hits;
-        tot.launches += ctx->stats.filter_launches;
-        if (ctx->stats.verify_form != FZ_FORM_NONE) form = ctx->stats.verify_form;
-    }
-    ctx->view = nullptr; ctx->view_n = 0; ctx->rows_ready = false;
-    std::vector<uint32_t> desc;
+    rc = mp_run_solo(ctx, group_of, tot, form, /* form_none_too = */ false, [&](uint32_t i, bool &) {
+        return batch_search_impl(ctx, batch, mode, pats + offs[i], pm[i], k, 0, no_rows, no_seq, &ac, ac.d_pat + groups.size() * FZ_MP_MAX_PATS + i);
+    });
+    if (rc) return rc;
     for (size_t gi = 0; gi < groups.size(); ++gi) {
         const MpGroup &g = groups[gi];
-        uint32_t nent = 0, max_m = 0, sigma = 0;
-        rc = mp_describe_group(pats, offs, g, desc, &nent, &max_m, &sigma);
-        if (rc) return rc;
         uint64_t nr = 0;
-        rc = mp_launch_shard(ctx, sh, mode, desc.data(), nent, k, g.L, max_m, sigma, &nr, tot, true);
+        rc = mp_launch_group(ctx, sh, mode, pats, offs, k, g, &nr, tot, true);
         if (rc) return rc;
         // the attempt that did not overflow: its records, where they lie
         rc = assign_fold_device(ctx, ac, reinterpret_cast<const FzRec *>(d.d_mp_recs), nr, g.L, ac.d_pat + gi * FZ_MP_MAX_PATS, FZ_MP_MAX_PATS);
@@ -4153,33 +4126,17 @@ int fz_batch_assign(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8_t *pa
         ac.folded += nr;
         form = FZ_FORM_KERNEL;
     }
-    {
-        const uint32_t grid = (uint32_t)std::min<uint64_t>((n_seqs + FZ_ASSIGN_THREADS - 1) / FZ_ASSIGN_THREADS, (uint64_t)d.n_cus * 8);
-        if (ctx->timing) HIP_TRY(hipEventRecord(d.ev[2], d.stream));
-        hipLaunchKernelGGL(fz_assign_finish_kernel, dim3(grid), dim3(FZ_ASSIGN_THREADS), 0, d.stream, ac.d_lo, ac.d_hi, n_seqs, ac.d_pm, k, ac.d_rows);
-        HIP_TRY(hipGetLastError());
-        if (ctx->timing) HIP_TRY(hipEventRecord(d.ev[3], d.stream));
-        HIP_TRY(hipMemcpyAsync(rows, ac.d_rows, (size_t)n_seqs * sizeof(fz_assign), hipMemcpyDeviceToHost, d.stream));
-        HIP_TRY(hipStreamSynchronize(d.stream));
-        if (ctx->timing) {
-            float v = 0;
-            if (hipEventElapsedTime(&v, d.ev[2], d.ev[3]) == hipSuccess) ac.fold_ms += v;
-            (void)hipGetLastError();
-        }
-    }
+    rc = assign_launch(ctx, d, [&]() {
+        hipLaunchKernelGGL(fz_assign_finish_kernel, dim3(assign_grid(d, n_seqs)), dim3(FZ_ASSIGN_THREADS), 0, d.stream, ac.d_lo, ac.d_hi, n_seqs,
+                           ac.d_pm, k, ac.d_rows);
+    });
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(rows, ac.d_rows, (size_t)n_seqs * sizeof(fz_assign), hipMemcpyDeviceToHost, d.stream));
+    HIP_TRY(hipStreamSynchronize(d.stream));
+    if (ctx->timing) ac.fold_ms += span_ms(d.ev[2], d.ev[3]);
     guard.p = nullptr;
     *out = rows;
-    memset(&ctx->stats, 0, sizeof ctx->stats);
-    ctx->tref.clear();
-    ctx->stats.n_devices = (uint32_t)ctx->devs.size();
-    ctx->stats.filter_launches = tot.launches;
-    ctx->stats.bytes_scanned = tot.bytes;
-    ctx->stats.ngram_hits = tot.hits;
-    ctx->stats.raw_matches = ac.folded;
-    ctx->stats.filter_ms = tot.filter_ms;
-    ctx->stats.verify_ms = tot.verify_ms + ac.fold_ms;
-    ctx->stats.device_ms = tot.filter_ms + tot.verify_ms + ac.fold_ms;
-    ctx->stats.verify_form = form;
+    mp_publish(ctx, tot, ac.folded, form, ac.fold_ms);
     return FZ_OK;
 }
 
@@ -4222,51 +4179,7 @@ int fz_debug_assign_fold(const uint64_t *offs, uint64_t n_seqs, const void *recs
 }
 
 static int generic_ngrams_impl(fz_ctx *ctx, fz_seq *seq, const uint8_t *p, uint32_t m, uint32_t max_subs, uint32_t max_ins,
-                               uint32_t max_dels, uint32_t max_l, fz_match **out, uint64_t *n, int *found, bool consolidated = false);
-
-int fz_generic_ngrams_consolidated(fz_ctx *ctx, fz_seq *seq, const uint8_t *p, uint32_t m, uint32_t max_subs, uint32_t max_ins,
-                                   uint32_t max_dels, uint32_t max_l, fz_match **out, uint64_t *n) {
-    if (!out || !n) return fail(FZ_EINVAL, "null argument");
-    *out = nullptr; *n = 0;
-    return generic_ngrams_impl(ctx, seq, p, m, max_subs, max_ins, max_dels, max_l, out, n, nullptr, true);
-}
-
-int fz_generic_ngrams(fz_ctx *ctx, fz_seq *seq, const uint8_t *p, uint32_t m, uint32_t max_subs, uint32_t max_ins,
-                      uint32_t max_dels, uint32_t max_l, fz_match **out, uint64_t *n) {
-    if (!out || !n) return fail(FZ_EINVAL, "null argument");
-    *out = nullptr; *n = 0;
-    return generic_ngrams_impl(ctx, seq, p, m, max_subs, max_ins, max_dels, max_l, out, n, nullptr);
-}
-
-int fz_generic_ngrams_any(fz_ctx *ctx, fz_seq *seq, const uint8_t *p, uint32_t m, uint32_t max_subs, uint32_t max_ins,
-                          uint32_t max_dels, uint32_t max_l, int *found) {
-    if (!found) return fail(FZ_EINVAL, "null argument");
-    *found = 0;
-    return generic_ngrams_impl(ctx, seq, p, m, max_subs, max_ins, max_dels, max_l, nullptr, nullptr, found);
-}
-
-// What a finished generic search hands over: the raw stream in the reference's order, or — consolidated — the device's
-// (hull, best match) pairs, one or a few per n-gram hit, through the second stage of the consolidation.
-static int emit_generic_result(fz_ctx *ctx, fz_seq *seq, const Search &q, const std::vector<FzGenRec> &recs_vec, bool consolidated,
-                               fz_match **out, uint64_t *n) {
-    const uint32_t L = q.plan.L, k = q.k;
-    if (!consolidated) return emit_generic(ctx, seq, recs_vec, L, k, out, n, nullptr);
-    const FzGenRec *prs = ctx->gen_view ? ctx->gen_view : recs_vec.data();
-    const size_t npr = ctx->gen_view ? (size_t)ctx->gen_view_n : recs_vec.size();
-    static thread_local std::vector<Hull> hulls;
-    hulls.clear();
-    hulls.reserve(npr);
-    for (size_t i = 0; i < npr; ++i) {
-        const FzOutRow best = fz_gen_row(prs[i].key, L, k, 0, prs[i].se, prs[i].dist);
-        const FzOutRow hull = fz_gen_row(prs[i].key, L, k, 0, prs[i].win, 0);
-        hulls.push_back(Hull{hull.start, hull.end, fz_match{best.start, best.end, best.dist, best.block}});
-    }
-    ctx->stats.raw_matches = npr;
-    return consolidate_hulls(hulls, out, n);
-}
-
-static int generic_ngrams_impl(fz_ctx *ctx, fz_seq *seq, const uint8_t *p, uint32_t m, uint32_t max_subs, uint32_t max_ins,
-                               uint32_t max_dels, uint32_t max_l, fz_match **out, uint64_t *n, int *found, bool consolidated) {
+                               uint32_t max_dels, uint32_t max_l, fz_match **out, uint64_t *n, int *found, bool consolidated = false) {
     Search q;
     int rc = generic_plan(ctx, seq, p, m, max_subs, max_ins, max_dels, max_l, q);
     if (rc) return rc;
@@ -4295,6 +4208,27 @@ static int generic_ngrams_impl(fz_ctx *ctx, fz_seq *seq, const uint8_t *p, uint3
     rc = emit_generic_result(ctx, seq, q, recs_vec, consolidated, out, n);
     tr.mark("generic: rows");
     return rc;
+}
+
+int fz_generic_ngrams_consolidated(fz_ctx *ctx, fz_seq *seq, const uint8_t *p, uint32_t m, uint32_t max_subs, uint32_t max_ins,
+                                   uint32_t max_dels, uint32_t max_l, fz_match **out, uint64_t *n) {
+    if (!out || !n) return fail(FZ_EINVAL, "null argument");
+    *out = nullptr; *n = 0;
+    return generic_ngrams_impl(ctx, seq, p, m, max_subs, max_ins, max_dels, max_l, out, n, nullptr, true);
+}
+
+int fz_generic_ngrams(fz_ctx *ctx, fz_seq *seq, const uint8_t *p, uint32_t m, uint32_t max_subs, uint32_t max_ins,
+                      uint32_t max_dels, uint32_t max_l, fz_match **out, uint64_t *n) {
+    if (!out || !n) return fail(FZ_EINVAL, "null argument");
+    *out = nullptr; *n = 0;
+    return generic_ngrams_impl(ctx, seq, p, m, max_subs, max_ins, max_dels, max_l, out, n, nullptr);
+}
+
+int fz_generic_ngrams_any(fz_ctx *ctx, fz_seq *seq, const uint8_t *p, uint32_t m, uint32_t max_subs, uint32_t max_ins,
+                          uint32_t max_dels, uint32_t max_l, int *found) {
+    if (!found) return fail(FZ_EINVAL, "null argument");
+    *found = 0;
+    return generic_ngrams_impl(ctx, seq, p, m, max_subs, max_ins, max_dels, max_l, nullptr, nullptr, found);
 }
 
 }  // extern "C"

@@ -446,6 +446,54 @@ def test_refusals_and_state(engine, force_pass):
     hs.release()
 
 
+def test_timing_totals(engine, force_pass):
+    """The device times of the three list-of-patterns calls — the plain sequence's, the batch's and the assignment — with four
+    patterns that ride one pass and one (n-grams of 2: below the batched domain) that is searched on its own: with timing on
+    both spans are measured and device_ms is their sum; with timing off all three are exactly 0 and the results the same."""
+    force_pass(True)
+    rnd = random.Random(200)
+    k = 2
+    seqs = [_rand(rnd, b"ACGT", 200) for _ in range(20)]
+    pats = [seqs[4][50:70], seqs[9][100:120], seqs[0][:20], seqs[19][180:], seqs[12][30:37]]
+    blob, offs = _pack(seqs)
+    lib = _native.load_library()
+    hb = engine.upload_batch(blob, offs)
+    hs = engine.upload(blob)
+
+    def plain(mode):
+        rows, bounds = engine.multi_rows_call(hs, pats, k, fn=None if mode == LEV else lib.fz_subs_ngrams_multi_best)
+        return rows.to_array().tolist(), list(bounds)
+
+    def batch(mode):
+        return [_flat(*g) for g in engine.batch_search_multi(hb, mode, pats, k)]
+
+    def assign(mode):
+        return engine.batch_assign(hb, mode, pats, k).tolist()
+
+    try:
+        for mode in (LEV, SUBS):
+            group_of, ng = _native.multi_plan(pats, k, mode)
+            assert ng == 1 and group_of[:4] == [0] * 4 and group_of[4] is None, "four patterns in a pass, one on its own"
+            for call in (plain, batch, assign):
+                engine.set_timing(1)
+                timed = call(mode)
+                st = engine.stats()
+                print(call.__name__, mode, st["filter_ms"], st["verify_ms"], st["device_ms"], st["n_devices"])
+                assert st["filter_ms"] > 0 and st["verify_ms"] > 0
+                assert st["device_ms"] == pytest.approx(st["filter_ms"] + st["verify_ms"], rel=1e-9, abs=0)
+                assert st["n_devices"] == 1
+                engine.set_timing(0)
+                untimed = call(mode)
+                st = engine.stats()
+                assert st["filter_ms"] == 0 and st["verify_ms"] == 0 and st["device_ms"] == 0
+                assert st["n_devices"] == 1
+                assert untimed == timed and len(timed) > 0
+    finally:
+        engine.set_timing(1)
+        hb.release()
+        hs.release()
+
+
 # ---- the public call ------------------------------------------------------------------------------------------------
 
 def _reads(rnd, pats, alpha="ACGT"):
