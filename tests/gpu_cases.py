@@ -2,7 +2,8 @@
 of the library are process-wide statics read from the environment (FZ_FORCE_BIG_VERIFY, FZ_NO_SLOT_AND,
 FZ_MAX_BLOCKS, FZ_NO_DIRECT), so a test that wants them set starts a fresh interpreter.  Prints "OK <n cases> <n records>".
 The seam sweeps of tests/seam_case.py run through here as well (`seams <route> <CUs>`: the route's small texts, then the
-text with several tiles per workgroup; in-process from tests/test_gpu_scan_seams.py for the routes that need no switch)."""
+text with several tiles per workgroup; in-process from tests/test_gpu_scan_seams.py for the routes that need no switch), and
+those of tests/batch_seam_case.py (`batch-seams <route> <CUs>`)."""
 import io
 import os
 import random
@@ -244,6 +245,124 @@ def run_seam_route_iterations(engine, route, n_cus, text=None, bg=None):
     finally:
         case.bg.restore(case.text, case.plants)
     return "%s | grid %d, %d MiB" % (sc.coverage_line(route.name, case.coverage, route.form), case.plan[0], n >> 20), rows, case.text, case.bg
+
+
+# -- the batch seam sweep (tests/batch_seam_case.py) ---------------------------------------------------------------------------
+def batch_rows(engine, h, mode, p, k, reduced):
+    """fz_batch_search -> rows (sequence, start, end, dist, block); seq_of is non-decreasing."""
+    import numpy as np
+    rows, seq_of = engine.batch_search(h, mode, p, k, reduced=reduced)
+    assert len(rows) == len(seq_of)
+    assert np.all(np.diff(seq_of.astype(np.int64)) >= 0), "seq_of is non-decreasing"
+    return [(int(j),) + tuple(int(x) for x in r) for j, r in zip(seq_of.tolist(), rows.tolist())]
+
+
+def batch_form(route, p, n, n_cus):
+    """The verify_form a batch of n packed bytes must report: what the plan hook names for the unsegmented search of the same
+    pattern over the same length (tests/test_gpu_batch.py::test_one_pass pins that a batch plans as that search does) - and
+    that is the form the route is there for."""
+    from tests import seam_case as sc
+    form = sc.scan_plan(p, route.k, n, n_cus)[1] if route.kind == "lev" else route.form
+    assert form == route.form, (route.name, "the plan names form", form)
+    return form
+
+
+def check_batch_seam_case(engine, route, p, cls, seqs, plants, cache, n_cus):
+    """One batch: upload, the raw and the reduced search; the full ordered raw stream with its sequence numbers, the reduced
+    rows, stats()["raw_matches"] and ["verify_form"] against the oracle per sequence.  -> rows compared."""
+    from tests import batch_seam_case as bc
+    mode = bc.MODE[route.kind]
+    blob, offs = bc.pack(seqs)
+    want_raw, want_red = bc.expected(mode, p, seqs, route.k, cache)
+    form = batch_form(route, p, len(blob), n_cus)
+
+    def differ(what, got, want):
+        bad = next((i for i, (a, b) in enumerate(zip(got, want)) if a != b), min(len(got), len(want)))
+        j = (got[bad] if bad < len(got) else want[bad])[0]
+        raise AssertionError("%s %s, %s: %d rows against %d expected, first difference at row %d: %r / %r; plants there (class, d): %r" % (
+            route.name, cls, what, len(got), len(want), bad, got[bad:bad + 2], want[bad:bad + 2], bc.near(plants, seqs, j)))
+
+    h = engine.upload_batch(blob, offs)
+    try:
+        got = batch_rows(engine, h, mode, p, route.k, False)
+        st = engine.stats()
+        if got != want_raw:
+            differ("raw", got, want_raw)
+        assert st["raw_matches"] == len(want_raw), (route.name, cls, "raw_matches", st["raw_matches"], len(want_raw))
+        assert st["verify_form"] == form, (route.name, cls, "verify_form", st["verify_form"], form)
+        if route.kind == "lev" and len(p) // (len(p) // (route.k + 1)) > 16:
+            assert st["filter_launches"] >= 2, (route.name, cls, "more than 16 blocks: a second launch")
+        got = [g[:4] for g in batch_rows(engine, h, mode, p, route.k, True)]
+        if got != want_red:
+            differ("reduced", got, want_red)
+    finally:
+        h.release()
+    return len(want_raw) + len(want_red)
+
+
+def check_batch_public(route, p, seqs, plants):
+    """find_near_matches_batch over the sequences that hold (a part of) a plant against the loop of find_near_matches."""
+    import numpy as np
+    import fuzzysearch_amd as fa
+    offs = np.concatenate([[0], np.cumsum([len(s) for s in seqs])]).astype(np.int64)
+    held = sorted(set(j for pl in plants for j in range(int(np.searchsorted(offs, pl.start, side="right")) - 1,
+                                                          int(np.searchsorted(offs, pl.start + len(pl.data) - 1, side="right")))))
+    step = max(1, len(held) // 48)
+    sub = [seqs[j] for j in held[::step]]
+    kw = dict(max_substitutions=route.k, max_insertions=0, max_deletions=0) if route.kind == "subs" else dict(max_l_dist=route.k)
+    got = fa.find_near_matches_batch(p, sub, **kw)
+    want = [fa.find_near_matches(p, s, **kw) for s in sub]
+    assert got == want, (route.name, "find_near_matches_batch")
+    assert [[x.matched for x in g] for g in got] == [[x.matched for x in w] for w in want], (route.name, "matched")
+    assert sum(len(g) for g in got) > 0
+    return len(sub)
+
+
+def run_batch_seam_route(engine, route, n_cus, public=False, classes=None):
+    """Every batch of one route of tests/batch_seam_case.py (of `classes`) -> (line, searches, rows compared)."""
+    from tests import batch_seam_case as bc
+    from tests import seam_case as sc
+    p = sc.route_pattern(route)
+    cache = {}
+    n_search = n_rows = 0
+    parts = []
+    for cls, seqs, plants, cover in bc.batches(route, p, classes):
+        bc.check_coverage(route, cls, cover, seqs)
+        n_rows += check_batch_seam_case(engine, route, p, cls, seqs, plants, cache, n_cus)
+        n_search += 2
+        parts.append("%s %d seqs %d plants" % (cls, len(seqs), len(plants)))
+        if public and cls == "mid":
+            parts.append("public %d seqs" % check_batch_public(route, p, seqs, plants))
+    return "batch seams %-22s form %s | %s" % (route.name, route.form, "; ".join(parts)), n_search, n_rows
+
+
+def run_batch_noisy(engine, route, n_cus, tiles=3, side=None):
+    """One noisy batch of the route: reads of 30 .. 300 bytes over the pattern's own alphabet (full queues, block-range passes,
+    the slow-tile path).  `side`: 'slotted' / 'compact' - the hit list of fz_batch_verify_wf_kernel on that side of
+    FZ_WF_COMPACT_MIN, by the oracle's own count of n-gram hits AND by the device's (stats()["ngram_hits"], the length of the
+    list the kernel reads; it holds the oracle's hits and those the per-sequence range test then drops).  -> (rows, hits, device hits)."""
+    from tests import batch_seam_case as bc
+    from tests import seam_case as sc
+    p = sc.route_pattern(route)
+    seqs, plants = bc.noisy(route, p, tiles)
+    hits = bc.ngram_hits(p, seqs, route.k)
+    if side == "compact":
+        assert hits > bc.WF_COMPACT_MIN, (route.name, "n-gram hits", hits)
+    if side == "slotted":
+        assert 0 < hits <= bc.WF_COMPACT_MIN, (route.name, "n-gram hits", hits)
+    rows = check_batch_seam_case(engine, route, p, "noisy", seqs, plants, {}, n_cus)
+    assert rows > 0
+    blob, offs = bc.pack(seqs)
+    h = engine.upload_batch(blob, offs)
+    try:
+        engine.batch_search(h, bc.MODE[route.kind], p, route.k)
+        on_device = engine.stats()["ngram_hits"]
+    finally:
+        h.release()
+    if side:
+        assert on_device >= hits, (route.name, "the device lists fewer n-gram hits than the oracle verifies", on_device, hits)
+        assert (on_device > bc.WF_COMPACT_MIN) == (side == "compact"), (route.name, side, on_device)
+    return rows, hits, on_device
 
 
 # -- the file stream (tests/file_seam_case.py) -------------------------------------------------------------------------------
@@ -529,6 +648,16 @@ def main(argv):
         print(line)
         line, rows, _text, _bg = run_seam_route_iterations(eng, route, int(argv[2]))
         n_search, n_rows = n_search + 1, n_rows + rows
+        eng.close()
+        print(line)
+        print("OK %d %d" % (n_search, n_rows))
+        return
+    if what == "batch-seams":
+        # one route of tests/batch_seam_case.py under the process-wide switch it needs (FZ_NO_BITS, FZ_NO_WF_FUSE,
+        # FZ_FORCE_BIG_VERIFY): argv = route name, CU count of the device[, classes]
+        from tests import batch_seam_case as bc
+        eng = _native.Engine([0])
+        line, n_search, n_rows = run_batch_seam_route(eng, bc.route(argv[1]), int(argv[2]), classes=argv[3].split(",") if len(argv) > 3 else None)
         eng.close()
         print(line)
         print("OK %d %d" % (n_search, n_rows))

@@ -707,7 +707,81 @@ static int64_t search_bits_nw(const uint8_t *p, uint32_t m, const uint8_t *t, ui
     return cnt;
 }
 
+// A batch of sequences (fz_device.h: ragged segments) through the per-hit forms with INTERIOR bounds: every n-gram occurrence
+// in the packed bytes is given to its own sequence as the ragged kernel instances do (fz_segment_ragged over ends[] / first[]
+// -> fz_hit_in_range_s -> the verification with (sg.sa, sg.se)).  NW = 0: fz_verify_lev (register band / score ring);
+// NW = 1, 2, 4: fz_verify_lev_bits on a window whose base is computed AS THE PREFETCH COMPUTES IT (fz_kernels.h:
+// fz_window_base(fz_window_lo(a, idx, s, 0)), restated here - the two are __device__ functions): the window of an unsegmented
+// search, which starts below sg.sa and holds the neighbouring sequence's real bytes, so that only the arithmetic of the
+// verification keeps them out.  The packed bytes lie between zero padding as on the device.  Rows in the coordinates of their
+// sequence, block-major over the whole batch (the caller orders them by sequence, stably).
+template <int NW>
+static int64_t search_ragged_nw(const uint8_t *p, uint32_t m, const uint8_t *t, uint64_t n, uint32_t k,
+                                const uint64_t *ends, uint64_t n_seqs, OutRecSeg *out, int64_t cap) {
+    const uint32_t L = m / (k + 1);
+    if (L == 0 || (NW != 0 && m > FZ_BITS_WIDTH(NW ? NW : 1))) return -1;
+    if (n_seqs == 0 || ends[n_seqs - 1] != n) return -2;
+    const uint64_t ntiles = (n + (1ull << FZ_RAG_TILE_BITS) - 1) >> FZ_RAG_TILE_BITS;
+    std::vector<uint32_t> first(ntiles + 1);
+    fz_ragged_first(ends, n_seqs, ntiles, first.data());
+    FzScanArgs a;
+    memset(&a, 0, sizeof a);
+    a.geom.n = n; a.geom.buf_off = 0; a.geom.buf_len = n; a.geom.own_lo = 0; a.geom.own_hi = n;
+    a.geom.seg_stride = 0;
+    a.geom.seg_org = reinterpret_cast<uint64_t>(ends);
+    a.geom.seg_j0 = reinterpret_cast<uint64_t>(first.data());
+    a.geom.seg_j1 = n_seqs;
+    a.mode = FZ_MODE_LEV; a.m = m; a.k = k; a.L = L; a.abs_lo = 0; a.abs_hi = ~0ull;
+    const uint64_t PAD = 512;
+    std::vector<uint8_t> buf(PAD + n + PAD, 0);
+    memcpy(buf.data() + PAD, t, n);
+    FzSeqView view{buf.data() + PAD, 0};
+    HostScores sc;
+    sc.v.assign(2 * k + 4, 0);
+    const HostPeq<(NW ? NW : 1)> peq(p, NW ? m : 1);
+    int64_t cnt = 0;
+    uint32_t g = 0;
+    for (uint32_t s = 0; s + L <= m; s += L, ++g) {
+        for (uint64_t idx = 0; idx + L <= n; ++idx) {
+            if (memcmp(t + idx, p + s, L) != 0) continue;
+            const FzSeg sg = fz_segment_ragged(fz_ragged(a.geom), n, idx);
+            if (!fz_hit_in_range_s(a, s, idx, sg)) continue;
+            FzRec rec;
+            bool ok;
+            if constexpr (NW == 0) {
+                ok = fz_verify_lev<FZ_REG_BAND_MAX>(sc, view, sg.sa, sg.se, p, m, k, L, s, idx, rec);
+            } else {
+                const uint64_t reach = (uint64_t)s + k;
+                const uint64_t wlo = idx > reach ? idx - reach : 0;            // fz_window_lo(a, idx, s, 0), buf_off = 0
+                const uint64_t wbase = wlo & ~(uint64_t)3;                     // fz_window_base
+                auto txt = [&](uint32_t o) -> uint8_t {
+                    const int64_t at = (int64_t)(PAD + wbase) + (int64_t)(int32_t)o;
+                    return at >= 0 && (uint64_t)at < buf.size() ? buf[(size_t)at] : (uint8_t)0xEE;
+                };
+                ok = fz_verify_lev_bits<(NW ? NW : 1)>(peq, txt, wbase, sg.sa, sg.se, m, k, L, s, idx, true, rec);
+            }
+            if (!ok) continue;
+            if (cnt < cap) {
+                out[cnt].start = (int64_t)idx - (int64_t)rec.l - (int64_t)sg.sa;
+                out[cnt].end = (int64_t)idx + L + rec.r - (int64_t)sg.sa;
+                out[cnt].dist = (int32_t)rec.dist;
+                out[cnt].block = (int32_t)g;
+                out[cnt].seg = sg.j;
+            }
+            ++cnt;
+        }
+    }
+    return cnt;
+}
+
 extern "C" {
+int64_t emul_search_ragged(int form, const uint8_t *p, uint32_t m, const uint8_t *t, uint64_t n, uint32_t k,
+                           const uint64_t *ends, uint64_t n_seqs, OutRecSeg *out, int64_t cap) {
+    return form == 0 ? search_ragged_nw<0>(p, m, t, n, k, ends, n_seqs, out, cap)
+         : form == 1 ? search_ragged_nw<1>(p, m, t, n, k, ends, n_seqs, out, cap)
+         : form == 2 ? search_ragged_nw<2>(p, m, t, n, k, ends, n_seqs, out, cap)
+         : form == 4 ? search_ragged_nw<4>(p, m, t, n, k, ends, n_seqs, out, cap) : -3;
+}
 int emul_expand_bits(int NW, const uint8_t *sub, uint32_t sublen, const uint8_t *win, uint32_t winlen, uint32_t budget,
                      uint32_t *dist, uint32_t *consumed) {
     return NW == 1 ? expand_bits_nw<1>(sub, sublen, win, winlen, budget, dist, consumed)

@@ -18,6 +18,11 @@ class OutRec(ctypes.Structure):
     _fields_ = [("start", ctypes.c_int64), ("end", ctypes.c_int64), ("dist", ctypes.c_int32), ("block", ctypes.c_int32)]
 
 
+class OutRecSeq(ctypes.Structure):
+    _fields_ = [("start", ctypes.c_int64), ("end", ctypes.c_int64), ("dist", ctypes.c_int32), ("block", ctypes.c_int32),
+                ("seq", ctypes.c_int64)]
+
+
 @pytest.fixture(scope="module")
 def emul():
     out = os.path.join(tempfile.gettempdir(), "fz_hostemul_%d.so" % os.getpid())
@@ -39,6 +44,9 @@ def emul():
     L.emul_search_bits.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint32,
                                    ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
                                    ctypes.POINTER(OutRec), ctypes.c_int64]
+    L.emul_search_ragged.restype = ctypes.c_int64
+    L.emul_search_ragged.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint32,
+                                     ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(OutRecSeq), ctypes.c_int64]
     yield L
     os.remove(out)
 
@@ -422,3 +430,97 @@ def test_lane_per_cell_expansion_equals_oracle(emul):
         r2 = emul.emul_wf_expand(gw, K, sub, len(sub), longer, len(longer), K, len(win), budget, ctypes.byref(d), ctypes.byref(c))
         assert ((d.value, c.value) if r2 else (None, None)) == want, ("narrowed", gw, K, budget, sub, win, longer)
     assert n_ok > 3000
+
+
+# ---- a batch of sequences: the per-hit forms with interior bounds (fz_device.h: ragged segments) -------------------------------
+RAGGED_FORMS = {0: 128, 4: 32, 1: 64, 2: 128}            # fz_verify_lev; fz_verify_lev_bits on 32-, 64-, 128-bit columns: longest pattern
+
+
+def _search_ragged(L, form, p, seqs, k):
+    """emul_search_ragged over the packed sequences -> rows (sequence, start, end, dist, block) ordered by sequence (stably:
+    block-major inside a sequence, as fz_batch_search orders them)."""
+    import numpy as np
+    blob = b"".join(seqs)
+    ends = np.cumsum([len(s) for s in seqs]).astype(np.uint64)
+    cap = 1 << 16
+    out = (OutRecSeq * cap)()
+    c = L.emul_search_ragged(form, p, len(p), blob, len(blob), k, ends.ctypes.data, len(seqs), out, cap)
+    assert 0 <= c <= cap, c
+    rows = [(out[i].seq, out[i].start, out[i].end, out[i].dist, out[i].block) for i in range(c)]
+    rows.sort(key=lambda r: r[0])
+    return rows
+
+
+def _oracle_per_sequence(p, seqs, k):
+    return [(j,) + tuple(r) for j, s in enumerate(seqs) if s for r in oracle.lev_ngrams_raw(p, s, k)]
+
+
+def _ragged_batch(rnd, top):
+    """A pattern of up to `top` characters, a budget up to 15, sequences of 0 .. m + 2k + 5 bytes with copies of the pattern
+    inside them, flush against their ends and CUT by the seams between them."""
+    sigma = rnd.choice([2, 3, 4, 4, 20])
+    alpha = bytes(rnd.sample(range(1, 256), sigma))
+    k = rnd.choice([1, 1, 2, 2, 3, 4, 5, 8, 15])
+    lo_m = k + 1
+    m = rnd.choice([lo_m, top, rnd.randint(lo_m, max(lo_m, top)), rnd.randint(lo_m, max(lo_m, min(top, 30)))])
+    if m > top or m < lo_m:
+        return None
+    p = bytes(rnd.choice(alpha) for _ in range(m))
+    seqs = []
+    for _ in range(rnd.randint(1, 8)):
+        n = rnd.choice([0, 0, rnd.randint(0, m + 2 * k + 5), rnd.randint(0, m + 2 * k + 5), rnd.randint(max(0, m - k - 1), m + k + 1)])
+        t = bytearray(rnd.choice(alpha) for _ in range(n))
+        if rnd.random() < 0.6:
+            v = _edited(rnd, p, alpha, rnd.randint(0, k), 0)
+            if len(v) <= n:
+                at = rnd.choice([0, n - len(v), rnd.randint(0, n - len(v))])
+                t[at:at + len(v)] = v
+        seqs.append(t)
+    for j in range(len(seqs) - 1):                         # a copy cut by the seam behind sequence j (over empty sequences too)
+        if rnd.random() < 0.5 and m > 1:
+            cut = rnd.randint(1, m - 1)
+            a = seqs[j]
+            b = next((s for s in seqs[j + 1:] if len(s)), None)
+            if b is not None and len(a) >= cut and len(b) >= m - cut:
+                a[len(a) - cut:] = p[:cut]
+                b[:m - cut] = p[cut:]
+    return p, [bytes(s) for s in seqs], k
+
+
+@pytest.mark.parametrize("form", sorted(RAGGED_FORMS))
+def test_ragged_per_hit_verification_equals_oracle_per_sequence(emul, form):
+    """fz_segment_ragged -> fz_hit_in_range_s -> fz_verify_lev / fz_verify_lev_bits<NW> with a sequence's interior bounds, the
+    bit-vector forms on the window an unsegmented search would prefetch (its base below sa, the neighbour's real bytes in it):
+    3000 random batches per form against the oracle run on every sequence alone."""
+    rnd = random.Random(70 + form)
+    done = rows = seams_cut = 0
+    while done < 3000:
+        case = _ragged_batch(rnd, RAGGED_FORMS[form])
+        if case is None:
+            continue
+        p, seqs, k = case
+        want = _oracle_per_sequence(p, seqs, k)
+        if len(want) > 20000:
+            continue
+        assert _search_ragged(emul, form, p, seqs, k) == want, (form, p, seqs, k)
+        done += 1
+        rows += len(want)
+        seams_cut += oracle.lev_ngrams_raw(p, b"".join(seqs), k) != [r[1:] for r in want]
+    assert rows > 3000 and seams_cut > 300, (rows, seams_cut)    # (batches on which a seam-blind search returns other rows)
+
+
+@pytest.mark.parametrize("name, forms", [("band-L6-k2", (0, 4)), ("bits64-54-8", (0, 1)), ("bits128-65-10", (0, 2))])
+def test_ragged_per_hit_verification_on_the_seam_sweep(emul, name, forms):
+    """The deterministic classes of tests/batch_seam_case.py whose seams need no device: `short` (both clamps in one window),
+    `empty` (equal ends[]), and `tile` (a seam on a multiple of 16 384: fz_ragged_first's first[] table)."""
+    from tests import batch_seam_case as bc
+    r = bc.route(name)
+    p = bc.sc.route_pattern(r)
+    cache = {}
+    for cls in ("short", "empty", "tile"):
+        seqs, _plants, _cover = bc.build(r, cls, p)
+        want, _red = bc.expected(bc.LEV, p, seqs, r.k, cache)
+        assert want
+        for form in forms:
+            got = _search_ragged(emul, form, p, seqs, r.k)
+            assert got == want, (name, cls, form, next((a, b) for a, b in zip(got + [None], want + [None]) if a != b))
