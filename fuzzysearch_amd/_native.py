@@ -34,6 +34,8 @@ EXPORTED_SYMBOLS = (
     "fz_batch_assign", "fz_debug_assign_fold",
     "fz_batch_upload_records", "fz_batch_tables", "fz_debug_batch_bytes", "fz_debug_records_split", "fz_debug_scan_items",
     "fz_debug_records_ms",
+    "fz_subs_ngrams_multi_cls", "fz_subs_ngrams_multi_best_cls", "fz_batch_search_multi_cls", "fz_batch_assign_cls",
+    "fz_debug_multi_plan_cls",
 )
 
 
@@ -204,6 +206,18 @@ def load_library():
             L.fz_debug_scan_items.argtypes = []
             L.fz_debug_records_ms.restype = ci
             L.fz_debug_records_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
+        if hasattr(L, "fz_subs_ngrams_multi_cls"):          # (absent from builds of earlier rounds named by FUZZYSEARCH_HIP_LIB for an A/B)
+            for fn in (L.fz_subs_ngrams_multi_cls, L.fz_subs_ngrams_multi_best_cls):
+                fn.restype = ci
+                fn.argtypes = [vp, vp, u8p, u64p, u32, u32, u8p, u8p, mpp, ctypes.POINTER(u64p)]
+            L.fz_batch_search_multi_cls.restype = ci
+            L.fz_batch_search_multi_cls.argtypes = [vp, vp, u8p, u64p, u32, u32, u8p, u8p, ci, mpp, ctypes.POINTER(ctypes.POINTER(u32)),
+                                                    ctypes.POINTER(u64p)]
+            L.fz_batch_assign_cls.restype = ci
+            L.fz_batch_assign_cls.argtypes = [vp, vp, u8p, u64p, u32, u32, u8p, u8p, ctypes.POINTER(vp)]
+            L.fz_debug_multi_plan_cls.restype = ci
+            L.fz_debug_multi_plan_cls.argtypes = [u8p, u64p, u32, u32, u8p, u8p, ctypes.POINTER(u32), ctypes.POINTER(u32),
+                                                  ctypes.POINTER(u32), ctypes.POINTER(u32)]
         L.fz_subs_ngrams_best.restype = ci
         L.fz_subs_ngrams_best.argtypes = [vp, vp, u8p, u32, u32, mpp, u64p]
         L.fz_generic_ngrams_consolidated.restype = ci
@@ -439,6 +453,28 @@ def multi_plan(patterns, k, mode=MODE_LEV):
     ng = ctypes.c_uint32(0)
     _check(L.fz_debug_multi_plan_mode(mode, blob, offs, n, k, group_of, ctypes.byref(ng)))
     return [None if group_of[i] == 0xffffffff else group_of[i] for i in range(n)], ng.value
+
+
+def _class_entry(L, name):
+    """The class form `name` of the loaded library; a build without it cannot search classes (there is no fallback)."""
+    fn = getattr(L, name, None)
+    if fn is None:
+        raise HipEngineError("this libfzhip.so has no %s: it was built before symbol classes" % name)
+    return fn
+
+
+def multi_plan_classes(patterns, k, tables):
+    """fz_debug_multi_plan_cls (no device): -> (group of every pattern, table entries of every pattern, entries of every
+    group) of a class call with tables = (pmask, tmask), two bytes objects of 256.  Raises what the class calls raise."""
+    L = load_library()
+    blob, offs = pack_patterns(patterns)
+    n = len(patterns)
+    group_of = (ctypes.c_uint32 * max(1, n))()
+    per_pat = (ctypes.c_uint32 * max(1, n))()
+    per_group = (ctypes.c_uint32 * max(1, n))()
+    ng = ctypes.c_uint32(0)
+    _check(_class_entry(L, "fz_debug_multi_plan_cls")(blob, offs, n, k, tables[0], tables[1], group_of, ctypes.byref(ng), per_pat, per_group))
+    return list(group_of[:n]), list(per_pat[:n]), list(per_group[:ng.value])
 
 
 def batch_segment(offs, idx):
@@ -821,6 +857,38 @@ class Engine(object):
         ptr, seq_of, bounds = self._batch_multi_call(batch, mode, patterns, k, reduced)
         return OwnedRows(self._lib, ptr, bounds[-1]), seq_of, bounds
 
+    def batch_multi_rows_call_classes(self, batch, patterns, k, tables, reduced=True):
+        """batch_multi_rows_call in substitutions mode with symbol classes (fz_batch_search_multi_cls); tables = (pmask, tmask)."""
+        patterns = list(patterns)
+        fn = _class_entry(self._lib, "fz_batch_search_multi_cls")
+        blob, offs = pack_patterns(patterns)
+        ptr = ctypes.POINTER(FzMatch)()
+        sptr = ctypes.POINTER(ctypes.c_uint32)()
+        optr = ctypes.POINTER(ctypes.c_uint64)()
+        with self._lock:
+            _check(fn(self._h, batch._h, blob, offs, len(patterns), k, tables[0], tables[1], 1 if reduced else 0,
+                      ctypes.byref(ptr), ctypes.byref(sptr), ctypes.byref(optr)))
+        bounds = optr[:len(patterns) + 1]
+        self._lib.fz_free(optr)
+        return OwnedRows(self._lib, ptr, bounds[-1]), self._take_seq_of(sptr, bounds[-1]), bounds
+
+    def batch_search_multi_classes(self, batch, patterns, k, tables, reduced=False):
+        """The same as a list of (rows, seq_of) arrays per pattern."""
+        patterns = list(patterns)
+        rows, seq_of, bounds = self.batch_multi_rows_call_classes(batch, patterns, k, tables, reduced)
+        arr = rows.to_array()
+        return [(arr[bounds[i]:bounds[i + 1]], seq_of[bounds[i]:bounds[i + 1]]) for i in range(len(patterns))]
+
+    def batch_assign_classes(self, batch, patterns, k, tables):
+        """batch_assign in substitutions mode with symbol classes (fz_batch_assign_cls)."""
+        patterns = list(patterns)
+        fn = _class_entry(self._lib, "fz_batch_assign_cls")
+        blob, offs = pack_patterns(patterns)
+        ptr = ctypes.c_void_p()
+        with self._lock:
+            _check(fn(self._h, batch._h, blob, offs, len(patterns), k, tables[0], tables[1], ctypes.byref(ptr)))
+        return _take_assign_array(self._lib, ptr.value, batch.n_seqs)
+
     def batch_assign(self, batch, mode, patterns, k):
         """fz_batch_assign: the best pattern of the list per sequence of the batch -> a structured array (assign_dtype) of
         one row per sequence over the library's buffer: pattern (-1: none), dist, tied, start, end (local coordinates)."""
@@ -1026,6 +1094,32 @@ class Engine(object):
     def subs_ngrams_multi_best(self, seq, patterns, k, as_array=False):
         """[subs_ngrams_best(seq, p, k) for p in patterns] (fz_subs_ngrams_multi_best)."""
         return self._multi(self._lib.fz_subs_ngrams_multi_best, seq, patterns, k, as_array)
+
+    def _multi_call_classes(self, name, seq, patterns, k, tables):
+        fn = _class_entry(self._lib, name)
+        blob, offs = pack_patterns(patterns)
+        ptr = ctypes.POINTER(FzMatch)()
+        optr = ctypes.POINTER(ctypes.c_uint64)()
+        with self._lock:
+            _check(fn(self._h, seq._h, blob, offs, len(patterns), k, tables[0], tables[1], ctypes.byref(ptr), ctypes.byref(optr)))
+        bounds = optr[:len(patterns) + 1]
+        self._lib.fz_free(optr)
+        return ptr, bounds
+
+    def subs_ngrams_multi_classes(self, seq, patterns, k, tables, best=False, as_array=False):
+        """fz_subs_ngrams_multi_cls (best: fz_subs_ngrams_multi_best_cls): one stream per pattern under the class distance of
+        tables = (pmask, tmask)."""
+        patterns = list(patterns)
+        ptr, bounds = self._multi_call_classes("fz_subs_ngrams_multi_best_cls" if best else "fz_subs_ngrams_multi_cls", seq, patterns, k, tables)
+        rows = _take_matches_array(self._lib, ptr, bounds[-1])
+        out = [rows[bounds[i]:bounds[i + 1]] for i in range(len(patterns))]
+        return out if as_array else [r.tolist() for r in out]
+
+    def multi_rows_call_classes(self, seq, patterns, k, tables):
+        """fz_subs_ngrams_multi_best_cls -> (OwnedRows of all patterns' rows, row offsets per pattern)."""
+        patterns = list(patterns)
+        ptr, bounds = self._multi_call_classes("fz_subs_ngrams_multi_best_cls", seq, patterns, k, tables)
+        return OwnedRows(self._lib, ptr, bounds[-1]), bounds
 
     def multi_rows_call(self, seq, patterns, k, fn=None):
         """fz_lev_ngrams_multi_consolidated (or `fn`: fz_subs_ngrams_multi_best) -> (OwnedRows of all patterns' rows, row

@@ -85,11 +85,27 @@ def _from_matches(index, per_sequence):
     return out
 
 
+def _best_with_classes(subsequences, sequences, limits, classes):
+    from .multi_batch import held_for_classes
+    subsequences = list(subsequences)
+    if len(subsequences) > MAX_PATTERNS:
+        raise _native.UnsupportedSearch('best-pattern assignment takes at most %d subsequences' % MAX_PATTERNS)
+    patterns, k, tables, seqs, held, own = held_for_classes(subsequences, sequences, limits, classes)
+    if held is None:
+        return BestMatches(len(seqs))
+    try:
+        return _from_rows(held.engine.batch_assign_classes(held.handle, patterns, k, tables))
+    finally:
+        if own is not None:
+            own.release()
+
+
 def find_best_matches_batch(subsequences, sequences,
                             max_substitutions=None,
                             max_insertions=None,
                             max_deletions=None,
-                            max_l_dist=None):
+                            max_l_dist=None,
+                            classes=None):
     """the best-fitting subsequence per sequence -> BestMatches (arrays ``pattern``, ``dist``, ``start``, ``end``, ``tied``
     of one entry per sequence; ``len()`` = the number of sequences).
 
@@ -104,7 +120,12 @@ def find_best_matches_batch(subsequences, sequences,
 
     ``sequences`` may be a ``resident_batch()`` handle.  Refusals are those of find_near_matches_batch, with its exception
     types and texts; in addition UnsupportedSearch for an n-gram budget above 127, more than 65 535 subsequences or a
-    sequence of 2^32 items or more.  No subsequences: every entry is -1.  No sequences: empty arrays."""
+    sequence of 2^32 items or more.  No subsequences: every entry is -1.  No sequences: empty arrays.
+
+    ``classes`` (a mapping such as ``fuzzysearch_amd.IUPAC_DNA``): the same answer under the class distance of
+    find_near_matches_multi — mismatch-only limits, bytes-like sequences, every subsequence on the pass (fz_batch_assign_cls)."""
+    if classes is not None:
+        return _best_with_classes(subsequences, sequences, (max_substitutions, max_insertions, max_deletions, max_l_dist), classes)
     subsequences = list(subsequences)
     limits = (max_substitutions, max_insertions, max_deletions, max_l_dist)
     held = sequences if isinstance(sequences, BatchSequences) else None

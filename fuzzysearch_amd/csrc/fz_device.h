@@ -1260,6 +1260,169 @@ FZ_HD bool fz_mp_verify_subs(const Win &t, uint32_t sh, const uint32_t *p4, uint
 }
 
 // ---------------------------------------------------------------------------------------------
+// Symbol classes on the substitutions-only multi-pattern pass (fz_subs_ngrams_multi_cls; fz_kernels.h:
+// fz_mp_verify_cls_kernel).  Two 256-byte tables define them:
+//   tmask[t]   the one-hot bit of text byte t among the (at most 8) base symbols, 0 when t is no base symbol
+//   pmask[c]   the set of pattern byte c as a mask over those bits, 0 for a plain byte
+// Pattern byte c matches text byte t iff t == c or (tmask[t] & pmask[c]) != 0: text bytes are never classes.
+//
+// The filter and its table layout are unchanged: a block contributes one entry per DISTINCT hash over the spellings of the
+// bytes the filter hashes (fz_mp_hash_bytes: [0, 4) and [dh, dh + 3) of the first min(L, 8) bytes).  A window within k class
+// mismatches has a block with none (pigeonhole, as before); that block's text is one of its spellings, so its hash is in the
+// table.  Class bytes the hash does not cover — block offset 8 and beyond, byte 4 of an L >= 8 block, bytes behind the last
+// block — cost no entry.  Equal hashes of two spellings of ONE block give one entry, so a text position never reports the
+// same (block, index) twice.
+//
+// The class descriptor = the plain descriptor, then one mask byte per pattern position in rows of FZ_MP_MAX_M (bytes behind
+// m are zero, like the pattern rows), then tmask.
+#define FZ_MP_CLS_DESC_MASK FZ_MP_DESC_WORDS
+#define FZ_MP_CLS_DESC_TMASK (FZ_MP_CLS_DESC_MASK + FZ_MP_MAX_PATS * FZ_MP_MAX_M / 4u)
+#define FZ_MP_CLS_DESC_WORDS (FZ_MP_CLS_DESC_TMASK + 256u / 4u)
+#define FZ_MP_CLS_VERIFY_WORDS (FZ_MP_CLS_DESC_WORDS - FZ_MP_DESC_ENT)
+#define FZ_MP_CLS_MAX_BASE 8u
+
+FZ_HD bool fz_cls_match(uint8_t c, uint8_t t, const uint8_t *pmask, const uint8_t *tmask) { return t == c || (tmask[t] & pmask[c]) != 0; }
+
+// Is byte b of a block's first H = min(L, 8) bytes part of the window hash?
+FZ_HD bool fz_mp_hashed_byte(uint32_t L, uint32_t b) { return b < 4u || b >= fz_mp_dh(L); }
+
+// Host: the distinct hashes over the spellings of one block (w = its first byte, L >= FZ_MP_MIN_L) in ascending order.
+// -> their number; cap + 1 as soon as there are more than cap (hs holds cap + 1 values).
+inline uint32_t fz_mp_cls_block_hashes(const uint8_t *w, uint32_t L, const uint8_t *pmask, const uint8_t *tmask, uint32_t *hs, uint32_t cap) {
+    const uint32_t H = L < 8u ? L : 8u;
+    uint8_t alt[8][FZ_MP_CLS_MAX_BASE + 1u];                                     // what each byte may be spelled as
+    uint32_t nalt[8], at[8];
+    uint8_t cur[8];
+    for (uint32_t b = 0; b < H; ++b) {
+        alt[b][0] = w[b];
+        nalt[b] = 1u;
+        if (pmask[w[b]] && fz_mp_hashed_byte(L, b))
+            for (uint32_t t = 0; t < 256u; ++t)
+                if (t != w[b] && (tmask[t] & pmask[w[b]]) && nalt[b] <= FZ_MP_CLS_MAX_BASE) alt[b][nalt[b]++] = (uint8_t)t;
+        at[b] = 0u;
+        cur[b] = w[b];
+    }
+    uint32_t n = 0;
+    for (;;) {
+        const uint32_t h = fz_mp_hash_bytes(cur, L);
+        uint32_t lo = 0;
+        while (lo < n && hs[lo] < h) ++lo;
+        if (lo == n || hs[lo] != h) {
+            for (uint32_t j = n; j > lo; --j) hs[j] = hs[j - 1];
+            hs[lo] = h;
+            if (++n > cap) return n;
+        }
+        uint32_t b = 0;                                                          // the next spelling
+        for (; b < H; ++b) {
+            if (++at[b] < nalt[b]) { cur[b] = alt[b][at[b]]; break; }
+            at[b] = 0u;
+            cur[b] = alt[b][0];
+        }
+        if (b == H) return n;
+    }
+}
+
+// Host: the table entries of one pattern of n-gram length L: the sum over its blocks.  -> FZ_MP_MAX_BLOCKS + 1 when more.
+inline uint32_t fz_mp_cls_entries(const uint8_t *p, uint32_t m, uint32_t L, const uint8_t *pmask, const uint8_t *tmask) {
+    uint32_t hs[FZ_MP_MAX_BLOCKS + 1u], total = 0;
+    for (uint32_t s = 0; s + L <= m; s += L) {
+        total += fz_mp_cls_block_hashes(p + s, L, pmask, tmask, hs, FZ_MP_MAX_BLOCKS - total);
+        if (total > FZ_MP_MAX_BLOCKS) return FZ_MP_MAX_BLOCKS + 1u;
+    }
+    return total;
+}
+
+// Host: fz_mp_build for a class group.  desc = FZ_MP_CLS_DESC_WORDS dwords.  -> number of entries, 0 when they exceed
+// FZ_MP_MAX_BLOCKS (then the distinct hashes, at most as many, also stay within half of FZ_MP_SLOTS).
+inline uint32_t fz_mp_build_cls(uint32_t *desc, const uint8_t *const *pat, const uint32_t *m, uint32_t npat, uint32_t L, const uint8_t *pmask,
+                                const uint8_t *tmask) {
+    static_assert(2u * FZ_MP_MAX_BLOCKS <= FZ_MP_SLOTS, "a full block table keeps the slot table's load within 1/2");
+    for (uint32_t i = 0; i < FZ_MP_CLS_DESC_WORDS; ++i) desc[i] = 0u;
+    uint32_t hs[FZ_MP_MAX_BLOCKS], es[FZ_MP_MAX_BLOCKS], one[FZ_MP_MAX_BLOCKS + 1u], n = 0;
+    for (uint32_t i = 0; i < npat; ++i) {
+        uint32_t g = 0;
+        for (uint32_t s = 0; s + L <= m[i]; s += L, ++g) {
+            const uint32_t c = fz_mp_cls_block_hashes(pat[i] + s, L, pmask, tmask, one, FZ_MP_MAX_BLOCKS - n);
+            if (n + c > FZ_MP_MAX_BLOCKS) return 0u;
+            for (uint32_t j = 0; j < c; ++j) { hs[n] = one[j]; es[n] = fz_mp_entry(i, g, s); ++n; }
+        }
+        desc[FZ_MP_DESC_M + i] = m[i];
+        uint8_t *dst = reinterpret_cast<uint8_t *>(desc + FZ_MP_DESC_PAT) + i * FZ_MP_MAX_M;
+        uint8_t *msk = reinterpret_cast<uint8_t *>(desc + FZ_MP_CLS_DESC_MASK) + i * FZ_MP_MAX_M;
+        for (uint32_t q = 0; q < m[i]; ++q) { dst[q] = pat[i][q]; msk[q] = pmask[pat[i][q]]; }
+    }
+    uint8_t *tm = reinterpret_cast<uint8_t *>(desc + FZ_MP_CLS_DESC_TMASK);
+    for (uint32_t t = 0; t < 256u; ++t) tm[t] = tmask[t];
+    for (uint32_t i = 1; i < n; ++i) {                                           // insertion sort by hash: runs of equal hashes
+        const uint32_t h = hs[i], e = es[i];
+        uint32_t j = i;
+        for (; j > 0 && hs[j - 1] > h; --j) { hs[j] = hs[j - 1]; es[j] = es[j - 1]; }
+        hs[j] = h; es[j] = e;
+    }
+    uint32_t *slots = desc + FZ_MP_DESC_SLOTS;
+    for (uint32_t i = 0; i < n;) {
+        uint32_t j = i;
+        while (j < n && hs[j] == hs[i]) ++j;
+        const uint32_t t = fz_mp_sig_bit(hs[i]);
+        desc[t >> 5] |= 1u << (t & 31u);
+        uint32_t s = fz_mp_slot(hs[i]);
+        while ((slots[2u * s + 1u] >> 16) != 0u) s = (s + 1u) & (FZ_MP_SLOTS - 1u);
+        slots[2u * s] = hs[i];
+        slots[2u * s + 1u] = i | ((j - i) << 16);
+        i = j;
+    }
+    for (uint32_t i = 0; i < n; ++i) desc[FZ_MP_DESC_ENT + i] = es[i];
+    return n;
+}
+
+// Bit 7 of every byte of `keep` in which the window dword does not CLASS-match the pattern dword: fz_dword_diff, and a
+// differing byte whose mask byte (k4: the pattern's mask dword) is non-zero is taken back when the text byte's bit is in it.
+// Plain positions cost what they cost before; a class position pays one tmask lookup, and only where the bytes differ.
+// Bytes outside `keep` — another sequence's, the padding's, the pattern's zeros behind m — are never looked up nor counted.
+FZ_HD uint32_t fz_dword_diff_cls(uint32_t lo, uint32_t hi, uint32_t sh, uint32_t pat, uint32_t k4, uint32_t keep, const uint8_t *tmask) {
+    const uint32_t w = (uint32_t)(((((uint64_t)hi) << 32) | lo) >> (8u * sh));
+    const uint32_t x = w ^ pat;
+    uint32_t d = (((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x) & 0x80808080u & keep;
+    const uint32_t cls = (((k4 & 0x7f7f7f7fu) + 0x7f7f7f7fu) | k4) & d;           // differing bytes at class positions
+    if (cls) {
+        for (uint32_t b = 0; b < 4u; ++b)
+            if (((cls >> (8u * b + 7u)) & 1u) && (tmask[(w >> (8u * b)) & 0xffu] & (k4 >> (8u * b)) & 0xffu)) d &= ~(0x80u << (8u * b));
+    }
+    return d;
+}
+
+// fz_mp_block_equal with classes: does the window class-match the pattern on [s, s + L)?  k4 = the pattern's mask row, laid
+// out as p4 (same stride).
+template <class Win>
+FZ_HD bool fz_mp_block_match_cls(const Win &t, uint32_t sh, const uint32_t *p4, const uint32_t *k4, uint32_t ps, const uint8_t *tmask, uint32_t L,
+                                 uint32_t s) {
+    const uint32_t q0 = s & ~3u;
+    uint32_t prev = t.dword(q0 >> 2), bad = 0;
+    for (uint32_t q = q0; q < s + L; q += 4u) {
+        const uint32_t next = t.dword((q >> 2) + 1u);
+        bad |= fz_dword_diff_cls(prev, next, sh, p4[(q >> 2) * ps], k4[(q >> 2) * ps], fz_dword_bytes_in(q, s, s + L), tmask);
+        prev = next;
+    }
+    return bad == 0u;
+}
+
+// fz_mp_verify_subs with classes: the class mismatches outside the block, accepted when they are <= k.
+template <class Win>
+FZ_HD bool fz_mp_verify_cls(const Win &t, uint32_t sh, const uint32_t *p4, const uint32_t *k4, uint32_t ps, const uint8_t *tmask, uint32_t m,
+                            uint32_t m_max, uint32_t k, uint32_t L, uint32_t s, bool valid, FzRec &rec) {
+    uint32_t prev = t.dword(0u), nd = 0;
+    for (uint32_t q = 0; q < m_max; q += 4u) {
+        const uint32_t next = t.dword((q >> 2) + 1u);
+        const uint32_t keep = fz_dword_bytes_in(q, 0u, s) | fz_dword_bytes_in(q, s + L, m);
+        nd += (uint32_t)__builtin_popcount(fz_dword_diff_cls(prev, next, sh, p4[(q >> 2) * ps], k4[(q >> 2) * ps], keep, tmask));
+        prev = next;
+        if ((q & 4u) && !FZ_WAVE_BALLOT(valid && nd <= k)) break;
+    }
+    rec.l = s; rec.r = m - s - L; rec.dist = nd; rec.aux = 0;
+    return valid && nd <= k;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Multi-pattern search over a batch (fz_batch_search_multi; fz_kernels.h: fz_mp_batch_verify_kernel /
 // fz_mp_batch_verify_subs_kernel).  The filter streams the packed bytes as one sequence and may report n-grams that straddle
 // a seam; a candidate is accepted inside ITS sequence sg = fz_segment_ragged(idx) only — the block's hit range

@@ -689,6 +689,103 @@
         }
     }
     if (lane == 0 && confirmed) atomicAdd(&counters[8u + (blockIdx.x & 63u)], (unsigned long long)confirmed);
+#elif FZ_KERNEL_BODY == 7    // ---- fz_mp_verify_cls_kernel / fz_mp_batch_verify_cls_kernel
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    uint32_t *tab = reinterpret_cast<uint32_t *>(smem);
+    constexpr uint32_t kPat = FZ_MP_DESC_PAT - FZ_MP_DESC_ENT, kRow = FZ_MP_MAX_M / 4u, kRows = FZ_MP_MAX_PATS * kRow;
+    constexpr uint32_t kMsk = kPat + kRows, kTm = kMsk + kRows;
+    static_assert(FZ_MP_MAX_PATS == 64u, "the transposed tables have one column per pattern");
+    static_assert(kTm == FZ_MP_CLS_DESC_TMASK - FZ_MP_DESC_ENT && kTm + 64u == FZ_MP_CLS_VERIFY_WORDS, "the class descriptor's layout");
+    for (uint32_t i = threadIdx.x; i < FZ_MP_CLS_VERIFY_WORDS; i += FZ_FILTER_THREADS) {
+        const uint32_t v = desc[FZ_MP_DESC_ENT + i];
+        if (i < kPat || i >= kTm) tab[i] = v;
+        else {                                             // pattern rows, then mask rows: both transposed
+            const uint32_t base = i < kMsk ? kPat : kMsk, r = i - base;
+            tab[base + (r % kRow) * FZ_MP_MAX_PATS + r / kRow] = v;
+        }
+    }
+    __syncthreads();
+    const uint32_t *ent = tab;
+    const uint32_t *pm = tab + (FZ_MP_DESC_M - FZ_MP_DESC_ENT);
+    const uint32_t *pat4 = tab + kPat;
+    const uint32_t *msk4 = tab + kMsk;
+    const uint8_t *tmask = reinterpret_cast<const uint8_t *>(tab + kTm);
+    const uint32_t lane = fz_lane();
+    uint32_t *win = reinterpret_cast<uint32_t *>(smem + FZ_MP_CLS_VERIFY_WORDS * 4u) + (threadIdx.x >> 6) * a.win_dwords * 64u;
+    const uint32_t m_max = (a.win_dwords - 1u) * 4u;       // (the longest pattern rounded up to dwords)
+    const uint64_t waves = (uint64_t)gridDim.x * FZ_WAVES_PER_BLOCK;
+    const uint64_t wave = (uint64_t)blockIdx.x * FZ_WAVES_PER_BLOCK + (threadIdx.x >> 6);
+    const uint64_t n = a.geom.n;
+    const uint64_t data_end = a.geom.buf_off + a.geom.buf_len;
+    uint32_t confirmed = 0;
+    for (uint32_t l = 0; l < FZ_MP_LISTS; ++l) {
+        unsigned long long nh = counters[FZ_MP_CTR_LIST(l)];
+        if (nh > a.hit_cap) nh = a.hit_cap;
+        const uint64_t *lh = hits + (uint64_t)l * a.hit_cap;
+        for (uint64_t q0 = ((wave + 251u * l) % waves) * 64u; q0 < nh; q0 += waves * 64u) {
+            const uint64_t q = q0 + lane;
+            const bool have = q < nh;
+            const uint64_t hit = have ? lh[q] : 0ull;
+            const uint32_t e = ent[fz_hit_block(hit) & (FZ_MP_MAX_BLOCKS - 1u)];
+            const uint32_t pid = e & (FZ_MP_MAX_PATS - 1u), g = (e >> 8) & 0xffu, s = e >> 16;
+            const uint32_t m = pm[pid];
+            const uint64_t idx = fz_hit_index(hit);
+            bool valid;
+            if constexpr (RAG) {
+                // the candidate's own sequence, then the window [idx - s, idx - s + m) inside it, ownership, the whole
+                // window resident (fz_mp_rag_accept: the substitutions acceptance — a class changes no window)
+                valid = have && fz_hit_block(hit) < a.nent && m != 0u && m <= m_max && s + a.L <= m;
+                FzSeg sg;
+                sg.sa = sg.se = 0; sg.j = 0; sg.ok = 0;
+                if (valid) sg = fz_segment_ragged(fz_ragged(a.geom), n, idx);
+                FzMpRagCand c;
+                valid = valid && fz_mp_rag_accept(FZ_MODE_SUBS, a.geom, sg, m, a.k, a.L, s, idx, c);
+            } else {
+                uint32_t lo_rel, hi_sub;
+                fz_block_range(FZ_MODE_SUBS, m, a.k, a.L, s, lo_rel, hi_sub);
+                valid = have && fz_hit_block(hit) < a.nent && m != 0u && m <= m_max && s + a.L <= m &&
+                        idx >= lo_rel && n >= hi_sub && idx + a.L <= n - hi_sub &&
+                        idx >= a.geom.own_lo && idx < a.geom.own_hi && idx - lo_rel >= a.geom.buf_off && idx + a.L + hi_sub <= data_end;
+            }
+            if (!__ballot(valid)) continue;
+            const uint64_t i0 = valid ? idx - s : a.geom.buf_off;
+            const uint64_t wbase = a.geom.buf_off + ((i0 - a.geom.buf_off) & ~(uint64_t)3);
+            const uint32_t sh = (uint32_t)(i0 - wbase);
+            uint32_t nd = valid ? (uint32_t)((i0 + m - wbase + 3) >> 2) : 0u;      // <= (m + 6) / 4 <= win_dwords
+            if (nd > a.win_dwords) nd = a.win_dwords;
+            const int64_t lbase = (int64_t)(wbase - a.geom.buf_off);
+            for (uint32_t d0 = 0; d0 < a.win_dwords; d0 += 8) {
+                uint32_t x[8];
+#pragma unroll
+                for (uint32_t j = 0; j < 8; ++j)
+                    x[j] = (d0 + j < nd) ? *reinterpret_cast<const uint32_t *>(buf + lbase + (int64_t)(d0 + j) * 4) : 0u;
+#pragma unroll
+                for (uint32_t j = 0; j < 8; ++j)
+                    if (d0 + j < a.win_dwords) win[(d0 + j) * 64u + lane] = x[j];
+            }
+            fz_wave_lds_sync();
+            const FzLdsColumn t{win + lane};
+            const uint32_t *p4 = pat4 + pid, *k4 = msk4 + pid;
+            valid = valid && fz_mp_block_match_cls(t, sh, p4, k4, FZ_MP_MAX_PATS, tmask, a.L, valid ? s : 0u);
+            confirmed += (uint32_t)__popcll(__ballot(valid));
+            FzRec rec;
+            const bool ok = fz_mp_verify_cls(t, sh, p4, k4, FZ_MP_MAX_PATS, tmask, m, m_max, a.k, a.L, s, valid, rec);
+            const unsigned long long mask = __ballot(ok);
+            if (mask) {
+                unsigned long long base = 0;
+                if (lane == 0) base = atomicAdd(&counters[FZ_MP_CTR_RECS], (unsigned long long)__popcll(mask));
+                base = fz_bcast64(base);
+                if (ok) {
+                    rec.key = fz_hit_pack(g, idx);
+                    rec.aux = pid;
+                    const unsigned long long slot = base + fz_rank(mask);
+                    if (slot < a.rec_cap) recs[slot] = rec;
+                }
+            }
+            fz_wave_lds_sync();
+        }
+    }
+    if (lane == 0 && confirmed) atomicAdd(&counters[8u + (blockIdx.x & 63u)], (unsigned long long)confirmed);
 #else
 #error "FZ_KERNEL_BODY names no section"
 #endif

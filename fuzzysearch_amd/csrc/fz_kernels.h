@@ -2255,6 +2255,38 @@ __global__ __launch_bounds__(FZ_FILTER_THREADS) void fz_mp_batch_verify_subs_ker
 #undef FZ_KERNEL_BODY
 }
 
+// fz_mp_verify_subs_kernel's counterpart for groups with symbol classes (fz_subs_ngrams_multi_cls; fz_device.h: the class
+// descriptor): same launch shape, hit lists, counters, records, staging and acceptance.  Kernels of their own, so the
+// substitutions kernels' code does not move.  What differs per candidate:
+//   * the mask rows ride into LDS transposed exactly as the pattern rows do (dword j of pattern i at msk4[j * 64 + i]) and
+//     tmask follows as 256 bytes; a workgroup's tables are FZ_MP_CLS_VERIFY_WORDS dwords (17.5 KiB) in front of the windows;
+//   * the block test is class-exact (fz_mp_block_match_cls) and the count is the class mismatches outside the block
+//     (fz_mp_verify_cls): the dword xor as before, and one tmask byte read for a differing byte at a class position — the
+//     lanes' addresses are data-dependent there, as a table lookup's are, and plain positions never reach it.
+__host__ __device__ inline uint32_t fz_mp_verify_cls_lds(uint32_t win_dwords) {
+    return FZ_MP_CLS_VERIFY_WORDS * 4u + FZ_WAVES_PER_BLOCK * win_dwords * 256u;
+}
+
+__global__ __launch_bounds__(FZ_FILTER_THREADS) void fz_mp_verify_cls_kernel(const uint8_t *__restrict__ buf, const FzMpArgs a,
+                                                                             const uint32_t *__restrict__ desc, const uint64_t *__restrict__ hits,
+                                                                             FzRec *__restrict__ recs, unsigned long long *__restrict__ counters) {
+    constexpr bool RAG = false;
+#define FZ_KERNEL_BODY 7
+#include "fz_kernel_bodies.inc"
+#undef FZ_KERNEL_BODY
+}
+// ... and over a batch (fz_batch_search_multi_cls, fz_batch_assign_cls).  The bytes of a neighbouring sequence or of the
+// padding that the dword-granular staging brings along lie outside the byte masks of both tests, and the masks cover the
+// class lookup too: such a byte is neither compared nor looked up.
+__global__ __launch_bounds__(FZ_FILTER_THREADS) void fz_mp_batch_verify_cls_kernel(const uint8_t *__restrict__ buf, const FzMpArgs a,
+                                                                                   const uint32_t *__restrict__ desc, const uint64_t *__restrict__ hits,
+                                                                                   FzRec *__restrict__ recs, unsigned long long *__restrict__ counters) {
+    constexpr bool RAG = true;
+#define FZ_KERNEL_BODY 7
+#include "fz_kernel_bodies.inc"
+#undef FZ_KERNEL_BODY
+}
+
 // ---------------------------------------------------------------------------------------------
 // Best-pattern assignment (fz_batch_assign; fz_device.h: fz_assign_*).  Behind a verification launch the records are in HBM
 // and the answer a demultiplexer wants is a minimum per sequence over them:

@@ -210,6 +210,7 @@ struct DevState {
     // single-pattern searches keep between calls (zeroed headers, result slots, the direct mode) is touched
     uint8_t *d_mp_desc = nullptr, *d_mp_ctr = nullptr, *d_mp_hits = nullptr, *d_mp_recs = nullptr;
     uint64_t mp_hit_cap = 0, mp_rec_cap = 0;
+    uint32_t mp_desc_words = 0;        // dwords of d_mp_desc (a class group's descriptor is longer: it grows for those only)
     // fz_batch_assign: the call's tables and output rows (lo, hi, rows, pattern lengths, aux table: assign_ensure), and the
     // records of a pattern searched on its own on their way to the fold; both grow and stay, like the buffers above
     uint8_t *d_assign = nullptr, *d_assign_recs = nullptr;
@@ -3203,9 +3204,71 @@ static void mp_plan(uint32_t mode, const uint8_t *pats, const uint64_t *offs, ui
         for (uint32_t i : groups[gi].pats) group_of[i] = gi;
 }
 
-static int mp_ensure(DevState &d, uint64_t hit_cap, uint64_t rec_cap) {
+// Symbol classes of a call (fz_*_cls; fz_device.h: the class descriptor): the caller's two 256-byte tables.
+struct MpCls { const uint8_t *pmask, *tmask; };
+
+static int mp_check_cls(const uint8_t *pmask, const uint8_t *tmask) {
+    if (!pmask || !tmask) return fail(FZ_EINVAL, "null argument");
+    uint32_t seen = 0;
+    for (uint32_t t = 0; t < 256; ++t) {
+        if (tmask[t] & (tmask[t] - 1u)) return fail(FZ_EINVAL, "tmask[%u] has more than one bit", t);
+        if (tmask[t] & seen) return fail(FZ_EINVAL, "tmask[%u] repeats the bit of another base symbol", t);
+        seen |= tmask[t];
+    }
+    return FZ_OK;
+}
+
+// mp_plan for a call with classes.  Every pattern rides a pass — the single-pattern route knows no classes, so the cost
+// rule is not consulted and a group of one is a group — and so every pattern has to be inside the batched domain.  A group's
+// `blocks` are its table entries, expansions included (fz_mp_cls_entries): it is closed when the next pattern of its L would
+// take it beyond FZ_MP_MAX_PATS patterns or FZ_MP_MAX_BLOCKS entries.  pat_entries (optional): the entries of every pattern.
+static int mp_plan_cls(const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k, const MpCls &cls, std::vector<MpGroup> &groups,
+                       std::vector<uint32_t> &group_of, uint32_t *pat_entries = nullptr) {
+    groups.clear();
+    group_of.assign(n_pats, 0xffffffffu);
+    std::vector<MpGroup> open, closed;
+    for (uint32_t i = 0; i < n_pats; ++i) {
+        const uint64_t m64 = offs[i + 1] - offs[i];
+        if (m64 > FZ_MP_MAX_M || !mp_in_domain(FZ_MODE_SUBS, (uint32_t)m64, k))
+            return fail(FZ_EUNSUPPORTED, "pattern %u (length %llu, %u substitutions) is outside the multi-pattern domain "
+                        "1 <= k <= %u, m <= %u, m / (k + 1) >= %u: symbol classes are searched there only", i, (unsigned long long)m64, k,
+                        FZ_MP_MAX_K, FZ_MP_MAX_M, FZ_MP_MIN_L);
+        const uint32_t m = (uint32_t)m64, L = m / (k + 1);
+        const uint32_t ne = fz_mp_cls_entries(pats + offs[i], m, L, cls.pmask, cls.tmask);
+        if (ne > FZ_MP_MAX_BLOCKS)
+            return fail(FZ_EUNSUPPORTED, "pattern %u: the spellings of its n-gram blocks need more than %u table entries "
+                        "(too many class symbols within the first 8 bytes of a block)", i, FZ_MP_MAX_BLOCKS);
+        if (pat_entries) pat_entries[i] = ne;
+        MpGroup *g = nullptr;
+        for (MpGroup &o : open) if (o.L == L) g = &o;
+        if (g && (g->pats.size() + 1 > FZ_MP_MAX_PATS || g->blocks + ne > FZ_MP_MAX_BLOCKS)) {
+            closed.push_back(*g);
+            g->pats.clear();
+            g->blocks = 0;
+        }
+        if (!g) { open.emplace_back(); g = &open.back(); g->L = L; }
+        g->pats.push_back(i);
+        g->blocks += ne;
+    }
+    for (MpGroup &o : open) if (!o.pats.empty()) closed.push_back(o);
+    std::sort(closed.begin(), closed.end(), [](const MpGroup &x, const MpGroup &y) { return x.pats[0] < y.pats[0]; });
+    groups.swap(closed);
+    for (uint32_t gi = 0; gi < groups.size(); ++gi)
+        for (uint32_t i : groups[gi].pats) group_of[i] = gi;
+    return FZ_OK;
+}
+
+static int mp_ensure(DevState &d, uint64_t hit_cap, uint64_t rec_cap, uint32_t desc_words = FZ_MP_DESC_WORDS) {
     HIP_TRY(hipSetDevice(d.device));
-    if (!d.d_mp_desc) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d.d_mp_desc), FZ_MP_DESC_WORDS * 4u));
+    if (d.d_mp_desc && d.mp_desc_words < desc_words) {         // (the stream is idle between group launches)
+        HIP_TRY(hipFree(d.d_mp_desc));
+        d.d_mp_desc = nullptr;
+        d.mp_desc_words = 0;
+    }
+    if (!d.d_mp_desc) {
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d.d_mp_desc), (size_t)desc_words * 4u));
+        d.mp_desc_words = desc_words;
+    }
     if (!d.d_mp_ctr) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d.d_mp_ctr), FZ_MP_CTR_WORDS * 8u));
     int rc = grow_device(d, d.d_mp_hits, d.mp_hit_cap, hit_cap, (uint64_t)FZ_MP_LISTS * hit_cap * sizeof(uint64_t));
     if (rc) return rc;
@@ -3243,7 +3306,7 @@ static void mp_publish(fz_ctx *ctx, const MpTotals &tot, uint64_t raw_matches, u
 // run again with what its counters ask for.
 // -> *n_recs records in d.d_mp_recs (the attempt that did not overflow), the stream idle.
 static int mp_launch_shard(fz_ctx *ctx, const Shard &sh, uint32_t mode, const uint32_t *desc, uint32_t nent, uint32_t k, uint32_t L, uint32_t max_m,
-                           uint32_t sigma, uint64_t *n_recs, MpTotals &tot, bool rag = false) {
+                           uint32_t sigma, uint64_t *n_recs, MpTotals &tot, bool rag = false, bool cls = false) {
     DevState &d = ctx->devs[sh.dev];
     *n_recs = 0;
     const uint64_t ntiles = (sh.geom.buf_len + FZ_TILE_BYTES - 1) / FZ_TILE_BYTES;
@@ -3263,15 +3326,17 @@ static int mp_launch_shard(fz_ctx *ctx, const Shard &sh, uint32_t mode, const ui
     static const FilterKernel filters[6] = {nullptr, fz_mp_filter_kernel<1>, fz_mp_filter_kernel<2>, fz_mp_filter_kernel<3>,
                                             fz_mp_filter_kernel<4>, fz_mp_filter_kernel<5>};
     const FilterKernel fk = filters[fz_mp_dh(L)];
+    // (cls: desc is a class descriptor — the filter reads its first part as ever, the class kernels the whole of it)
+    const uint32_t desc_words = cls ? FZ_MP_CLS_DESC_WORDS : FZ_MP_DESC_WORDS;
     const uint32_t grid = (uint32_t)std::min<uint64_t>(ntiles, (uint64_t)d.n_cus * 8);
     for (int attempt = 0; attempt < 4; ++attempt) {
-        int rc = mp_ensure(d, hit_cap, rec_cap);
+        int rc = mp_ensure(d, hit_cap, rec_cap, desc_words);
         if (rc) return rc;
         a.hit_cap = d.mp_hit_cap;
         a.rec_cap = d.mp_rec_cap;
         const uint32_t *ddesc = reinterpret_cast<const uint32_t *>(d.d_mp_desc);
         unsigned long long *dctr = reinterpret_cast<unsigned long long *>(d.d_mp_ctr);
-        HIP_TRY(hipMemcpyAsync(d.d_mp_desc, desc, FZ_MP_DESC_WORDS * 4u, hipMemcpyHostToDevice, d.stream));
+        HIP_TRY(hipMemcpyAsync(d.d_mp_desc, desc, (size_t)desc_words * 4u, hipMemcpyHostToDevice, d.stream));
         HIP_TRY(hipMemsetAsync(d.d_mp_ctr, 0, FZ_MP_CTR_WORDS * 8u, d.stream));
         if (ctx->timing) HIP_TRY(hipEventRecord(d.ev[0], d.stream));
         hipLaunchKernelGGL(fk, dim3(grid), dim3(FZ_FILTER_THREADS), FZ_MP_FILTER_LDS, d.stream, sh.d_buf, a, ntiles, ddesc,
@@ -3279,7 +3344,11 @@ static int mp_launch_shard(fz_ctx *ctx, const Shard &sh, uint32_t mode, const ui
         HIP_TRY(hipGetLastError());
         if (ctx->timing) HIP_TRY(hipEventRecord(d.ev[1], d.stream));
         // (rag: the shard is a batch — the ragged instances look every candidate's sequence up in the geometry's tables)
-        if (subs)
+        if (cls)
+            hipLaunchKernelGGL(rag ? fz_mp_batch_verify_cls_kernel : fz_mp_verify_cls_kernel, dim3((uint32_t)d.n_cus * 4), dim3(FZ_FILTER_THREADS),
+                               fz_mp_verify_cls_lds(a.win_dwords), d.stream,
+                               sh.d_buf, a, ddesc, reinterpret_cast<const uint64_t *>(d.d_mp_hits), reinterpret_cast<FzRec *>(d.d_mp_recs), dctr);
+        else if (subs)
             hipLaunchKernelGGL(rag ? fz_mp_batch_verify_subs_kernel : fz_mp_verify_subs_kernel, dim3((uint32_t)d.n_cus * 4), dim3(FZ_FILTER_THREADS),
                                fz_mp_verify_subs_lds(a.win_dwords), d.stream,
                                sh.d_buf, a, ddesc, reinterpret_cast<const uint64_t *>(d.d_mp_hits), reinterpret_cast<FzRec *>(d.d_mp_recs), dctr);
@@ -3322,7 +3391,7 @@ static int mp_launch_shard(fz_ctx *ctx, const Shard &sh, uint32_t mode, const ui
 // One group over one shard: its descriptor built (fz_mp_build), then mp_launch_shard.
 // -> *n_recs records in d.d_mp_recs (aux = the pattern's number in the group), the stream idle.
 static int mp_launch_group(fz_ctx *ctx, const Shard &sh, uint32_t mode, const uint8_t *pats, const uint64_t *offs, uint32_t k, const MpGroup &g,
-                           uint64_t *n_recs, MpTotals &tot, bool rag) {
+                           uint64_t *n_recs, MpTotals &tot, bool rag, const MpCls *cls = nullptr) {
     const uint32_t np = (uint32_t)g.pats.size();
     const uint8_t *pp[FZ_MP_MAX_PATS];
     uint32_t pm[FZ_MP_MAX_PATS], max_m = 0;
@@ -3331,20 +3400,20 @@ static int mp_launch_group(fz_ctx *ctx, const Shard &sh, uint32_t mode, const ui
         pm[j] = (uint32_t)(offs[g.pats[j] + 1] - offs[g.pats[j]]);
         max_m = std::max(max_m, pm[j]);
     }
-    std::vector<uint32_t> desc(FZ_MP_DESC_WORDS, 0u);
-    const uint32_t nent = fz_mp_build(desc.data(), pp, pm, np, g.L);
+    std::vector<uint32_t> desc(cls ? FZ_MP_CLS_DESC_WORDS : FZ_MP_DESC_WORDS, 0u);
+    const uint32_t nent = cls ? fz_mp_build_cls(desc.data(), pp, pm, np, g.L, cls->pmask, cls->tmask) : fz_mp_build(desc.data(), pp, pm, np, g.L);
     if (nent == 0 || nent != g.blocks) return fail(FZ_EDEVICE, "internal: the group's block table does not match its plan");
-    return mp_launch_shard(ctx, sh, mode, desc.data(), nent, k, g.L, max_m, std::max(1u, mp_sigma(pats, offs, g)), n_recs, tot, rag);
+    return mp_launch_shard(ctx, sh, mode, desc.data(), nent, k, g.L, max_m, std::max(1u, mp_sigma(pats, offs, g)), n_recs, tot, rag, cls != nullptr);
 }
 
 // One group over every shard of the sequence, the records copied back -> rows[i] of every pattern i of the group.
 static int mp_run_group(fz_ctx *ctx, fz_seq *seq, uint32_t mode, const uint8_t *pats, const uint64_t *offs, uint32_t k, const MpGroup &g,
-                        std::vector<std::vector<fz_match>> &rows, MpTotals &tot) {
+                        std::vector<std::vector<fz_match>> &rows, MpTotals &tot, const MpCls *cls = nullptr) {
     const uint32_t np = (uint32_t)g.pats.size();
     std::vector<FzRec> recs;
     for (const Shard &sh : seq->shards) {
         uint64_t nr = 0;
-        int rc = mp_launch_group(ctx, sh, mode, pats, offs, k, g, &nr, tot, seq->is_batch);
+        int rc = mp_launch_group(ctx, sh, mode, pats, offs, k, g, &nr, tot, seq->is_batch, cls);
         if (rc) return rc;
         const size_t at = recs.size();
         recs.resize(at + nr);
@@ -3469,22 +3538,34 @@ static int mp_pack(const std::vector<fz_match> *rows, const std::vector<uint32_t
     return FZ_OK;
 }
 
+// What a call with classes plans with: mp_plan_cls' groups, or its refusal — before anything is searched.
+static int mp_groups(uint32_t mode, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k, const MpCls *cls,
+                     std::vector<MpGroup> &groups, std::vector<uint32_t> &group_of) {
+    if (cls) return mp_plan_cls(pats, offs, n_pats, k, *cls, groups, group_of);
+    mp_plan(mode, pats, offs, n_pats, k, groups, group_of);
+    return FZ_OK;
+}
+
 // fz_lev_ngrams_multi* (mode = FZ_MODE_LEV; reduced: fz_consolidate per pattern) and fz_subs_ngrams_multi* (FZ_MODE_SUBS;
-// reduced: fz_group_best per pattern).
+// reduced: fz_group_best per pattern; cls: the class forms, every pattern on a pass).
 static int multi_impl(fz_ctx *ctx, fz_seq *seq, uint32_t mode, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k,
-                      bool consolidated, fz_match **out, uint64_t **out_offs) {
+                      bool consolidated, fz_match **out, uint64_t **out_offs, const MpCls *cls = nullptr) {
     const bool subs = mode == FZ_MODE_SUBS;
     if (!out || !out_offs) return fail(FZ_EINVAL, "null argument");
     *out = nullptr; *out_offs = nullptr;
-    int rc = mp_admit(ctx, seq, mode, pats, offs, n_pats, k, nullptr);
+    int rc = cls ? mp_check_cls(cls->pmask, cls->tmask) : (int)FZ_OK;
+    if (rc) return rc;
+    rc = mp_admit(ctx, seq, mode, pats, offs, n_pats, k, nullptr);
     if (rc) return rc;
     std::vector<MpGroup> groups;
     std::vector<uint32_t> group_of;
     // a context in a communicator searches collectively, pattern by pattern, through the existing collective search
     bool batched = !ctx->snapshot;
     for (const Shard &sh : seq->shards) batched = batched && sh.geom.seg_stride == 0;
-    if (batched) mp_plan(mode, pats, offs, n_pats, k, groups, group_of);
+    if (cls && !batched) return fail(FZ_EUNSUPPORTED, "symbol classes are searched on the multi-pattern pass only: not collectively, not over strided sequences");
+    if (batched) rc = mp_groups(mode, pats, offs, n_pats, k, cls, groups, group_of);
     else group_of.assign(n_pats, 0xffffffffu);
+    if (rc) return rc;
     std::vector<std::vector<fz_match>> rows(n_pats);
     MpTotals tot;
     uint32_t form = FZ_FORM_NONE;
@@ -3502,7 +3583,7 @@ static int multi_impl(fz_ctx *ctx, fz_seq *seq, uint32_t mode, const uint8_t *pa
     });
     if (rc) return rc;
     for (const MpGroup &g : groups) {
-        rc = mp_run_group(ctx, seq, mode, pats, offs, k, g, rows, tot);
+        rc = mp_run_group(ctx, seq, mode, pats, offs, k, g, rows, tot, cls);
         if (rc) return rc;
         form = FZ_FORM_KERNEL;
     }
@@ -3540,6 +3621,37 @@ int fz_subs_ngrams_multi(fz_ctx *ctx, fz_seq *seq, const uint8_t *pats, const ui
 int fz_subs_ngrams_multi_best(fz_ctx *ctx, fz_seq *seq, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k,
                               fz_match **out, uint64_t **out_offs) {
     return multi_impl(ctx, seq, FZ_MODE_SUBS, pats, offs, n_pats, k, true, out, out_offs);
+}
+
+int fz_subs_ngrams_multi_cls(fz_ctx *ctx, fz_seq *seq, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k,
+                             const uint8_t *pmask, const uint8_t *tmask, fz_match **out, uint64_t **out_offs) {
+    const MpCls cls{pmask, tmask};
+    return multi_impl(ctx, seq, FZ_MODE_SUBS, pats, offs, n_pats, k, false, out, out_offs, &cls);
+}
+
+int fz_subs_ngrams_multi_best_cls(fz_ctx *ctx, fz_seq *seq, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k,
+                                  const uint8_t *pmask, const uint8_t *tmask, fz_match **out, uint64_t **out_offs) {
+    const MpCls cls{pmask, tmask};
+    return multi_impl(ctx, seq, FZ_MODE_SUBS, pats, offs, n_pats, k, true, out, out_offs, &cls);
+}
+
+int fz_debug_multi_plan_cls(const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k, const uint8_t *pmask, const uint8_t *tmask,
+                            uint32_t *group_of, uint32_t *n_groups, uint32_t *pat_entries, uint32_t *group_entries) {
+    if (!group_of || !n_groups) return fail(FZ_EINVAL, "null argument");
+    int rc = mp_check_cls(pmask, tmask);
+    if (rc) return rc;
+    rc = mp_check_lists(pats, offs, n_pats);
+    if (rc) return rc;
+    const MpCls cls{pmask, tmask};
+    std::vector<MpGroup> groups;
+    std::vector<uint32_t> of;
+    rc = mp_plan_cls(pats, offs, n_pats, k, cls, groups, of, pat_entries);
+    if (rc) return rc;
+    for (uint32_t i = 0; i < n_pats; ++i) group_of[i] = of[i];
+    if (group_entries)
+        for (size_t gi = 0; gi < groups.size(); ++gi) group_entries[gi] = groups[gi].blocks;
+    *n_groups = (uint32_t)groups.size();
+    return FZ_OK;
 }
 
 int fz_debug_multi_plan(const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k, uint32_t *group_of, uint32_t *n_groups) {
@@ -4003,15 +4115,18 @@ int fz_batch_search(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8_t *p,
 // too), every group one filter launch over the packed bytes plus one RAGGED verification launch (fz_mp_batch_verify_kernel /
 // fz_mp_batch_verify_subs_kernel: every candidate inside its own sequence), every other pattern through batch_search_impl.
 // Per pattern the rows are then ordered, shifted and reduced exactly as fz_batch_search does it (batch_order).
-int fz_batch_search_multi(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k,
-                          int reduced, fz_match **out, uint32_t **seq_of, uint64_t **out_offs) {
+static int batch_multi_impl(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k,
+                            int reduced, fz_match **out, uint32_t **seq_of, uint64_t **out_offs, const MpCls *cls, const char *call) {
     if (!out || !seq_of || !out_offs) return fail(FZ_EINVAL, "null argument");
     *out = nullptr; *seq_of = nullptr; *out_offs = nullptr;
-    int rc = mp_admit(ctx, batch, mode, pats, offs, n_pats, k, "fz_batch_search_multi");
+    int rc = cls ? mp_check_cls(cls->pmask, cls->tmask) : (int)FZ_OK;
+    if (rc) return rc;
+    rc = mp_admit(ctx, batch, mode, pats, offs, n_pats, k, call);
     if (rc) return rc;
     std::vector<MpGroup> groups;
     std::vector<uint32_t> group_of;
-    mp_plan(mode, pats, offs, n_pats, k, groups, group_of);
+    rc = mp_groups(mode, pats, offs, n_pats, k, cls, groups, group_of);
+    if (rc) return rc;
     std::vector<std::vector<fz_match>> fin(n_pats);
     std::vector<std::vector<uint32_t>> fin_seq(n_pats);
     MpTotals tot;
@@ -4025,7 +4140,7 @@ int fz_batch_search_multi(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8
     if (!groups.empty() && batch->n_seqs && batch->n) {
         std::vector<std::vector<fz_match>> rows(n_pats);           // global coordinates, in-memory order
         for (const MpGroup &g : groups) {
-            rc = mp_run_group(ctx, batch, mode, pats, offs, k, g, rows, tot);
+            rc = mp_run_group(ctx, batch, mode, pats, offs, k, g, rows, tot, cls);
             if (rc) return rc;
             form = FZ_FORM_KERNEL;
             for (uint32_t i : g.pats) {
@@ -4041,15 +4156,32 @@ int fz_batch_search_multi(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8
     return FZ_OK;
 }
 
+int fz_batch_search_multi(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k,
+                          int reduced, fz_match **out, uint32_t **seq_of, uint64_t **out_offs) {
+    return batch_multi_impl(ctx, batch, mode, pats, offs, n_pats, k, reduced, out, seq_of, out_offs, nullptr, "fz_batch_search_multi");
+}
+
+int fz_batch_search_multi_cls(fz_ctx *ctx, fz_seq *batch, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k,
+                              const uint8_t *pmask, const uint8_t *tmask, int reduced, fz_match **out, uint32_t **seq_of, uint64_t **out_offs) {
+    const MpCls cls{pmask, tmask};
+    return batch_multi_impl(ctx, batch, FZ_MODE_SUBS, pats, offs, n_pats, k, reduced, out, seq_of, out_offs, &cls, "fz_batch_search_multi_cls");
+}
+
 // Best pattern per sequence.  The checks, the plan and the launches of fz_batch_search_multi; behind every verification
 // launch fz_assign_reduce_kernel folds the records where they lie into the call's tables (lo: u64, hi: u32 per sequence),
 // fz_assign_finish_kernel decodes them and ONE copy brings the rows to the host: no record copy, no ordering, no rows.
-int fz_batch_assign(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k,
-                    fz_assign **out) {
+static int batch_assign_impl(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k,
+                             fz_assign **out, const MpCls *cls, const char *call) {
     static_assert(sizeof(fz_assign) == sizeof(FzAssignRow) && sizeof(fz_assign) == 16, "the kernel writes the C-ABI's rows");
     if (!out) return fail(FZ_EINVAL, "null argument");
     *out = nullptr;
-    int rc = mp_admit(ctx, batch, mode, pats, offs, n_pats, k, "fz_batch_assign");
+    int rc = cls ? mp_check_cls(cls->pmask, cls->tmask) : (int)FZ_OK;
+    if (rc) return rc;
+    rc = mp_admit(ctx, batch, mode, pats, offs, n_pats, k, call);
+    if (rc) return rc;
+    std::vector<MpGroup> groups;
+    std::vector<uint32_t> group_of;
+    rc = mp_groups(mode, pats, offs, n_pats, k, cls, groups, group_of);      // (a class call's refusals: before anything is allocated)
     if (rc) return rc;
     // the domain of the tables' keys (fz_device.h: fz_assign_key)
     if (k > FZ_ASSIGN_MAX_K) return fail(FZ_EUNSUPPORTED, "best-pattern assignment takes budgets up to %u", FZ_ASSIGN_MAX_K);
@@ -4069,9 +4201,6 @@ int fz_batch_assign(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8_t *pa
         *out = rows;
         return FZ_OK;
     }
-    std::vector<MpGroup> groups;
-    std::vector<uint32_t> group_of;
-    mp_plan(mode, pats, offs, n_pats, k, groups, group_of);
     // the aux tables of the whole call: 64 entries per group, then one entry per pattern searched on its own
     std::vector<FzAssignPat> table(groups.size() * FZ_MP_MAX_PATS + n_pats);
     std::vector<uint32_t> pm(n_pats);
@@ -4118,7 +4247,7 @@ int fz_batch_assign(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8_t *pa
     for (size_t gi = 0; gi < groups.size(); ++gi) {
         const MpGroup &g = groups[gi];
         uint64_t nr = 0;
-        rc = mp_launch_group(ctx, sh, mode, pats, offs, k, g, &nr, tot, true);
+        rc = mp_launch_group(ctx, sh, mode, pats, offs, k, g, &nr, tot, true, cls);
         if (rc) return rc;
         // the attempt that did not overflow: its records, where they lie
         rc = assign_fold_device(ctx, ac, reinterpret_cast<const FzRec *>(d.d_mp_recs), nr, g.L, ac.d_pat + gi * FZ_MP_MAX_PATS, FZ_MP_MAX_PATS);
@@ -4138,6 +4267,17 @@ int fz_batch_assign(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8_t *pa
     *out = rows;
     mp_publish(ctx, tot, ac.folded, form, ac.fold_ms);
     return FZ_OK;
+}
+
+int fz_batch_assign(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k,
+                    fz_assign **out) {
+    return batch_assign_impl(ctx, batch, mode, pats, offs, n_pats, k, out, nullptr, "fz_batch_assign");
+}
+
+int fz_batch_assign_cls(fz_ctx *ctx, fz_seq *batch, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k,
+                        const uint8_t *pmask, const uint8_t *tmask, fz_assign **out) {
+    const MpCls cls{pmask, tmask};
+    return batch_assign_impl(ctx, batch, FZ_MODE_SUBS, pats, offs, n_pats, k, out, &cls, "fz_batch_assign_cls");
 }
 
 int fz_debug_assign_fold(const uint64_t *offs, uint64_t n_seqs, const void *recs, uint64_t n, uint32_t L, const uint32_t *pat_table,

@@ -12,9 +12,12 @@ per pass:
 
 Everything else — the generic class, the exact and linear-programming routes, sequences whose coding depends on the
 subsequence — takes the per-pattern code inside the same call, with the results in input order.
+
+``classes=`` (classes.py: IUPAC patterns) is answered by the pass alone: fz_subs_ngrams_multi_best_cls for the whole list.
 """
+from ._native import UnsupportedSearch
 from .common import LevenshteinSearchParams, matches_from_rows_multi
-from .engine import is_byteslike, prepare_shared
+from .engine import DeviceSequence, is_byteslike, prepare_shared
 
 __all__ = ['find_near_matches_multi']
 
@@ -31,16 +34,42 @@ def _batch_pattern(p, byteslike):
     return None
 
 
+def _find_with_classes(subsequences, sequence, limits, classes):
+    from .classes import class_call
+    subsequences = list(subsequences)
+    byteslike = sequence.byteslike if isinstance(sequence, DeviceSequence) else is_byteslike(sequence)
+    patterns, k, tables = class_call(subsequences, limits, classes, byteslike)
+    if not patterns:
+        return []
+    shared = prepare_shared(sequence)
+    if shared is None:
+        raise UnsupportedSearch('classes are searched in bytes-like sequences only')
+    pr = shared[0]
+    try:
+        rows, bounds = pr.engine.multi_rows_call_classes(pr.handle, patterns, k, tables)
+        return matches_from_rows_multi(rows, bounds, pr.original)
+    finally:
+        pr.release()
+
+
 def find_near_matches_multi(subsequences, sequence,
                             max_substitutions=None,
                             max_insertions=None,
                             max_deletions=None,
-                            max_l_dist=None):
+                            max_l_dist=None,
+                            classes=None):
     """search for near-matches of every subsequence in sequence -> a list with one list of Match per subsequence,
     equal to ``[find_near_matches(p, sequence, ...) for p in subsequences]`` (same limits for all of them).
 
     ``sequence`` may be a ``resident()`` handle.  The first subsequence that ``find_near_matches`` would refuse raises
-    its exception before anything is searched."""
+    its exception before anything is searched.
+
+    ``classes`` (a mapping such as ``fuzzysearch_amd.IUPAC_DNA``: pattern byte -> the sequence bytes it accepts) searches
+    under the class distance instead: mismatch-only limits, a bytes-like sequence, every subsequence on the multi-pattern
+    pass (``UnsupportedSearch`` otherwise, naming the list position).  Per subsequence: every window within the budget,
+    reduced to the best match of every overlap group."""
+    if classes is not None:
+        return _find_with_classes(subsequences, sequence, (max_substitutions, max_insertions, max_deletions, max_l_dist), classes)
     from . import find_near_matches, choose_search_class, LevenshteinSearch, SubstitutionsOnlySearch
     from .substitutions_only import _finish_ngrams
     subsequences = list(subsequences)

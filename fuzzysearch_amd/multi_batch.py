@@ -17,6 +17,7 @@ import numpy as np
 from . import _native
 from .batch import BatchSequences, batch_route, find_near_matches_batch, _MODES, _fzmatch
 from .common import LevenshteinSearchParams, RawMatches
+from .engine import is_byteslike
 
 __all__ = ['find_near_matches_multi_batch', 'multi_batch_routes']
 
@@ -67,16 +68,57 @@ def _matches_per_pattern(rows, seq_of, bounds, sequences):
         rows.release()
 
 
+def held_for_classes(subsequences, sequences, limits, classes):
+    """What the two batch calls with ``classes`` share: every check (classes.class_call) before anything is uploaded, then
+    the batch.  -> (patterns, k, tables, sequences as a list, held batch or None when there is nothing to search, owned)."""
+    from .classes import class_call
+    subsequences = list(subsequences)
+    held = sequences if isinstance(sequences, BatchSequences) else None
+    seqs = held.sequences if held is not None else list(sequences)
+    if held is not None:
+        byteslike = held.kind == 'bytes' or not seqs
+    else:
+        byteslike = all(is_byteslike(s) for s in seqs)
+    patterns, k, tables = class_call(subsequences, limits, classes, byteslike)
+    if not patterns or not seqs:
+        return patterns, k, tables, seqs, None, None
+    own = None
+    if held is None:
+        held = own = BatchSequences(seqs)
+        if held.kind != 'bytes':
+            own.release()
+            raise _native.UnsupportedSearch('classes are searched by single-device, non-collective engines')
+    return patterns, k, tables, seqs, held, own
+
+
+def _find_with_classes(subsequences, sequences, limits, classes):
+    patterns, k, tables, seqs, held, own = held_for_classes(subsequences, sequences, limits, classes)
+    if held is None:
+        return [[] for _ in patterns]
+    try:
+        rows, seq_of, bounds = held.engine.batch_multi_rows_call_classes(held.handle, patterns, k, tables, reduced=True)
+        return _matches_per_pattern(rows, seq_of, bounds, seqs)
+    finally:
+        if own is not None:
+            own.release()
+
+
 def find_near_matches_multi_batch(subsequences, sequences,
                                   max_substitutions=None,
                                   max_insertions=None,
                                   max_deletions=None,
-                                  max_l_dist=None):
+                                  max_l_dist=None,
+                                  classes=None):
     """search for near-matches of every subsequence in every sequence -> a list with, per subsequence, one list of Match
     per sequence: ``[find_near_matches_batch(p, sequences, ...) for p in subsequences]`` (same limits for all of them).
 
     ``sequences`` may be a ``resident_batch()`` handle; otherwise the sequences are packed and uploaded once for the whole
-    call."""
+    call.
+
+    ``classes`` (a mapping such as ``fuzzysearch_amd.IUPAC_DNA``): the class distance of find_near_matches_multi, per
+    sequence; mismatch-only limits, bytes-like sequences, every subsequence on the pass (fz_batch_search_multi_cls)."""
+    if classes is not None:
+        return _find_with_classes(subsequences, sequences, (max_substitutions, max_insertions, max_deletions, max_l_dist), classes)
     subsequences = list(subsequences)
     limits = (max_substitutions, max_insertions, max_deletions, max_l_dist)
     if not subsequences:

@@ -307,6 +307,39 @@ int fz_debug_assign_fold(const uint64_t *offs, uint64_t n_seqs, const void *recs
                          const uint32_t *pat_table, uint32_t n_table, const uint32_t *pat_m, uint32_t n_pats, uint32_t k,
                          fz_assign *out);
 
+/* Symbol classes (IUPAC patterns) on the substitutions-only multi-pattern pass.  Two tables of 256 bytes define them:
+ *   tmask[t]  the one-hot bit of text byte t among the base symbols (at most 8), 0 when t is no base symbol
+ *   pmask[c]  the set of pattern byte c as a mask over those bits, 0 for a plain byte
+ * Pattern byte c matches text byte t iff t == c or (tmask[t] & pmask[c]) != 0; text bytes are never classes.  The class
+ * distance of a pattern and a window of its length is the number of positions that do not match; the class forms below are
+ * the named calls with that distance in the place of the Hamming distance: every window within k appears once in the raw
+ * stream of every n-gram block it class-matches, rows (start, end, dist, block) in the order of the plain calls.
+ * Every pattern rides a pass, a list of one included: the cost rule is not consulted and there is no single-pattern route.
+ * So every pattern must be inside the batched domain (1 <= k <= 8, m <= 128, m / (k + 1) >= 4), and its n-gram blocks must
+ * fit the filter's table: a block contributes one entry per distinct hash over the spellings of the bytes the filter hashes
+ * (bytes 0 .. 3 and the last three of its first min(L, 8) bytes; class bytes elsewhere are free), a group holds 64 patterns
+ * and 256 entries, and a pattern that needs more than 256 on its own is refused.  FZ_EUNSUPPORTED names the pattern in both
+ * cases, before anything is searched; so do collective contexts and strided sequences.  FZ_EINVAL for a tmask entry of more
+ * than one bit or a bit used twice.  All other checks, shards and halos (m bytes), outputs and fz_stats as for the plain call. */
+int fz_subs_ngrams_multi_cls(fz_ctx *ctx, fz_seq *seq, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k,
+                             const uint8_t *pmask, const uint8_t *tmask, fz_match **out, uint64_t **out_offs);
+/* ... with every pattern's slice reduced by fz_group_best (the best match of every overlap group). */
+int fz_subs_ngrams_multi_best_cls(fz_ctx *ctx, fz_seq *seq, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats,
+                                  uint32_t k, const uint8_t *pmask, const uint8_t *tmask, fz_match **out, uint64_t **out_offs);
+/* fz_batch_search_multi in substitutions mode, with classes. */
+int fz_batch_search_multi_cls(fz_ctx *ctx, fz_seq *batch, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats,
+                              uint32_t k, const uint8_t *pmask, const uint8_t *tmask, int reduced, fz_match **out,
+                              uint32_t **seq_of, uint64_t **out_offs);
+/* fz_batch_assign in substitutions mode, with classes: the same fold over the class forms' records. */
+int fz_batch_assign_cls(fz_ctx *ctx, fz_seq *batch, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k,
+                        const uint8_t *pmask, const uint8_t *tmask, fz_assign **out);
+/* Test hook, no device needed: the plan of a class call.  group_of[i] = the pass pattern i rides in (never 0xffffffff);
+ * pat_entries[i] (optional, n_pats values) = the table entries of pattern i; group_entries[g] (optional, room for n_pats
+ * values) = the entries of group g.  The class calls' refusals, with their codes. */
+int fz_debug_multi_plan_cls(const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k, const uint8_t *pmask,
+                            const uint8_t *tmask, uint32_t *group_of, uint32_t *n_groups, uint32_t *pat_entries,
+                            uint32_t *group_entries);
+
 /* Test hook, no device needed: the sequence of position idx of a batch with the offsets `offs` — the lookup the kernels
  * run (fz_device.h: fz_segment_ragged, the per-tile bound included), on the host.  *j = its number, [*sa, *se) its bytes.
  * FZ_EINVAL for idx >= offs[n_seqs].  The tables are built on the first call for an offset array and kept for the next
