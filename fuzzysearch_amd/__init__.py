@@ -12,7 +12,8 @@ Extra, MI355X-specific surface: ``resident(sequence)`` uploads a long sequence t
 many patterns can be searched without re-crossing PCIe; ``find_near_matches_multi`` searches many subsequences in one
 sequence and ``find_near_matches_batch`` one subsequence in many sequences (``resident_batch`` keeps them in HBM), each
 in one pass; ``find_near_matches_multi_batch`` searches many subsequences in many sequences, a pass per group of up to 64;
-``resident_records`` makes such a batch from a FASTQ file or a file of lines, split on the device.  The multi-pattern
+``resident_records`` makes such a batch from a FASTQ file or a file of lines and ``resident_fasta`` from the contigs of a
+FASTA file, split on the device.  The multi-pattern
 calls take ``classes=IUPAC_DNA`` (or any mapping of pattern byte -> accepted sequence bytes) for degenerate patterns.
 """
 import io
@@ -30,6 +31,7 @@ from .batch import find_near_matches_batch, resident_batch
 from .multi_batch import find_near_matches_multi_batch
 from .assign import find_best_matches_batch, BestMatches
 from .records import resident_records, RecordBatch
+from .fasta import resident_fasta, FastaBatch
 from .classes import IUPAC_DNA
 
 __version__ = '0.1.0'
@@ -48,6 +50,8 @@ __all__ = [
     'resident_batch',
     'resident_records',
     'RecordBatch',
+    'resident_fasta',
+    'FastaBatch',
     'cache_info',
     'cache_clear',
     'UnsupportedSearch',

@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = (
     "fz_batch_assign", "fz_debug_assign_fold",
     "fz_batch_upload_records", "fz_batch_tables", "fz_debug_batch_bytes", "fz_debug_records_split", "fz_debug_scan_items",
     "fz_debug_records_ms",
+    "fz_batch_upload_fasta", "fz_batch_fasta_index", "fz_debug_fasta_split", "fz_debug_fasta_upper4", "fz_debug_fasta_src",
     "fz_subs_ngrams_multi_cls", "fz_subs_ngrams_multi_best_cls", "fz_batch_search_multi_cls", "fz_batch_assign_cls",
     "fz_debug_multi_plan_cls",
 )
@@ -206,6 +207,18 @@ def load_library():
             L.fz_debug_scan_items.argtypes = []
             L.fz_debug_records_ms.restype = ci
             L.fz_debug_records_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
+        if hasattr(L, "fz_batch_upload_fasta"):             # (absent from builds of earlier rounds named by FUZZYSEARCH_HIP_LIB for an A/B)
+            rip = ctypes.POINTER(FzRecordsInfo)
+            L.fz_batch_upload_fasta.restype = ci
+            L.fz_batch_upload_fasta.argtypes = [vp, vp, u64, u32, ctypes.POINTER(vp), rip]
+            L.fz_batch_fasta_index.restype = ci
+            L.fz_batch_fasta_index.argtypes = [vp, vp]
+            L.fz_debug_fasta_split.restype = ci
+            L.fz_debug_fasta_split.argtypes = [vp, u64, u32, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), rip]
+            L.fz_debug_fasta_upper4.restype = u32
+            L.fz_debug_fasta_upper4.argtypes = [u32]
+            L.fz_debug_fasta_src.restype = u64
+            L.fz_debug_fasta_src.argtypes = [u64, u64, u64, u64]
         if hasattr(L, "fz_subs_ngrams_multi_cls"):          # (absent from builds of earlier rounds named by FUZZYSEARCH_HIP_LIB for an A/B)
             for fn in (L.fz_subs_ngrams_multi_cls, L.fz_subs_ngrams_multi_best_cls):
                 fn.restype = ci
@@ -524,6 +537,52 @@ def records_split(text, lines_per_record, sequence_line, flags):
     return starts, ends, packed, d
 
 
+FA_UPPER = 1                                      # FZ_FA_UPPER
+_FASTA_DTYPE = None
+
+
+def fasta_dtype():
+    """The numpy dtype of an fz_fasta_row (include/fzhip.h)."""
+    global _FASTA_DTYPE
+    if _FASTA_DTYPE is None:
+        import numpy as np
+        _FASTA_DTYPE = np.dtype([(name, "<u8") for name in ("header_start", "header_len", "length", "offset", "linebases", "linewidth")])
+    return _FASTA_DTYPE
+
+
+def fasta_split(text, flags=0):
+    """fz_debug_fasta_split (no device): the split of fz_batch_upload_fasta on the host, through the functions its kernels run
+    -> (rows: structured array of fasta_dtype(), ends, packed bytes, info dict).  A malformed text raises ValueError as the
+    upload does; the exception carries the info dict as ``.info``."""
+    import numpy as np
+    L = load_library()
+    addr, n, keep = _buffer_address(text)
+    pr, pe, pp = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+    info = FzRecordsInfo()
+    rc = L.fz_debug_fasta_split(addr, n, flags, ctypes.byref(pr), ctypes.byref(pe), ctypes.byref(pp), ctypes.byref(info))
+    del keep
+    d = _records_info(info)
+    if rc != FZ_OK:
+        _raise_records(rc, d)
+    ns = d['n_seqs']
+    rows = np.frombuffer(ctypes.string_at(pr, ns * fasta_dtype().itemsize), dtype=fasta_dtype())
+    ends = np.frombuffer(ctypes.string_at(pe, ns * 8), dtype=np.uint64)
+    packed = ctypes.string_at(pp, d['packed_bytes'])
+    for p in (pr, pe, pp):
+        L.fz_free(p)
+    return rows, ends, packed, d
+
+
+def fasta_upper4(w):
+    """fz_debug_fasta_upper4: the gather's fold of four bytes (a 32-bit word)."""
+    return int(load_library().fz_debug_fasta_upper4(w))
+
+
+def fasta_src(offset, linebases, linewidth, q):
+    """fz_debug_fasta_src: where base q of a record with that offset, linebases and linewidth lies in the text."""
+    return int(load_library().fz_debug_fasta_src(offset, linebases, linewidth, q))
+
+
 def _records_info(info):
     return {'n_lines': int(info.n_lines), 'n_seqs': int(info.n_seqs), 'packed_bytes': int(info.packed_bytes),
             'bad_record': int(info.bad_record), 'bad_reason': int(info.bad_reason)}
@@ -772,6 +831,31 @@ class Engine(object):
         seq.info = d
         return seq
 
+    def upload_fasta(self, text, flags=0):
+        """fz_batch_upload_fasta: `text` (bytes-like: a FASTA file) is copied to the device once and split there into a batch of
+        its contigs -> a ResidentSequence like upload_records'.  A malformed text raises ValueError naming the record."""
+        addr, n, keep = _buffer_address(text)
+        h = ctypes.c_void_p()
+        info = FzRecordsInfo()
+        with self._lock:
+            rc = self._lib.fz_batch_upload_fasta(self._h, addr, n, flags, ctypes.byref(h), ctypes.byref(info))
+        del keep
+        d = _records_info(info)
+        if rc != FZ_OK:
+            _raise_records(rc, d)
+        seq = ResidentSequence(self, h, d['packed_bytes'])
+        seq.n_seqs = d['n_seqs']
+        seq.info = d
+        return seq
+
+    def fasta_index(self, batch):
+        """fz_batch_fasta_index -> the rows of an upload_fasta handle: a structured array of fasta_dtype()."""
+        import numpy as np
+        rows = np.zeros(batch.n_seqs, dtype=fasta_dtype())
+        with self._lock:
+            _check(self._lib.fz_batch_fasta_index(batch._h, rows.ctypes.data))
+        return rows
+
     def batch_tables(self, batch):
         """fz_batch_tables -> (src_starts, ends): numpy uint64 arrays of the batch's n_seqs sequences — where each one starts
         in the text it was cut from (upload_batch: its offset in the packed bytes) and where it ends in the packed bytes."""
@@ -790,7 +874,7 @@ class Engine(object):
         return buf.raw[:batch.nbytes]
 
     def records_ms(self):
-        """fz_debug_records_ms: {h2d, kernels, ends_d2h, call} milliseconds of this engine's last upload_records."""
+        """fz_debug_records_ms: {h2d, kernels, ends_d2h, call} milliseconds of this engine's last upload_records / upload_fasta."""
         ms = (ctypes.c_double * 4)()
         with self._lock:
             _check(self._lib.fz_debug_records_ms(self._h, ms))

@@ -1606,3 +1606,85 @@ FZ_HD int fz_rscan_levels(uint64_t n, uint64_t *blocks) {
     }
     return l;
 }
+
+// ---------------------------------------------------------------------------------------------
+// FASTA (fz_batch_upload_fasta; fz_kernels.h: fz_fa_*_kernel): the rule of `samtools faidx`.  Lines are the records path's
+// (nl[], fz_rec_line; trailing empty lines dropped first).  A line whose first byte is '>' is a header and opens a record;
+// every other line is a sequence line of the record the nearest header above it opened.  Per record: linebases = the
+// content length of its first sequence line, linewidth = the distance from that line's first byte to the next line's
+// first byte (to the end of the text when there is none), offset = the position of its first base; all three 0 for a
+// record without sequence lines, whose offset is the position behind the header line.  The smallest error key
+// (record << 8 | reason, fz_rec_err_key) is the one reported; the reasons follow the FASTQ ones:
+//     5 the text does not start with '>' (record 0)            6 an empty sequence line
+//     7 a sequence line that is not the record's last differs from linebases / linewidth, or the last is longer than linebases
+// head[r] = the line of record r's header (head[n_seqs] = n_lines), rank[i] = the headers in front of line i.
+#define FZ_FA_UPPER 1u                 // = FZ_FA_UPPER (include/fzhip.h)
+#define FZ_FA_E_START 5u
+#define FZ_FA_E_EMPTY 6u
+#define FZ_FA_E_WIDTH 7u
+
+struct FzFaRow { uint64_t header_start, header_len, length, offset, linebases, linewidth; };   // = fz_fasta_row
+
+// Where line i ends with its terminator: the first byte of line i + 1, or the end of the text.
+FZ_HD uint64_t fz_fa_line_next(uint64_t n, const uint64_t *nl, uint64_t n_nl, uint64_t i) { return i < n_nl ? nl[i] + 1u : n; }
+
+FZ_HD uint64_t fz_fa_is_head(const uint8_t *text, const uint64_t *nl, uint64_t i) { return text[i ? nl[i - 1] + 1u : 0u] == '>' ? 1u : 0u; }
+
+// The text's own error key (FZ_REC_NO_ERROR: none).
+FZ_HD uint64_t fz_fa_text_key(const uint8_t *text, uint64_t n) {
+    return (n && text[0] != '>') ? fz_rec_err_key(0, FZ_FA_E_START) : FZ_REC_NO_ERROR;
+}
+
+// record -> its row and the verdict on its last sequence line, from its first and last sequence line only.
+struct FzFaOut { FzFaRow row; uint32_t reason; };
+FZ_HD FzFaOut fz_fa_measure(const uint8_t *text, uint64_t n, const uint64_t *nl, uint64_t n_nl, const uint64_t *head, uint64_t r) {
+    FzFaOut o;
+    const uint64_t h = head[r], lines = head[r + 1] - h - 1u;
+    const FzRecLine hl = fz_rec_line(text, n, nl, n_nl, h);
+    o.row.header_start = hl.start + 1u;
+    o.row.header_len = hl.end - hl.start - 1u;
+    o.reason = FZ_REC_OK;
+    if (lines == 0) {
+        o.row.length = 0; o.row.offset = fz_fa_line_next(n, nl, n_nl, h); o.row.linebases = 0; o.row.linewidth = 0;
+        return o;
+    }
+    const FzRecLine f = fz_rec_line(text, n, nl, n_nl, h + 1u);
+    const FzRecLine l = fz_rec_line(text, n, nl, n_nl, h + lines);
+    o.row.offset = f.start;
+    o.row.linebases = f.end - f.start;
+    o.row.linewidth = fz_fa_line_next(n, nl, n_nl, h + 1u) - f.start;
+    o.row.length = (lines - 1u) * o.row.linebases + (l.end - l.start);
+    if (l.end - l.start > o.row.linebases) o.reason = FZ_FA_E_WIDTH;
+    return o;
+}
+
+// Sequence line i of a record with (linebases, linewidth); last: it is the record's last line.
+FZ_HD uint32_t fz_fa_line_check(const uint8_t *text, uint64_t n, const uint64_t *nl, uint64_t n_nl, uint64_t i, bool last,
+                                uint64_t linebases, uint64_t linewidth) {
+    const FzRecLine l = fz_rec_line(text, n, nl, n_nl, i);
+    const uint64_t len = l.end - l.start;
+    if (len == 0) return FZ_FA_E_EMPTY;
+    if (last) return len > linebases ? FZ_FA_E_WIDTH : FZ_REC_OK;
+    return (len != linebases || fz_fa_line_next(n, nl, n_nl, i) - l.start != linewidth) ? FZ_FA_E_WIDTH : FZ_REC_OK;
+}
+
+// Base q of a record -> its position in the text (linebases > 0: the record has bases).
+FZ_HD uint64_t fz_fa_src(uint64_t offset, uint64_t linebases, uint64_t linewidth, uint64_t q) {
+    if ((q | linebases) >> 32) return offset + (q / linebases) * linewidth + q % linebases;
+    const uint32_t q32 = (uint32_t)q, lb32 = (uint32_t)linebases;
+    return offset + (uint64_t)(q32 / lb32) * linewidth + q32 % lb32;
+}
+
+// ... and its column in its line (the same quotient: one division serves both).
+FZ_HD uint64_t fz_fa_col(uint64_t linebases, uint64_t q) {
+    if ((q | linebases) >> 32) return q % linebases;
+    return (uint32_t)q % (uint32_t)linebases;
+}
+
+// bytes.upper() of four bytes at once: bit 5 cleared in every byte of 'a' .. 'z' (no carry crosses a byte: the operands
+// are 7-bit), every other byte, those above 0x7f included, as it is.
+FZ_HD uint32_t fz_fa_upper4(uint32_t w) {
+    const uint32_t x = w & 0x7f7f7f7fu;
+    const uint32_t ge_a = x + 0x1f1f1f1fu, gt_z = x + 0x05050505u;
+    return w ^ ((ge_a & ~gt_z & ~w & 0x80808080u) >> 2);
+}

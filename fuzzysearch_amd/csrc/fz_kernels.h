@@ -2548,3 +2548,154 @@ __global__ __launch_bounds__(FZ_REC_THREADS) void fz_rec_gather_kernel(const uin
         __syncthreads();
     }
 }
+
+// ---------------------------------------------------------------------------------------------
+// FASTA (fz_batch_upload_fasta; fz_device.h: fz_fa_*): behind the records path's newline count, scan and line table,
+//   fz_fa_heads_kernel         one lane per line.  First pass: flag[i] = line i starts with '>' (n_lines + 1 entries, the
+//                              last one 0); its exclusive scan is rank[]: line i belongs to record rank[i + 1] - 1, and
+//                              rank[n_lines] = the records.  Second pass (head != null): head[rank[i]] = i for every header
+//                              line, head[n_seqs] = n_lines
+//   fz_fa_measure_kernel       one lane per record, from its first and last sequence line only: the row of the index, the
+//                              length for the scan, the longest length, the verdict on the last line
+//   fz_fa_check_kernel         one lane per line: a sequence line against its record's linebases / linewidth
+//   fz_fa_gather_kernel        packed[] by 16-byte pieces of the DESTINATION, the newlines left behind
+// As above the launch boundaries are the only ordering between workgroups.
+__global__ __launch_bounds__(FZ_REC_THREADS) void fz_fa_heads_kernel(const uint8_t *__restrict__ raw, const uint64_t *__restrict__ nl,
+                                                                     uint64_t n_lines, uint64_t *__restrict__ flag,
+                                                                     uint64_t *__restrict__ head) {
+    const uint64_t stride = (uint64_t)gridDim.x * FZ_REC_THREADS;
+    for (uint64_t i = (uint64_t)blockIdx.x * FZ_REC_THREADS + threadIdx.x; i <= n_lines; i += stride) {
+        if (!head) flag[i] = i < n_lines ? fz_fa_is_head(raw, nl, i) : 0u;
+        else if (i == n_lines || flag[i + 1] != flag[i]) head[flag[i]] = i;
+    }
+}
+
+// info as fz_rec_measure_kernel's.  starts[r] = the row's offset (fz_batch_tables), lens: n_seqs + 1 entries, the last one 0.
+__global__ __launch_bounds__(FZ_REC_THREADS) void fz_fa_measure_kernel(const uint8_t *__restrict__ raw, uint64_t n,
+                                                                       const uint64_t *__restrict__ nl, uint64_t n_nl,
+                                                                       const uint64_t *__restrict__ head, uint64_t n_seqs,
+                                                                       FzFaRow *__restrict__ rows, uint64_t *__restrict__ starts,
+                                                                       uint64_t *__restrict__ lens, unsigned long long *__restrict__ info) {
+    const uint64_t stride = (uint64_t)gridDim.x * FZ_REC_THREADS;
+    unsigned long long longest = 0;
+    for (uint64_t r = (uint64_t)blockIdx.x * FZ_REC_THREADS + threadIdx.x; r < n_seqs; r += stride) {
+        const FzFaOut o = fz_fa_measure(raw, n, nl, n_nl, head, r);
+        rows[r] = o.row;
+        starts[r] = o.row.offset;
+        lens[r] = o.row.length;
+        longest = o.row.length > longest ? o.row.length : longest;
+        if (o.reason != FZ_REC_OK) (void)atomicMin(&info[0], (unsigned long long)fz_rec_err_key(r, o.reason));
+    }
+#pragma unroll
+    for (uint32_t d = 32; d; d >>= 1) {
+        const unsigned long long o = __shfl_xor(longest, d, 64);
+        longest = o > longest ? o : longest;
+    }
+    if ((threadIdx.x & 63u) == 0 && longest > __hip_atomic_load(&info[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+        (void)atomicMax(&info[1], longest);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        lens[n_seqs] = 0;
+        const uint64_t key = fz_fa_text_key(raw, n);
+        if (key != FZ_REC_NO_ERROR) (void)atomicMin(&info[0], (unsigned long long)key);
+    }
+}
+
+// rank[] = the scanned flags, head[] and rows[] as above.  Lines in front of the first header belong to no record (the
+// text's own error, fz_fa_text_key, is smaller than any of theirs).
+__global__ __launch_bounds__(FZ_REC_THREADS) void fz_fa_check_kernel(const uint8_t *__restrict__ raw, uint64_t n,
+                                                                     const uint64_t *__restrict__ nl, uint64_t n_nl, uint64_t n_lines,
+                                                                     const uint64_t *__restrict__ rank, const uint64_t *__restrict__ head,
+                                                                     const FzFaRow *__restrict__ rows, unsigned long long *__restrict__ info) {
+    const uint64_t stride = (uint64_t)gridDim.x * FZ_REC_THREADS;
+    for (uint64_t i = (uint64_t)blockIdx.x * FZ_REC_THREADS + threadIdx.x; i < n_lines; i += stride) {
+        const uint64_t c = rank[i + 1];
+        if (c == 0 || head[c - 1u] == i) continue;         // no record yet; a header line
+        const uint64_t r = c - 1u;
+        const uint32_t why = fz_fa_line_check(raw, n, nl, n_nl, i, i + 1u == head[r + 1u], rows[r].linebases, rows[r].linewidth);
+        if (why == FZ_REC_OK) continue;
+        const unsigned long long key = fz_rec_err_key(r, why);
+        if (key < __hip_atomic_load(&info[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) (void)atomicMin(&info[0], key);
+    }
+}
+
+__device__ __forceinline__ uint4 fz_fa_upper16(uint4 v) {
+    v.x = fz_fa_upper4(v.x); v.y = fz_fa_upper4(v.y); v.z = fz_fa_upper4(v.z); v.w = fz_fa_upper4(v.w);
+    return v;
+}
+
+// Bytes 0 .. room - 1 of a, the others of b (0 < room < 16).
+__device__ __forceinline__ uint32_t fz_fa_merge4(uint32_t a, uint32_t b, uint32_t room, uint32_t first) {
+    const uint32_t k = room > first ? room - first : 0u;
+    const uint32_t m = k >= 4u ? 0xffffffffu : (1u << (8u * k)) - 1u;
+    return (a & m) | (b & ~m);
+}
+
+// at[j] = where record j starts in packed[] (n_seqs + 1 entries, at[n_seqs] = total > 0); rows[j]: its offset, linebases
+// and linewidth in the text.  Base q of record j lies at fz_fa_src(rows[j], q).  A piece inside one record:
+//   - inside one line: one unaligned 16-byte load, one aligned 16-byte store;
+//   - across a line end, linebases >= 16 (3 pieces in 15 of 60-column lines): the piece holds `room` bytes of this line and
+//     16 - room of the next one, which starts linewidth - linebases behind this line's end.  Two unaligned 16-byte loads,
+//     at src and at src + (linewidth - linebases): byte i of the first is the piece's byte i for i < room, byte i of the
+//     second for i >= room (the second load is shifted by the terminator's width), merged by a byte mask;
+//   - linebases < 16 (a piece may hold three lines), a piece across a record's end, the last piece: byte by byte.
+// The over-read guard: neither slack behind the buffer nor a byte path near its end is needed, because every 16-byte load
+// covers only bytes between the source positions of the piece's first and last base (src <= load, load + 16 <= the last
+// base's position + 1 <= n): the one-line load reads exactly the 16 bases; of the two merged loads the first ends in front
+// of the second's end, and the second ends with the piece's last base.  (raw is whole tiles besides.)
+__global__ __launch_bounds__(FZ_REC_THREADS) void fz_fa_gather_kernel(const uint8_t *__restrict__ raw, const FzFaRow *__restrict__ rows,
+                                                                      const uint64_t *__restrict__ at, uint64_t n_seqs, uint64_t total,
+                                                                      uint32_t flags, uint8_t *__restrict__ packed) {
+    __shared__ uint64_t bound[2];
+    const uint64_t *ends = at + 1;
+    const uint64_t ntiles = (total + FZ_TILE_BYTES - 1u) / FZ_TILE_BYTES;
+    const bool upper = (flags & FZ_FA_UPPER) != 0;
+    for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const uint64_t p0 = t * (uint64_t)FZ_TILE_BYTES;
+        const uint64_t p1 = p0 + FZ_TILE_BYTES < total ? p0 + FZ_TILE_BYTES : total;
+        if (threadIdx.x < 2u) {                            // the records of the tile's first and last byte
+            const uint64_t target = threadIdx.x ? p1 - 1u : p0;
+            uint64_t lo = 0, hi = n_seqs - 1u;
+            while (lo < hi) {                              // first j with ends[j] > target (target < total = ends[n_seqs - 1])
+                const uint64_t mid = lo + ((hi - lo) >> 1);
+                if (ends[mid] > target) hi = mid; else lo = mid + 1u;
+            }
+            bound[threadIdx.x] = lo;
+        }
+        __syncthreads();
+        const uint64_t jlo = bound[0], jhi = bound[1];
+        for (uint32_t q = 0; q < FZ_TILE_BYTES / 16u / FZ_REC_THREADS; ++q) {
+            uint64_t p = p0 + (uint64_t)(q * FZ_REC_THREADS + threadIdx.x) * 16u;
+            if (p >= p1) continue;
+            uint64_t lo = jlo, hi = jhi;
+            while (lo < hi) {
+                const uint64_t mid = lo + ((hi - lo) >> 1);
+                if (ends[mid] > p) hi = mid; else lo = mid + 1u;
+            }
+            uint64_t j = lo;
+            if (p + 16u <= ends[j]) {                      // the piece lies inside record j
+                const uint64_t off = rows[j].offset, lb = rows[j].linebases, lw = rows[j].linewidth, b = p - at[j];
+                const uint64_t src = fz_fa_src(off, lb, lw, b), room = lb - fz_fa_col(lb, b);
+                if (room >= 16u || lb >= 16u) {
+                    uint4 v;
+                    __builtin_memcpy(&v, raw + src, 16);
+                    if (room < 16u) {
+                        uint4 w;
+                        __builtin_memcpy(&w, raw + src + (lw - lb), 16);
+                        const uint32_t rm = (uint32_t)room;
+                        v.x = fz_fa_merge4(v.x, w.x, rm, 0u); v.y = fz_fa_merge4(v.y, w.y, rm, 4u);
+                        v.z = fz_fa_merge4(v.z, w.z, rm, 8u); v.w = fz_fa_merge4(v.w, w.w, rm, 12u);
+                    }
+                    *reinterpret_cast<uint4 *>(packed + p) = upper ? fz_fa_upper16(v) : v;
+                    continue;
+                }
+            }
+            const uint64_t pe = p + 16u < total ? p + 16u : total;
+            for (; p < pe; ++p) {
+                while (ends[j] <= p) ++j;                  // (p < total: such a j exists; records without bases are passed)
+                const uint32_t c = raw[fz_fa_src(rows[j].offset, rows[j].linebases, rows[j].linewidth, p - at[j])];
+                packed[p] = (uint8_t)(upper ? fz_fa_upper4(c) : c);
+            }
+        }
+        __syncthreads();
+    }
+}

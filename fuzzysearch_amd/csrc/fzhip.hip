@@ -181,7 +181,7 @@ struct DevState {
     // hipMalloc + hipFree per chunk would dominate)
     uint8_t *spare_alloc = nullptr;
     uint64_t spare_bytes = 0;
-    hipEvent_t rec_ev[8] = {};                   // fz_batch_upload_records: the spans of its copy and kernels (created on first use)
+    hipEvent_t rec_ev[10] = {};                  // fz_batch_upload_records, _fasta: the spans of its copy and kernels (created on first use)
     uint64_t first_copy = 512;                   // records fetched with the header (tracks the last count)
     bool header_zeroed = false;                  // the counters were already zeroed after the last D2H copy
     bool verify_launched = false;                // the last enqueue ran fz_verify_kernel (ev[2] recorded)
@@ -472,6 +472,9 @@ struct fz_seq {
     // the sequences' offsets in the text they were cut from stay on the device until somebody asks (fz_batch_tables)
     uint64_t *d_ends_base = nullptr;
     uint64_t *d_src_starts = nullptr;
+    // fz_batch_upload_fasta: the index rows, on the device until somebody asks (fz_batch_fasta_index)
+    FzFaRow *d_fa_rows = nullptr;
+    bool is_fasta = false;
 };
 
 namespace {
@@ -2610,9 +2613,10 @@ void fz_seq_release(fz_seq *seq) {
         else if (seq->d_ends) (void)hipFree(seq->d_ends);
         if (seq->d_first) (void)hipFree(seq->d_first);
     }
-    if (seq->ctx && seq->d_src_starts) {
+    if (seq->ctx && (seq->d_src_starts || seq->d_fa_rows)) {
         (void)hipSetDevice(seq->ctx->devs[0].device);
-        (void)hipFree(seq->d_src_starts);
+        if (seq->d_src_starts) (void)hipFree(seq->d_src_starts);
+        if (seq->d_fa_rows) (void)hipFree(seq->d_fa_rows);
     }
     delete seq;
 }
@@ -2782,6 +2786,66 @@ int rec_malloc_bytes(void **p, uint64_t bytes) {
 }
 #define rec_malloc(pp, count) rec_malloc_bytes(reinterpret_cast<void **>(pp), std::max<uint64_t>(1, (count)) * sizeof(**(pp)))
 
+// The last step of the uploads that split a text: the handle of fz_batch_upload over `total` bytes, which gather(d_buf)
+// enqueues between the events ev and ev + 1.  at = the scanned length table (n_seqs + 1 entries) and starts = the sequences'
+// offsets in the text: the handle owns both from here on (the pointers are cleared).  *d2h_ms: the host's wait for ends[].
+int rec_make_handle(fz_ctx *ctx, uint64_t n_seqs, uint64_t total, uint64_t longest, uint64_t *&at, uint64_t *&starts, int ev,
+                    double *d2h_ms, fz_seq **out, const std::function<void(uint8_t *)> &gather) {
+    DevState &d = ctx->devs[0];
+    auto mark = [&](int i) { if (ctx->timing) (void)hipEventRecord(d.rec_ev[i], d.stream); };
+    fz_seq *seq = new (std::nothrow) fz_seq();
+    if (!seq) return fail(FZ_ENOMEM, "out of memory");
+    seq->ctx = ctx;
+    seq->n = total;
+    seq->is_batch = true;
+    seq->n_seqs = n_seqs;
+    seq->max_seq_len = longest;
+    FzGeom g{};
+    g.n = total;
+    g.buf_off = 0;
+    g.buf_len = total;
+    g.own_lo = 0;
+    g.own_hi = total;
+    seq->shards.emplace_back();
+    int rc = alloc_one(ctx, 0, g, seq->shards.back());
+    mark(ev);
+    if (rc == FZ_OK && total) gather(seq->shards.back().d_buf);
+    mark(ev + 1);
+    if (rc == FZ_OK) rc = ensure_hits(d, std::max<uint64_t>(1u << 20, total / 64));
+    std::vector<uint32_t> first;
+    if (rc == FZ_OK && n_seqs) {
+        const auto t0 = std::chrono::steady_clock::now();
+        seq->ends.resize(n_seqs);
+        hipError_t e = hipMemcpyAsync(seq->ends.data(), at + 1, n_seqs * sizeof(uint64_t), hipMemcpyDeviceToHost, d.stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
+        *d2h_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        const uint64_t nt = (total + FZ_TILE_BYTES - 1) / FZ_TILE_BYTES;
+        if (e == hipSuccess) {
+            first.resize(nt + 1);
+            fz_ragged_first(seq->ends.data(), n_seqs, nt, first.data());
+            e = hipMalloc(reinterpret_cast<void **>(&seq->d_first), first.size() * sizeof(uint32_t));
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(seq->d_first, first.data(), first.size() * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream);
+        if (e != hipSuccess) rc = fail(e == hipErrorOutOfMemory ? FZ_ENOMEM : FZ_EDEVICE, "batch tables: %s", hipGetErrorString(e));
+        seq->d_ends_base = at;                             // the handle owns the scanned table and the text offsets from here on
+        seq->d_ends = at + 1;
+        seq->d_src_starts = starts;
+        at = nullptr;
+        starts = nullptr;
+        FzGeom &sg = seq->shards.back().geom;
+        sg.seg_org = reinterpret_cast<uint64_t>(seq->d_ends);
+        sg.seg_j0 = reinterpret_cast<uint64_t>(seq->d_first);
+        sg.seg_j1 = n_seqs;
+    }
+    if (rc == FZ_OK) {
+        hipError_t e = hipStreamSynchronize(d.stream);    // the text and first[] are only borrowed; the transient buffers go
+        if (e != hipSuccess) rc = fail(FZ_EDEVICE, "upload failed: %s", hipGetErrorString(e));
+    }
+    if (rc) { fz_seq_release(seq); return rc; }
+    *out = seq;
+    return FZ_OK;
+}
+
 }  // namespace
 
 int fz_batch_upload_records(fz_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t lines_per_record, uint32_t sequence_line,
@@ -2863,58 +2927,13 @@ int fz_batch_upload_records(fz_ctx *ctx, const uint8_t *text, uint64_t n, uint32
     if (key != FZ_REC_NO_ERROR) return rec_report(what, key, info);
     if (info) info->packed_bytes = total;
     // 3. the handle of fz_batch_upload, its bytes gathered on the device
-    fz_seq *seq = new (std::nothrow) fz_seq();
-    if (!seq) return fail(FZ_ENOMEM, "out of memory");
-    seq->ctx = ctx;
-    seq->n = total;
-    seq->is_batch = true;
-    seq->n_seqs = n_seqs;
-    seq->max_seq_len = longest;
-    FzGeom g{};
-    g.n = total;
-    g.buf_off = 0;
-    g.buf_len = total;
-    g.own_lo = 0;
-    g.own_hi = total;
-    seq->shards.emplace_back();
-    rc = alloc_one(ctx, 0, g, seq->shards.back());
-    mark(5);
-    if (rc == FZ_OK && total)
-        hipLaunchKernelGGL(fz_rec_gather_kernel, dim3(rec_grid(d, (total + FZ_TILE_BYTES - 1) / FZ_TILE_BYTES)), dim3(FZ_REC_THREADS), 0, d.stream,
-                           tmp.raw, tmp.starts, tmp.at, n_seqs, total, seq->shards.back().d_buf);
-    mark(6);
-    if (rc == FZ_OK) rc = ensure_hits(d, std::max<uint64_t>(1u << 20, total / 64));
+    fz_seq *seq = nullptr;
     double d2h_ms = 0;
-    std::vector<uint32_t> first;
-    if (rc == FZ_OK && n_seqs) {
-        const auto t0 = std::chrono::steady_clock::now();
-        seq->ends.resize(n_seqs);
-        hipError_t e = hipMemcpyAsync(seq->ends.data(), tmp.at + 1, n_seqs * sizeof(uint64_t), hipMemcpyDeviceToHost, d.stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
-        d2h_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        const uint64_t nt = (total + FZ_TILE_BYTES - 1) / FZ_TILE_BYTES;
-        if (e == hipSuccess) {
-            first.resize(nt + 1);
-            fz_ragged_first(seq->ends.data(), n_seqs, nt, first.data());
-            e = hipMalloc(reinterpret_cast<void **>(&seq->d_first), first.size() * sizeof(uint32_t));
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(seq->d_first, first.data(), first.size() * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream);
-        if (e != hipSuccess) rc = fail(e == hipErrorOutOfMemory ? FZ_ENOMEM : FZ_EDEVICE, "batch tables: %s", hipGetErrorString(e));
-        seq->d_ends_base = tmp.at;                         // the handle owns the scanned table and the text offsets from here on
-        seq->d_ends = tmp.at + 1;
-        seq->d_src_starts = tmp.starts;
-        tmp.at = nullptr;
-        tmp.starts = nullptr;
-        FzGeom &sg = seq->shards.back().geom;
-        sg.seg_org = reinterpret_cast<uint64_t>(seq->d_ends);
-        sg.seg_j0 = reinterpret_cast<uint64_t>(seq->d_first);
-        sg.seg_j1 = n_seqs;
-    }
-    if (rc == FZ_OK) {
-        hipError_t e = hipStreamSynchronize(d.stream);    // the text and first[] are only borrowed; the transient buffers go
-        if (e != hipSuccess) rc = fail(FZ_EDEVICE, "upload failed: %s", hipGetErrorString(e));
-    }
-    if (rc) { fz_seq_release(seq); return rc; }
+    rc = rec_make_handle(ctx, n_seqs, total, longest, tmp.at, tmp.starts, 5, &d2h_ms, &seq, [&](uint8_t *d_buf) {
+        hipLaunchKernelGGL(fz_rec_gather_kernel, dim3(rec_grid(d, (total + FZ_TILE_BYTES - 1) / FZ_TILE_BYTES)), dim3(FZ_REC_THREADS), 0, d.stream,
+                           tmp.raw, tmp.starts, tmp.at, n_seqs, total, d_buf);
+    });
+    if (rc) return rc;
     if (timed) {
         ctx->rec_ms[0] = span_ms(d.rec_ev[0], d.rec_ev[1]);
         ctx->rec_ms[1] = span_ms(d.rec_ev[1], d.rec_ev[2]) + span_ms(d.rec_ev[3], d.rec_ev[4]) + span_ms(d.rec_ev[5], d.rec_ev[6]);
@@ -3008,6 +3027,246 @@ int fz_debug_records_split(const uint8_t *text, uint64_t n, uint32_t lines_per_r
     }
     *src_starts = static_cast<uint64_t *>(ms); *ends = static_cast<uint64_t *>(me); *packed = static_cast<uint8_t *>(mp);
     return FZ_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// FASTA (fz_batch_upload_fasta): the records path's line table, then headers ranked, records measured, lines checked and
+// the bases gathered without their newlines (fz_kernels.h: fz_fa_*_kernel; the rule: fz_device.h).
+
+namespace {
+static_assert(sizeof(FzFaRow) == sizeof(fz_fasta_row) && sizeof(fz_fasta_row) == 48, "fz_fasta_row is FzFaRow");
+
+const char *fa_reason_text(uint32_t reason) {
+    switch (reason) {
+    case FZ_FA_E_START: return "the text does not start with '>'";
+    case FZ_FA_E_EMPTY: return "an empty line inside the sequence";
+    case FZ_FA_E_WIDTH: return "the sequence lines are not of one length and width (all but the last, which may be shorter)";
+    }
+    return "malformed";
+}
+
+int fa_check_args(const uint8_t *text, uint64_t n, uint32_t flags) {
+    if (!text && n) return fail(FZ_EINVAL, "null argument");
+    if (flags & ~FZ_FA_UPPER) return fail(FZ_EINVAL, "unknown fasta flags");
+    if (n >= (1ull << FZ_IDX_BITS)) return fail(FZ_EUNSUPPORTED, "sequence too long");
+    return FZ_OK;
+}
+
+int fa_report(uint64_t key, fz_records_info *info) {
+    if (info) { info->bad_record = fz_rec_err_record(key); info->bad_reason = fz_rec_err_reason(key); }
+    return fail(FZ_EINVAL, "fasta: record %llu: %s", (unsigned long long)fz_rec_err_record(key), fa_reason_text(fz_rec_err_reason(key)));
+}
+
+struct FaTmp {                                            // the call's transient device memory besides RecTmp's
+    uint64_t *rank = nullptr, *head = nullptr;
+    FzFaRow *rows = nullptr;
+    ~FaTmp() {
+        for (void *p : {(void *)rank, (void *)head, (void *)rows})
+            if (p) (void)hipFree(p);
+    }
+};
+}  // namespace
+
+int fz_batch_upload_fasta(fz_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t flags, fz_seq **out, fz_records_info *info) {
+    if (!ctx || !out) return fail(FZ_EINVAL, "null argument");
+    *out = nullptr;
+    if (info) *info = fz_records_info{};
+    int rc = fa_check_args(text, n, flags);
+    if (rc) return rc;
+    if (ctx->devs.size() != 1 || ctx->snapshot || comm_multi_process(ctx))
+        return fail(FZ_EUNSUPPORTED, "batches are searched by single-device, non-collective contexts");
+    if (ctx->npend || ctx->stream_inflight) return fail(FZ_EINVAL, "a search of this context is in flight");
+    const auto t_call = std::chrono::steady_clock::now();
+    n = rec_trim(text, n);
+    DevState &d = ctx->devs[0];
+    HIP_TRY(hipSetDevice(d.device));
+    const bool timed = ctx->timing;
+    if (timed) for (auto &ev : d.rec_ev) if (!ev) HIP_TRY(hipEventCreate(&ev));
+    auto mark = [&](int i) { if (timed) (void)hipEventRecord(d.rec_ev[i], d.stream); };
+    RecTmp tmp;
+    FaTmp fa;
+    const uint64_t ntiles = (n + FZ_TILE_BYTES - 1) / FZ_TILE_BYTES;
+    uint64_t n_nl = 0, scratch_items = rec_scan_scratch(ntiles + 1);
+    auto scan = [&](uint64_t *data, uint64_t items) -> int {   // the exclusive scan, its scratch grown when this one needs more
+        if (rec_scan_scratch(items) > scratch_items) {
+            (void)hipFree(tmp.scratch);
+            tmp.scratch = nullptr;
+            scratch_items = rec_scan_scratch(items);
+            if (int r = rec_malloc(&tmp.scratch, scratch_items)) return r;
+        }
+        rec_scan(d, data, items, tmp.scratch);
+        return FZ_OK;
+    };
+    // 1. as fz_batch_upload_records: the text in whole tiles, the newlines per tile, their scan
+    mark(0);
+    if (n) {
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&tmp.raw), ntiles * FZ_TILE_BYTES));
+        if (ntiles * FZ_TILE_BYTES > n) HIP_TRY(hipMemsetAsync(tmp.raw + n, 0, ntiles * FZ_TILE_BYTES - n, d.stream));
+        HIP_TRY(hipMemcpyAsync(tmp.raw, text, n, hipMemcpyHostToDevice, d.stream));
+    }
+    mark(1);
+    if (n) {
+        if ((rc = rec_malloc(&tmp.counts, ntiles + 1))) return rc;
+        if ((rc = rec_malloc(&tmp.scratch, scratch_items))) return rc;
+        HIP_TRY(hipMemsetAsync(tmp.counts + ntiles, 0, sizeof(uint64_t), d.stream));
+        hipLaunchKernelGGL(fz_rec_count_kernel, dim3(rec_grid(d, ntiles)), dim3(FZ_REC_THREADS), 0, d.stream, tmp.raw, ntiles, tmp.counts);
+        rec_scan(d, tmp.counts, ntiles + 1, tmp.scratch);
+    }
+    mark(2);
+    if (n) {
+        HIP_TRY(hipMemcpyAsync(&n_nl, tmp.counts + ntiles, sizeof(uint64_t), hipMemcpyDeviceToHost, d.stream));
+        HIP_TRY(hipStreamSynchronize(d.stream));
+        if (n_nl > n) return fail(FZ_EDEVICE, "fasta: the newline count is outside the text");
+    }
+    const uint64_t n_lines = fz_rec_n_lines(text, n, n_nl);
+    // 2. the line table; one lane per line flags the headers; the scan of the flags ranks every line into its record
+    uint64_t n_seqs = 0;
+    mark(3);
+    if (n_lines) {
+        if ((rc = rec_malloc(&tmp.nl, n_nl))) return rc;
+        if ((rc = rec_malloc(&fa.rank, n_lines + 1))) return rc;
+        if (n_nl) hipLaunchKernelGGL(fz_rec_lines_kernel, dim3(rec_grid(d, ntiles)), dim3(FZ_REC_THREADS), 0, d.stream, tmp.raw, ntiles, tmp.counts, tmp.nl);
+        hipLaunchKernelGGL(fz_fa_heads_kernel, dim3(rec_grid(d, n_lines / FZ_REC_THREADS + 1)), dim3(FZ_REC_THREADS), 0, d.stream, tmp.raw, tmp.nl,
+                           n_lines, fa.rank, (uint64_t *)nullptr);
+        if ((rc = scan(fa.rank, n_lines + 1))) return rc;
+    }
+    mark(4);
+    if (n_lines) {
+        HIP_TRY(hipMemcpyAsync(&n_seqs, fa.rank + n_lines, sizeof(uint64_t), hipMemcpyDeviceToHost, d.stream));
+        HIP_TRY(hipStreamSynchronize(d.stream));
+        if (n_seqs > n_lines) return fail(FZ_EDEVICE, "fasta: the header count is outside the text");
+    }
+    if (info) { info->n_lines = n_lines; info->n_seqs = n_seqs; }
+    if (n_seqs >= (1ull << 32)) return fail(FZ_EUNSUPPORTED, "more than 2^32 - 1 sequences in a batch");
+    // 3. every header's line; one lane per record; one lane per line; the scan of the lengths
+    uint64_t key = fz_fa_text_key(text, n), total = 0, longest = 0;
+    mark(5);
+    if (n_seqs) {
+        if ((rc = rec_malloc(&fa.head, n_seqs + 1))) return rc;
+        if ((rc = rec_malloc(&fa.rows, n_seqs))) return rc;
+        if ((rc = rec_malloc(&tmp.starts, n_seqs))) return rc;
+        if ((rc = rec_malloc(&tmp.at, n_seqs + 1))) return rc;
+        if ((rc = rec_malloc(&tmp.info, 2))) return rc;
+        HIP_TRY(hipMemsetAsync(tmp.info, 0xff, sizeof(uint64_t), d.stream));
+        HIP_TRY(hipMemsetAsync(tmp.info + 1, 0, sizeof(uint64_t), d.stream));
+        hipLaunchKernelGGL(fz_fa_heads_kernel, dim3(rec_grid(d, n_lines / FZ_REC_THREADS + 1)), dim3(FZ_REC_THREADS), 0, d.stream, tmp.raw, tmp.nl,
+                           n_lines, fa.rank, fa.head);
+        hipLaunchKernelGGL(fz_fa_measure_kernel, dim3(rec_grid(d, (n_seqs + FZ_REC_THREADS - 1) / FZ_REC_THREADS)), dim3(FZ_REC_THREADS), 0, d.stream,
+                           tmp.raw, n, tmp.nl, n_nl, fa.head, n_seqs, fa.rows, tmp.starts, tmp.at, tmp.info);
+        hipLaunchKernelGGL(fz_fa_check_kernel, dim3(rec_grid(d, (n_lines + FZ_REC_THREADS - 1) / FZ_REC_THREADS)), dim3(FZ_REC_THREADS), 0, d.stream,
+                           tmp.raw, n, tmp.nl, n_nl, n_lines, fa.rank, fa.head, fa.rows, tmp.info);
+        if ((rc = scan(tmp.at, n_seqs + 1))) return rc;
+    }
+    mark(6);
+    if (n_seqs) {
+        unsigned long long got[2] = {0, 0};
+        HIP_TRY(hipMemcpyAsync(got, tmp.info, sizeof(got), hipMemcpyDeviceToHost, d.stream));
+        HIP_TRY(hipMemcpyAsync(&total, tmp.at + n_seqs, sizeof(uint64_t), hipMemcpyDeviceToHost, d.stream));
+        HIP_TRY(hipStreamSynchronize(d.stream));
+        key = std::min<uint64_t>(key, got[0]);
+        longest = got[1];
+        if (key == FZ_REC_NO_ERROR && (total > n || longest > total)) return fail(FZ_EDEVICE, "fasta: the packed length is outside the text");
+    }
+    if (key != FZ_REC_NO_ERROR) return fa_report(key, info);
+    if (info) info->packed_bytes = total;
+    // 4. the handle of fz_batch_upload, its bases gathered on the device; the index rows stay with it
+    fz_seq *seq = nullptr;
+    double d2h_ms = 0;
+    rc = rec_make_handle(ctx, n_seqs, total, longest, tmp.at, tmp.starts, 7, &d2h_ms, &seq, [&](uint8_t *d_buf) {
+        hipLaunchKernelGGL(fz_fa_gather_kernel, dim3(rec_grid(d, (total + FZ_TILE_BYTES - 1) / FZ_TILE_BYTES)), dim3(FZ_REC_THREADS), 0, d.stream,
+                           tmp.raw, fa.rows, tmp.at, n_seqs, total, flags, d_buf);
+    });
+    if (rc) return rc;
+    seq->d_fa_rows = fa.rows;
+    fa.rows = nullptr;
+    seq->is_fasta = true;
+    if (timed) {
+        ctx->rec_ms[0] = span_ms(d.rec_ev[0], d.rec_ev[1]);
+        ctx->rec_ms[1] = span_ms(d.rec_ev[1], d.rec_ev[2]) + span_ms(d.rec_ev[3], d.rec_ev[4]) + span_ms(d.rec_ev[5], d.rec_ev[6]) +
+                         span_ms(d.rec_ev[7], d.rec_ev[8]);
+        ctx->rec_ms[2] = d2h_ms;
+    }
+    ctx->rec_ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+    ctx->live.push_back(seq);
+    *out = seq;
+    return FZ_OK;
+}
+
+int fz_batch_fasta_index(const fz_seq *batch, fz_fasta_row *rows) {
+    if (!batch || !rows) return fail(FZ_EINVAL, "null argument");
+    if (!batch->is_batch || !batch->is_fasta) return fail(FZ_EINVAL, "fz_batch_fasta_index takes a handle of fz_batch_upload_fasta");
+    if (batch->n_seqs == 0) return FZ_OK;
+    HIP_TRY(hipSetDevice(batch->ctx->devs[0].device));
+    HIP_TRY(hipMemcpy(rows, batch->d_fa_rows, batch->n_seqs * sizeof(fz_fasta_row), hipMemcpyDeviceToHost));
+    return FZ_OK;
+}
+
+int fz_debug_fasta_split(const uint8_t *text, uint64_t n, uint32_t flags, fz_fasta_row **rows, uint64_t **ends, uint8_t **packed,
+                         fz_records_info *info) {
+    if (!rows || !ends || !packed) return fail(FZ_EINVAL, "null argument");
+    *rows = nullptr; *ends = nullptr; *packed = nullptr;
+    if (info) *info = fz_records_info{};
+    int rc = fa_check_args(text, n, flags);
+    if (rc) return rc;
+    n = rec_trim(text, n);
+    std::vector<uint64_t> nl;
+    for (uint64_t i = 0; i < n; ++i) if (text[i] == '\n') nl.push_back(i);
+    const uint64_t n_nl = nl.size();
+    const uint64_t n_lines = fz_rec_n_lines(text, n, n_nl);
+    std::vector<uint64_t> rank(n_lines + 1), head;       // the kernels' tables: the scanned flags, every header's line
+    uint64_t n_seqs = 0;
+    for (uint64_t i = 0; i < n_lines; ++i) {
+        rank[i] = n_seqs;
+        if (fz_fa_is_head(text, nl.data(), i)) { head.push_back(i); ++n_seqs; }
+    }
+    rank[n_lines] = n_seqs;
+    head.push_back(n_lines);
+    if (info) { info->n_lines = n_lines; info->n_seqs = n_seqs; }
+    if (n_seqs >= (1ull << 32)) return fail(FZ_EUNSUPPORTED, "more than 2^32 - 1 sequences in a batch");
+    uint64_t key = fz_fa_text_key(text, n), total = 0;
+    std::vector<FzFaRow> recs(n_seqs);
+    for (uint64_t r = 0; r < n_seqs; ++r) {
+        const FzFaOut o = fz_fa_measure(text, n, nl.data(), n_nl, head.data(), r);
+        recs[r] = o.row;
+        if (o.reason != FZ_REC_OK) key = std::min(key, fz_rec_err_key(r, o.reason));
+        total += o.row.length;
+    }
+    for (uint64_t i = 0; i < n_lines; ++i) {
+        const uint64_t c = rank[i + 1];
+        if (c == 0 || head[c - 1] == i) continue;
+        const uint32_t why = fz_fa_line_check(text, n, nl.data(), n_nl, i, i + 1 == head[c], recs[c - 1].linebases, recs[c - 1].linewidth);
+        if (why != FZ_REC_OK) key = std::min(key, fz_rec_err_key(c - 1, why));
+    }
+    if (key != FZ_REC_NO_ERROR) return fa_report(key, info);
+    if (info) info->packed_bytes = total;
+    void *mr = nullptr, *me = nullptr, *mp = nullptr;
+    rc = alloc_out(n_seqs, sizeof(fz_fasta_row), &mr);
+    if (rc == FZ_OK) rc = alloc_out(n_seqs, sizeof(uint64_t), &me);
+    if (rc == FZ_OK) rc = alloc_out((total + 3) / 4 * 4, 1, &mp);
+    if (rc) { release_out(mr); release_out(me); release_out(mp); return rc; }
+    uint8_t *dst = static_cast<uint8_t *>(mp);
+    uint64_t at = 0;
+    for (uint64_t r = 0; r < n_seqs; ++r) {
+        memcpy(static_cast<fz_fasta_row *>(mr) + r, &recs[r], sizeof(fz_fasta_row));
+        for (uint64_t q = 0; q < recs[r].length; ++q) dst[at + q] = text[fz_fa_src(recs[r].offset, recs[r].linebases, recs[r].linewidth, q)];
+        at += recs[r].length;
+        static_cast<uint64_t *>(me)[r] = at;
+    }
+    if (flags & FZ_FA_UPPER)                              // a dword at a time, as the gather folds (bytes behind `total`: the buffer's own)
+        for (uint64_t i = 0; i < total; i += 4) {
+            uint32_t w = 0;
+            memcpy(&w, dst + i, 4);
+            w = fz_fa_upper4(w);
+            memcpy(dst + i, &w, 4);
+        }
+    *rows = static_cast<fz_fasta_row *>(mr); *ends = static_cast<uint64_t *>(me); *packed = dst;
+    return FZ_OK;
+}
+
+uint32_t fz_debug_fasta_upper4(uint32_t w) { return fz_fa_upper4(w); }
+
+uint64_t fz_debug_fasta_src(uint64_t offset, uint64_t linebases, uint64_t linewidth, uint64_t q) {
+    return linebases ? fz_fa_src(offset, linebases, linewidth, q) : offset;
 }
 
 int fz_search_exact(fz_ctx *ctx, fz_seq *seq, const uint8_t *p, uint32_t m, uint64_t lo, uint64_t hi,

@@ -12,8 +12,8 @@ What a line is: it ends at ``\\n`` or, the last one, at the end of the text; one
                      line count is a multiple of 4, the first line starts with ``@``, the third with ``+``, the fourth is as
                      long as the second.  The first malformed record raises ``ValueError`` naming it.
 
-Not understood: FASTQ records whose sequence spans several lines, FASTA (newlines inside a sequence have to be removed,
-which is another gather) and compressed files — decompress and pass the bytes.
+Not understood: FASTQ records whose sequence spans several lines and compressed files — decompress and pass the bytes.
+FASTA (newlines inside a sequence have to be removed, which is another gather) is ``resident_fasta``'s (fasta.py).
 """
 import mmap
 import os

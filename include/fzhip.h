@@ -357,7 +357,7 @@ int fz_debug_batch_segment(const uint64_t *offs, uint64_t n_seqs, uint64_t idx, 
  *   smallest (record, reason) is an error: 1 the line count is no multiple of 4 (record = lines / 4), 2 line 0 does not
  *   start with '@', 3 line 2 does not start with '+', 4 line 3 is not as long as line 1.  Then the call answers FZ_EINVAL
  *   with *out = NULL, info->bad_record / bad_reason filled in and nothing left allocated.  (bad_reason = 0: no error.)
- *   Multi-line FASTQ, FASTA and compressed input are not understood.
+ *   Multi-line FASTQ and compressed input are not understood; FASTA is fz_batch_upload_fasta's.
  * The handle is a batch handle like fz_batch_upload's (same refusals: several devices or a communicator, a search in
  * flight, a text of 2^48 bytes or more, 2^32 sequences or more); fz_batch_search, _multi and _assign cannot tell them apart. */
 #define FZ_REC_FASTQ_CHECKS 1u
@@ -384,6 +384,40 @@ int fz_debug_records_split(const uint8_t *text, uint64_t n, uint32_t lines_per_r
                            uint64_t **src_starts, uint64_t **ends, uint8_t **packed, fz_records_info *info);
 uint32_t fz_debug_scan_items(void);
 int fz_debug_records_ms(fz_ctx *ctx, double *ms4);
+
+/* FASTA: the contigs of a FASTA text become a batch on the device, by the rule of `samtools faidx`.  Lines are those of
+ * fz_batch_upload_records, trailing empty lines dropped first.  A line whose first byte is '>' is a header and opens a
+ * record; every other line is a sequence line of the record the nearest header above it opened; a record's sequence is the
+ * concatenation of its sequence lines' contents (none: an empty contig).  Per record: linebases = the content length of its
+ * first sequence line, linewidth = the distance from that line's first byte to the next line's first byte (to the end of the
+ * text when no line follows), offset = the position of its first base; all 0 for an empty contig, whose offset is the
+ * position behind the header line.  header_start / header_len: the header line's content without the '>'.
+ *   The smallest (record, reason) is an error, reported as fz_batch_upload_records reports the FASTQ ones (FZ_EINVAL, *out =
+ *   NULL, info->bad_record / bad_reason, nothing left allocated), with the reasons behind the FASTQ ones: 5 the text is not
+ *   empty and does not start with '>' (record 0), 6 an empty sequence line inside a record, 7 a sequence line that is not
+ *   the record's last has a content length or width other than linebases / linewidth, or the last one is longer than
+ *   linebases.  ';' comment lines, blank lines between records and compressed input are not understood.
+ *   Sequence bytes pass through untouched; FZ_FA_UPPER clears bit 5 of every byte in 'a' .. 'z' as they are gathered.
+ * On the device (fz_kernels.h: fz_fa_*_kernel): behind the newline table of the records path one lane per line flags the
+ * headers, the scan of the flags gives every line its record, one lane per record measures it from its first and last
+ * sequence line, one lane per line checks it, the lengths are scanned and the bases gathered without their newlines.
+ * Refusals, the handle, fz_batch_tables (src_starts[j] = offset of record j) and fz_debug_records_ms as fz_batch_upload_records.
+ * fz_batch_fasta_index: the n_seqs rows of such a handle, copied from the device on demand (FZ_EINVAL for any other handle). */
+#define FZ_FA_UPPER 1u
+typedef struct {
+    uint64_t header_start, header_len, length, offset, linebases, linewidth;
+} fz_fasta_row;
+
+int fz_batch_upload_fasta(fz_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t flags, fz_seq **out, fz_records_info *info);
+int fz_batch_fasta_index(const fz_seq *batch, fz_fasta_row *rows);
+/* Test hooks, no device: the split of fz_batch_upload_fasta on the host through the functions its kernels run (fz_device.h:
+ * fz_fa_measure, fz_fa_line_check, fz_fa_src, fz_fa_upper4); *rows, *ends (n_seqs entries) and *packed are released with
+ * fz_free and are NULL after an error.  fz_debug_fasta_upper4: the gather's fold of four bytes.  fz_debug_fasta_src: the
+ * position in the text of base q of a record with that offset, linebases and linewidth (linebases = 0: offset). */
+int fz_debug_fasta_split(const uint8_t *text, uint64_t n, uint32_t flags, fz_fasta_row **rows, uint64_t **ends, uint8_t **packed,
+                         fz_records_info *info);
+uint32_t fz_debug_fasta_upper4(uint32_t w);
+uint64_t fz_debug_fasta_src(uint64_t offset, uint64_t linebases, uint64_t linewidth, uint64_t q);
 
 /* has_near_match_* (substitutions_only.py:139-145, :218-233; generic_search.py:240-253): *found = 1 iff the
  * corresponding search would return at least one record.  Nothing is ordered or copied, and device work that starts
