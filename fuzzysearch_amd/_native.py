@@ -518,23 +518,7 @@ def records_split(text, lines_per_record, sequence_line, flags):
     kernels run -> (src_starts, ends, packed bytes, info dict).  A malformed text raises ValueError as the upload does;
     the exception carries the info dict as ``.info``."""
     import numpy as np
-    L = load_library()
-    addr, n, keep = _buffer_address(text)
-    ps, pe, pp = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
-    info = FzRecordsInfo()
-    rc = L.fz_debug_records_split(addr, n, lines_per_record, sequence_line, flags, ctypes.byref(ps), ctypes.byref(pe),
-                                  ctypes.byref(pp), ctypes.byref(info))
-    del keep
-    d = _records_info(info)
-    if rc != FZ_OK:
-        _raise_records(rc, d)
-    ns = d['n_seqs']
-    starts = np.ctypeslib.as_array(ctypes.cast(ps, ctypes.POINTER(ctypes.c_uint64)), shape=(ns,)).copy() if ns else np.zeros(0, np.uint64)
-    ends = np.ctypeslib.as_array(ctypes.cast(pe, ctypes.POINTER(ctypes.c_uint64)), shape=(ns,)).copy() if ns else np.zeros(0, np.uint64)
-    packed = ctypes.string_at(pp, d['packed_bytes'])
-    for p in (ps, pe, pp):
-        L.fz_free(p)
-    return starts, ends, packed, d
+    return _split_twin('fz_debug_records_split', text, (lines_per_record, sequence_line, flags), np.dtype(np.uint64))
 
 
 FA_UPPER = 1                                      # FZ_FA_UPPER
@@ -554,23 +538,7 @@ def fasta_split(text, flags=0):
     """fz_debug_fasta_split (no device): the split of fz_batch_upload_fasta on the host, through the functions its kernels run
     -> (rows: structured array of fasta_dtype(), ends, packed bytes, info dict).  A malformed text raises ValueError as the
     upload does; the exception carries the info dict as ``.info``."""
-    import numpy as np
-    L = load_library()
-    addr, n, keep = _buffer_address(text)
-    pr, pe, pp = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
-    info = FzRecordsInfo()
-    rc = L.fz_debug_fasta_split(addr, n, flags, ctypes.byref(pr), ctypes.byref(pe), ctypes.byref(pp), ctypes.byref(info))
-    del keep
-    d = _records_info(info)
-    if rc != FZ_OK:
-        _raise_records(rc, d)
-    ns = d['n_seqs']
-    rows = np.frombuffer(ctypes.string_at(pr, ns * fasta_dtype().itemsize), dtype=fasta_dtype())
-    ends = np.frombuffer(ctypes.string_at(pe, ns * 8), dtype=np.uint64)
-    packed = ctypes.string_at(pp, d['packed_bytes'])
-    for p in (pr, pe, pp):
-        L.fz_free(p)
-    return rows, ends, packed, d
+    return _split_twin('fz_debug_fasta_split', text, (flags,), fasta_dtype())
 
 
 def fasta_upper4(w):
@@ -581,6 +549,28 @@ def fasta_upper4(w):
 def fasta_src(offset, linebases, linewidth, q):
     """fz_debug_fasta_src: where base q of a record with that offset, linebases and linewidth lies in the text."""
     return int(load_library().fz_debug_fasta_src(offset, linebases, linewidth, q))
+
+
+def _split_twin(entry, text, args, row_dtype):
+    """One host twin of a text upload: entry(text, n, *args, &rows, &ends, &packed, &info) -> (rows of row_dtype, ends,
+    packed bytes, info dict), the library's arrays copied and freed."""
+    import numpy as np
+    L = load_library()
+    addr, n, keep = _buffer_address(text)
+    pr, pe, pp = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+    info = FzRecordsInfo()
+    rc = getattr(L, entry)(addr, n, *args, ctypes.byref(pr), ctypes.byref(pe), ctypes.byref(pp), ctypes.byref(info))
+    del keep
+    d = _records_info(info)
+    if rc != FZ_OK:
+        _raise_records(rc, d)
+    ns = d['n_seqs']
+    rows = np.frombuffer(ctypes.string_at(pr, ns * row_dtype.itemsize), dtype=row_dtype).copy()
+    ends = np.frombuffer(ctypes.string_at(pe, ns * 8), dtype=np.uint64).copy()
+    packed = ctypes.string_at(pp, d['packed_bytes'])
+    for p in (pr, pe, pp):
+        L.fz_free(p)
+    return rows, ends, packed, d
 
 
 def _records_info(info):
@@ -816,29 +806,21 @@ class Engine(object):
         """fz_batch_upload_records: `text` (bytes-like: a FASTQ file, a file of lines) is copied to the device once and split
         there into a batch -> a ResidentSequence like upload_batch's, with `.n_seqs` and `.info` (n_lines, n_seqs,
         packed_bytes).  A malformed text raises ValueError naming the record (`.info` on the exception: bad_record, bad_reason)."""
-        addr, n, keep = _buffer_address(text)
-        h = ctypes.c_void_p()
-        info = FzRecordsInfo()
-        with self._lock:
-            rc = self._lib.fz_batch_upload_records(self._h, addr, n, lines_per_record, sequence_line, flags, ctypes.byref(h),
-                                                   ctypes.byref(info))
-        del keep
-        d = _records_info(info)
-        if rc != FZ_OK:
-            _raise_records(rc, d)
-        seq = ResidentSequence(self, h, d['packed_bytes'])
-        seq.n_seqs = d['n_seqs']
-        seq.info = d
-        return seq
+        return self._upload_text(self._lib.fz_batch_upload_records, text, lines_per_record, sequence_line, flags)
 
     def upload_fasta(self, text, flags=0):
         """fz_batch_upload_fasta: `text` (bytes-like: a FASTA file) is copied to the device once and split there into a batch of
         its contigs -> a ResidentSequence like upload_records'.  A malformed text raises ValueError naming the record."""
+        return self._upload_text(self._lib.fz_batch_upload_fasta, text, flags)
+
+    def _upload_text(self, entry, text, *args):
+        """entry(ctx, text, n, *args, &handle, &info) -> the batch handle with `.n_seqs` and `.info`; a refusal raises with
+        the info dict as `.info`."""
         addr, n, keep = _buffer_address(text)
         h = ctypes.c_void_p()
         info = FzRecordsInfo()
         with self._lock:
-            rc = self._lib.fz_batch_upload_fasta(self._h, addr, n, flags, ctypes.byref(h), ctypes.byref(info))
+            rc = entry(self._h, addr, n, *args, ctypes.byref(h), ctypes.byref(info))
         del keep
         d = _records_info(info)
         if rc != FZ_OK:

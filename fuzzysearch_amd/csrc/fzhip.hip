@@ -461,16 +461,16 @@ struct fz_seq {
     // on the sequence's first collective search; the ranks' segments are merged in that order
     std::vector<uint64_t> rank_lo;
     // fz_batch_upload: n_seqs sequences packed back to back (fz_device.h: ragged segments).  ends = the host copy of the
-    // cumulative end offsets (rows -> sequences), d_ends / d_first the device tables (null for an empty batch).
+    // cumulative end offsets (rows -> sequences).  The device tables (null for an empty batch): d_ends_base = the scanned
+    // length table, n_seqs + 1 entries of which the first is 0, so the kernels' ends[] is d_ends_base + 1; d_first.
     bool is_batch = false;
     uint64_t n_seqs = 0;
     std::vector<uint64_t> ends;
-    uint64_t *d_ends = nullptr;
+    uint64_t *d_ends_base = nullptr;
     uint32_t *d_first = nullptr;
     uint64_t max_seq_len = 0;                    // the longest sequence (fz_batch_assign: local starts are 32-bit key fields)
-    // fz_batch_upload_records: d_ends is the second entry of the scanned length table (d_ends_base, the allocation), and
-    // the sequences' offsets in the text they were cut from stay on the device until somebody asks (fz_batch_tables)
-    uint64_t *d_ends_base = nullptr;
+    // fz_batch_upload_records, _fasta: the sequences' offsets in the text they were cut from stay on the device until
+    // somebody asks (fz_batch_tables)
     uint64_t *d_src_starts = nullptr;
     // fz_batch_upload_fasta: the index rows, on the device until somebody asks (fz_batch_fasta_index)
     FzFaRow *d_fa_rows = nullptr;
@@ -2607,18 +2607,98 @@ void fz_seq_release(fz_seq *seq) {
             }
         }
     }
-    if (seq->ctx && (seq->d_ends || seq->d_first || seq->d_ends_base)) {
+    if (seq->ctx && (seq->d_ends_base || seq->d_first || seq->d_src_starts || seq->d_fa_rows)) {
         (void)hipSetDevice(seq->ctx->devs[0].device);
-        if (seq->d_ends_base) (void)hipFree(seq->d_ends_base);
-        else if (seq->d_ends) (void)hipFree(seq->d_ends);
-        if (seq->d_first) (void)hipFree(seq->d_first);
-    }
-    if (seq->ctx && (seq->d_src_starts || seq->d_fa_rows)) {
-        (void)hipSetDevice(seq->ctx->devs[0].device);
-        if (seq->d_src_starts) (void)hipFree(seq->d_src_starts);
-        if (seq->d_fa_rows) (void)hipFree(seq->d_fa_rows);
+        for (void *p : {(void *)seq->d_ends_base, (void *)seq->d_first, (void *)seq->d_src_starts, (void *)seq->d_fa_rows})
+            if (p) (void)hipFree(p);
     }
     delete seq;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Batch uploads.  fz_batch_upload, fz_batch_upload_records and fz_batch_upload_fasta share their admission
+// (batch_upload_admit) and the builder of their handle (batch_make_handle); the two that split a text on the device also
+// share one Ingest per call: the line table, the growing scan, the verdict words and the timing epilogue.
+
+static int batch_single_device(fz_ctx *ctx, fz_seq *batch) {
+    if (ctx->devs.size() != 1 || ctx->snapshot || comm_multi_process(ctx) || (batch && batch->is_batch && batch->shards.size() != 1))
+        return fail(FZ_EUNSUPPORTED, "batches are searched by single-device, non-collective contexts");
+    return FZ_OK;
+}
+
+// What every batch upload asks of its context: the searches' rule, and nothing in flight.
+static int batch_upload_admit(fz_ctx *ctx) {
+    if (int rc = batch_single_device(ctx, nullptr)) return rc;
+    if (ctx->npend || ctx->stream_inflight) return fail(FZ_EINVAL, "a search of this context is in flight");
+    return FZ_OK;
+}
+
+// The handle of every batch upload: `total` bytes, which fill(d_buf) enqueues on the device's stream, and the tables over
+// them (fz_device.h: ragged segments).  The scanned length table (n_seqs + 1 entries, the first 0) comes either from the
+// host (host_offs: it is uploaded) or from the device (d_table: the handle owns it from here on, the pointer is cleared,
+// and ends[] is read back; *d2h_ms = the host's wait for it).  An empty batch keeps null tables.  Not yet in ctx->live.
+static int batch_make_handle(fz_ctx *ctx, uint64_t n_seqs, uint64_t total, uint64_t longest, const uint64_t *host_offs,
+                             uint64_t *&d_table, double *d2h_ms, fz_seq **out, const std::function<int(uint8_t *)> &fill) {
+    static_assert(FZ_RAG_TILE_BITS == FZ_TILE_BITS, "first[] is indexed by the scan's tiles");
+    DevState &d = ctx->devs[0];
+    fz_seq *seq = new (std::nothrow) fz_seq();
+    if (!seq) return fail(FZ_ENOMEM, "out of memory");
+    seq->ctx = ctx;
+    seq->n = total;
+    seq->is_batch = true;
+    seq->n_seqs = n_seqs;
+    seq->max_seq_len = longest;
+    FzGeom g{};
+    g.n = total;
+    g.buf_off = 0;
+    g.buf_len = total;
+    g.own_lo = 0;
+    g.own_hi = total;
+    seq->shards.emplace_back();
+    int rc = alloc_one(ctx, 0, g, seq->shards.back());
+    if (rc == FZ_OK) rc = fill(seq->shards.back().d_buf);
+    // grow the hit list with the batch: n-gram hits on 4-letter text run at ~G * n / 4^L
+    if (rc == FZ_OK) rc = ensure_hits(d, std::max<uint64_t>(1u << 20, total / 64));
+    std::vector<uint32_t> first;
+    if (rc == FZ_OK && n_seqs) {
+        hipError_t e;
+        if (host_offs) {
+            seq->ends.assign(host_offs + 1, host_offs + 1 + n_seqs);
+            e = hipMalloc(reinterpret_cast<void **>(&seq->d_ends_base), (n_seqs + 1) * sizeof(uint64_t));
+            if (e == hipSuccess) e = hipMemcpyAsync(seq->d_ends_base, host_offs, (n_seqs + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, d.stream);
+        } else {
+            const auto t0 = std::chrono::steady_clock::now();
+            seq->ends.resize(n_seqs);
+            e = hipMemcpyAsync(seq->ends.data(), d_table + 1, n_seqs * sizeof(uint64_t), hipMemcpyDeviceToHost, d.stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
+            *d2h_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            seq->d_ends_base = d_table;
+            d_table = nullptr;
+        }
+        // per tile the first sequence that touches it
+        const uint64_t ntiles = (total + FZ_TILE_BYTES - 1) / FZ_TILE_BYTES;
+        if (e == hipSuccess) {
+            first.resize(ntiles + 1);
+            fz_ragged_first(seq->ends.data(), n_seqs, ntiles, first.data());
+            e = hipMalloc(reinterpret_cast<void **>(&seq->d_first), first.size() * sizeof(uint32_t));
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(seq->d_first, first.data(), first.size() * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream);
+        if (e != hipSuccess) {
+            rc = fail(e == hipErrorOutOfMemory ? FZ_ENOMEM : FZ_EDEVICE, "batch tables: %s", hipGetErrorString(e));
+        } else {
+            FzGeom &sg = seq->shards.back().geom;
+            sg.seg_org = reinterpret_cast<uint64_t>(seq->d_ends_base + 1);
+            sg.seg_j0 = reinterpret_cast<uint64_t>(seq->d_first);
+            sg.seg_j1 = n_seqs;
+        }
+    }
+    if (rc == FZ_OK) {
+        hipError_t e = hipStreamSynchronize(d.stream);    // the caller's bytes and the tables' host copies are only borrowed
+        if (e != hipSuccess) rc = fail(FZ_EDEVICE, "upload failed: %s", hipGetErrorString(e));
+    }
+    if (rc) { fz_seq_release(seq); return rc; }
+    *out = seq;
+    return FZ_OK;
 }
 
 int fz_batch_upload(fz_ctx *ctx, const uint8_t *bytes, const uint64_t *offs, uint64_t n_seqs, fz_seq **out) {
@@ -2633,48 +2713,16 @@ int fz_batch_upload(fz_ctx *ctx, const uint8_t *bytes, const uint64_t *offs, uin
     const uint64_t n = offs[n_seqs];
     if (!bytes && n) return fail(FZ_EINVAL, "null argument");
     if (n >= (1ull << FZ_IDX_BITS)) return fail(FZ_EUNSUPPORTED, "sequence too long");
-    if (ctx->devs.size() != 1 || ctx->snapshot || comm_multi_process(ctx))
-        return fail(FZ_EUNSUPPORTED, "batches are searched by single-device, non-collective contexts");
-    if (ctx->npend || ctx->stream_inflight) return fail(FZ_EINVAL, "a search of this context is in flight");
-    fz_seq *seq = new (std::nothrow) fz_seq();
-    if (!seq) return fail(FZ_ENOMEM, "out of memory");
-    seq->ctx = ctx;
-    seq->n = n;
-    seq->is_batch = true;
-    seq->n_seqs = n_seqs;
-    seq->max_seq_len = longest;
-    FzGeom g{};
-    g.n = n;
-    g.buf_off = 0;
-    g.buf_len = n;
-    g.own_lo = 0;
-    g.own_hi = n;
-    seq->shards.emplace_back();
-    int rc = upload_one(ctx, 0, bytes, g, seq->shards.back());
-    std::vector<uint32_t> first;
-    if (rc == FZ_OK && n_seqs) {
-        // the tables: cumulative end offsets, and per tile the first sequence that touches it (fz_device.h)
-        static_assert(FZ_RAG_TILE_BITS == FZ_TILE_BITS, "first[] is indexed by the scan's tiles");
-        DevState &d = ctx->devs[0];
-        seq->ends.assign(offs + 1, offs + 1 + n_seqs);
-        const uint64_t ntiles = (n + FZ_TILE_BYTES - 1) / FZ_TILE_BYTES;
-        first.resize(ntiles + 1);
-        fz_ragged_first(seq->ends.data(), n_seqs, ntiles, first.data());
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(&seq->d_ends), n_seqs * sizeof(uint64_t));
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&seq->d_first), first.size() * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMemcpyAsync(seq->d_ends, seq->ends.data(), n_seqs * sizeof(uint64_t), hipMemcpyHostToDevice, d.stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(seq->d_first, first.data(), first.size() * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream);
-        if (e != hipSuccess) rc = fail(e == hipErrorOutOfMemory ? FZ_ENOMEM : FZ_EDEVICE, "batch tables: %s", hipGetErrorString(e));
-        FzGeom &sg = seq->shards.back().geom;
-        sg.seg_org = reinterpret_cast<uint64_t>(seq->d_ends);
-        sg.seg_j0 = reinterpret_cast<uint64_t>(seq->d_first);
-        sg.seg_j1 = n_seqs;
-    }
-    if (rc == FZ_OK) {
-        hipError_t e = hipStreamSynchronize(ctx->devs[0].stream);      // bytes, offs and the tables' host copies are only borrowed
-        if (e != hipSuccess) rc = fail(FZ_EDEVICE, "upload failed: %s", hipGetErrorString(e));
-    }
-    if (rc) { fz_seq_release(seq); return rc; }
+    int rc = batch_upload_admit(ctx);
+    if (rc) return rc;
+    // offs[] is the scanned length table that the text uploads make on the device: it goes up as it is
+    fz_seq *seq = nullptr;
+    uint64_t *no_table = nullptr;
+    rc = batch_make_handle(ctx, n_seqs, n, longest, offs, no_table, nullptr, &seq, [&](uint8_t *d_buf) {
+        if (n) HIP_TRY(hipMemcpyAsync(d_buf, bytes, n, hipMemcpyHostToDevice, ctx->devs[0].stream));
+        return FZ_OK;
+    });
+    if (rc) return rc;
     ctx->live.push_back(seq);
     *out = seq;
     return FZ_OK;
@@ -2705,6 +2753,7 @@ int fz_debug_batch_segment(const uint64_t *offs, uint64_t n_seqs, uint64_t idx, 
 
 // ---------------------------------------------------------------------------------------------
 // Records (fz_batch_upload_records): the text crosses PCIe once and is split where it lies (fz_kernels.h: fz_rec_*_kernel).
+// What it shares with fz_batch_upload_fasta is here too: the reasons and their report, the scan, Ingest, the twins' helpers.
 
 namespace {
 const char *rec_reason_text(uint32_t reason) {
@@ -2713,6 +2762,9 @@ const char *rec_reason_text(uint32_t reason) {
     case FZ_REC_E_AT: return "the header line does not start with '@'";
     case FZ_REC_E_PLUS: return "the separator line does not start with '+'";
     case FZ_REC_E_QUAL: return "the quality line is not as long as the sequence line";
+    case FZ_FA_E_START: return "the text does not start with '>'";
+    case FZ_FA_E_EMPTY: return "an empty line inside the sequence";
+    case FZ_FA_E_WIDTH: return "the sequence lines are not of one length and width (all but the last, which may be shorter)";
     }
     return "malformed";
 }
@@ -2769,16 +2821,6 @@ void rec_scan(DevState &d, uint64_t *data, uint64_t n, uint64_t *scratch) {
                            d.stream, at[l], cnt[l], l < levels ? at[l + 1] : (uint64_t *)nullptr);
 }
 
-struct RecTmp {                                           // the call's transient device memory
-    uint8_t *raw = nullptr;
-    uint64_t *counts = nullptr, *scratch = nullptr, *nl = nullptr, *starts = nullptr, *at = nullptr;
-    unsigned long long *info = nullptr;
-    ~RecTmp() {
-        for (void *p : {(void *)raw, (void *)counts, (void *)scratch, (void *)nl, (void *)starts, (void *)at, (void *)info})
-            if (p) (void)hipFree(p);
-    }
-};
-
 int rec_malloc_bytes(void **p, uint64_t bytes) {
     hipError_t e = hipMalloc(p, bytes);
     if (e != hipSuccess) { *p = nullptr; return fail(e == hipErrorOutOfMemory ? FZ_ENOMEM : FZ_EDEVICE, "records: %s", hipGetErrorString(e)); }
@@ -2786,64 +2828,154 @@ int rec_malloc_bytes(void **p, uint64_t bytes) {
 }
 #define rec_malloc(pp, count) rec_malloc_bytes(reinterpret_cast<void **>(pp), std::max<uint64_t>(1, (count)) * sizeof(**(pp)))
 
-// The last step of the uploads that split a text: the handle of fz_batch_upload over `total` bytes, which gather(d_buf)
-// enqueues between the events ev and ev + 1.  at = the scanned length table (n_seqs + 1 entries) and starts = the sequences'
-// offsets in the text: the handle owns both from here on (the pointers are cleared).  *d2h_ms: the host's wait for ends[].
-int rec_make_handle(fz_ctx *ctx, uint64_t n_seqs, uint64_t total, uint64_t longest, uint64_t *&at, uint64_t *&starts, int ev,
-                    double *d2h_ms, fz_seq **out, const std::function<void(uint8_t *)> &gather) {
-    DevState &d = ctx->devs[0];
-    auto mark = [&](int i) { if (ctx->timing) (void)hipEventRecord(d.rec_ev[i], d.stream); };
-    fz_seq *seq = new (std::nothrow) fz_seq();
-    if (!seq) return fail(FZ_ENOMEM, "out of memory");
-    seq->ctx = ctx;
-    seq->n = total;
-    seq->is_batch = true;
-    seq->n_seqs = n_seqs;
-    seq->max_seq_len = longest;
-    FzGeom g{};
-    g.n = total;
-    g.buf_off = 0;
-    g.buf_len = total;
-    g.own_lo = 0;
-    g.own_hi = total;
-    seq->shards.emplace_back();
-    int rc = alloc_one(ctx, 0, g, seq->shards.back());
-    mark(ev);
-    if (rc == FZ_OK && total) gather(seq->shards.back().d_buf);
-    mark(ev + 1);
-    if (rc == FZ_OK) rc = ensure_hits(d, std::max<uint64_t>(1u << 20, total / 64));
-    std::vector<uint32_t> first;
-    if (rc == FZ_OK && n_seqs) {
-        const auto t0 = std::chrono::steady_clock::now();
-        seq->ends.resize(n_seqs);
-        hipError_t e = hipMemcpyAsync(seq->ends.data(), at + 1, n_seqs * sizeof(uint64_t), hipMemcpyDeviceToHost, d.stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
-        *d2h_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        const uint64_t nt = (total + FZ_TILE_BYTES - 1) / FZ_TILE_BYTES;
-        if (e == hipSuccess) {
-            first.resize(nt + 1);
-            fz_ragged_first(seq->ends.data(), n_seqs, nt, first.data());
-            e = hipMalloc(reinterpret_cast<void **>(&seq->d_first), first.size() * sizeof(uint32_t));
+// One call of fz_batch_upload_records or fz_batch_upload_fasta: the transient device memory (freed when the call ends), the
+// scan scratch with its capacity, the timing marks and the steps that the two calls share.  what ("records" / "fasta")
+// goes in front of the frame's own error texts.
+struct Ingest {
+    fz_ctx *ctx;
+    DevState &d;
+    const char *what;
+    const bool timed;
+    const std::chrono::steady_clock::time_point t_call = std::chrono::steady_clock::now();
+    int marks = 0;                                        // events recorded so far: mark() takes the next one
+    double d2h_ms = 0;
+    uint64_t n = 0, ntiles = 0, scratch_items = 0;
+    uint8_t *raw = nullptr;
+    uint64_t *counts = nullptr, *scratch = nullptr, *nl = nullptr, *starts = nullptr, *at = nullptr, *rank = nullptr, *head = nullptr;
+    FzFaRow *rows = nullptr;
+    unsigned long long *info = nullptr;
+
+    Ingest(fz_ctx *c, const char *w) : ctx(c), d(c->devs[0]), what(w), timed(c->timing) {}
+    ~Ingest() {
+        for (void *p : {(void *)raw, (void *)counts, (void *)scratch, (void *)nl, (void *)starts, (void *)at, (void *)rank, (void *)head,
+                        (void *)rows, (void *)info})
+            if (p) (void)hipFree(p);
+    }
+
+    void mark() {
+        if (timed && marks < (int)(sizeof(d.rec_ev) / sizeof(d.rec_ev[0]))) (void)hipEventRecord(d.rec_ev[marks], d.stream);
+        ++marks;
+    }
+
+    // The exclusive scan of data[0 .. items) in place, the scratch grown when this one needs more.
+    int scan(uint64_t *data, uint64_t items) {
+        if (rec_scan_scratch(items) > scratch_items) {
+            if (scratch) (void)hipFree(scratch);
+            scratch = nullptr;
+            scratch_items = rec_scan_scratch(items);
+            if (int rc = rec_malloc(&scratch, scratch_items)) return rc;
         }
-        if (e == hipSuccess) e = hipMemcpyAsync(seq->d_first, first.data(), first.size() * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream);
-        if (e != hipSuccess) rc = fail(e == hipErrorOutOfMemory ? FZ_ENOMEM : FZ_EDEVICE, "batch tables: %s", hipGetErrorString(e));
-        seq->d_ends_base = at;                             // the handle owns the scanned table and the text offsets from here on
-        seq->d_ends = at + 1;
-        seq->d_src_starts = starts;
-        at = nullptr;
-        starts = nullptr;
-        FzGeom &sg = seq->shards.back().geom;
-        sg.seg_org = reinterpret_cast<uint64_t>(seq->d_ends);
-        sg.seg_j0 = reinterpret_cast<uint64_t>(seq->d_first);
-        sg.seg_j1 = n_seqs;
+        rec_scan(d, data, items, scratch);
+        return FZ_OK;
     }
-    if (rc == FZ_OK) {
-        hipError_t e = hipStreamSynchronize(d.stream);    // the text and first[] are only borrowed; the transient buffers go
-        if (e != hipSuccess) rc = fail(FZ_EDEVICE, "upload failed: %s", hipGetErrorString(e));
+
+    // Stage 1 (marks 0 .. 3): the text in whole tiles (zeros behind it are no newlines), the newlines per tile, their
+    // exclusive scan with the total behind it, the count read back, and nl[], every newline's position, enqueued.
+    int line_table(const uint8_t *text, uint64_t n_, uint64_t *n_nl, uint64_t *n_lines) {
+        n = n_;
+        ntiles = (n + FZ_TILE_BYTES - 1) / FZ_TILE_BYTES;
+        *n_nl = 0;
+        HIP_TRY(hipSetDevice(d.device));
+        if (timed) for (auto &ev : d.rec_ev) if (!ev) HIP_TRY(hipEventCreate(&ev));
+        mark();
+        if (n) {
+            HIP_TRY(hipMalloc(reinterpret_cast<void **>(&raw), ntiles * FZ_TILE_BYTES));
+            if (ntiles * FZ_TILE_BYTES > n) HIP_TRY(hipMemsetAsync(raw + n, 0, ntiles * FZ_TILE_BYTES - n, d.stream));
+            HIP_TRY(hipMemcpyAsync(raw, text, n, hipMemcpyHostToDevice, d.stream));
+        }
+        mark();
+        if (n) {
+            if (int rc = rec_malloc(&counts, ntiles + 1)) return rc;
+            HIP_TRY(hipMemsetAsync(counts + ntiles, 0, sizeof(uint64_t), d.stream));
+            hipLaunchKernelGGL(fz_rec_count_kernel, dim3(rec_grid(d, ntiles)), dim3(FZ_REC_THREADS), 0, d.stream, raw, ntiles, counts);
+            if (int rc = scan(counts, ntiles + 1)) return rc;
+        }
+        mark();
+        if (n) {
+            HIP_TRY(hipMemcpyAsync(n_nl, counts + ntiles, sizeof(uint64_t), hipMemcpyDeviceToHost, d.stream));
+            HIP_TRY(hipStreamSynchronize(d.stream));
+            if (*n_nl > n) return fail(FZ_EDEVICE, "%s: the newline count is outside the text", what);
+        }
+        *n_lines = fz_rec_n_lines(text, n, *n_nl);
+        mark();                                           // the caller's kernels follow in this span, up to its next mark
+        if (*n_lines) {
+            if (int rc = rec_malloc(&nl, *n_nl)) return rc;
+            if (*n_nl) hipLaunchKernelGGL(fz_rec_lines_kernel, dim3(rec_grid(d, ntiles)), dim3(FZ_REC_THREADS), 0, d.stream, raw, ntiles, counts, nl);
+        }
+        return FZ_OK;
     }
-    if (rc) { fz_seq_release(seq); return rc; }
-    *out = seq;
-    return FZ_OK;
+
+    // The verdict words of the measure and check kernels: info[0] = the smallest error key, info[1] = the longest sequence.
+    int arm_verdict() {
+        if (int rc = rec_malloc(&info, 2)) return rc;
+        HIP_TRY(hipMemsetAsync(info, 0xff, sizeof(uint64_t), d.stream));
+        HIP_TRY(hipMemsetAsync(info + 1, 0, sizeof(uint64_t), d.stream));
+        return FZ_OK;
+    }
+
+    // ... read back with the packed length, the last entry of the scanned at[]; *key keeps the smaller of the caller's and
+    // the kernels'.  A malformed record is reported before the lengths are doubted: the FASTA kernels measure a refused
+    // text's records as they come.  For the records path the order makes no difference, since the lengths of the lines it
+    // keeps never sum to more than n.
+    int read_verdict(uint64_t n_seqs, uint64_t *key, uint64_t *total, uint64_t *longest) {
+        unsigned long long got[2] = {0, 0};
+        HIP_TRY(hipMemcpyAsync(got, info, sizeof(got), hipMemcpyDeviceToHost, d.stream));
+        HIP_TRY(hipMemcpyAsync(total, at + n_seqs, sizeof(uint64_t), hipMemcpyDeviceToHost, d.stream));
+        HIP_TRY(hipStreamSynchronize(d.stream));
+        *key = std::min<uint64_t>(*key, got[0]);
+        *longest = got[1];
+        if (*key == FZ_REC_NO_ERROR && (*total > n || *longest > *total)) return fail(FZ_EDEVICE, "%s: the packed length is outside the text", what);
+        return FZ_OK;
+    }
+
+    // The handle of fz_batch_upload over `total` bytes, which gather(d_buf) enqueues between two marks; at[] and starts[]
+    // become the handle's.
+    int handle(uint64_t n_seqs, uint64_t total, uint64_t longest, fz_seq **seq, const std::function<void(uint8_t *)> &gather) {
+        int rc = batch_make_handle(ctx, n_seqs, total, longest, nullptr, at, &d2h_ms, seq, [&](uint8_t *d_buf) {
+            mark();
+            if (total) gather(d_buf);
+            mark();
+            return FZ_OK;
+        });
+        if (rc == FZ_OK && n_seqs) { (*seq)->d_src_starts = starts; starts = nullptr; }
+        return rc;
+    }
+
+    // The last step: the spans of the marks go to rec_ms[] (the copy is (0, 1), the kernels are every (i, i + 1) of an odd
+    // i), and the handle is the caller's.
+    int finish(fz_seq *seq, fz_seq **out) {
+        if (timed) {
+            ctx->rec_ms[0] = span_ms(d.rec_ev[0], d.rec_ev[1]);
+            ctx->rec_ms[1] = 0;
+            for (int i = 1; i + 1 < marks; i += 2) ctx->rec_ms[1] += span_ms(d.rec_ev[i], d.rec_ev[i + 1]);
+            ctx->rec_ms[2] = d2h_ms;
+        }
+        ctx->rec_ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+        ctx->live.push_back(seq);
+        *out = seq;
+        return FZ_OK;
+    }
+};
+
+// The twins on the host (fz_debug_records_split, fz_debug_fasta_split): every newline's position, by the kernels' byte mask
+// word by word ...
+void host_line_table(const uint8_t *text, uint64_t n, std::vector<uint64_t> &nl) {
+    uint64_t i = 0;
+    for (; i + 4 <= n; i += 4) {
+        uint32_t w;
+        memcpy(&w, text + i, 4);
+        for (uint32_t m = fz_rec_nl_mask(w); m; m &= m - 1u) nl.push_back(i + ((uint32_t)__builtin_ctz(m) >> 3));
+    }
+    for (; i < n; ++i) if (text[i] == '\n') nl.push_back(i);
+}
+
+// ... and the three arrays they hand out: n_seqs rows of `row` bytes, n_seqs ends, the packed bytes.  All or none.
+int alloc_split_out(uint64_t n_seqs, size_t row, uint64_t packed, void **rows, void **ends, void **bytes) {
+    int rc = alloc_out(n_seqs, row, rows);
+    if (rc == FZ_OK) rc = alloc_out(n_seqs, sizeof(uint64_t), ends);
+    if (rc == FZ_OK) rc = alloc_out(packed, 1, bytes);
+    if (rc) { release_out(*rows); release_out(*ends); release_out(*bytes); *rows = *ends = *bytes = nullptr; }
+    return rc;
 }
 
 }  // namespace
@@ -2854,95 +2986,39 @@ int fz_batch_upload_records(fz_ctx *ctx, const uint8_t *text, uint64_t n, uint32
     *out = nullptr;
     if (info) *info = fz_records_info{};
     int rc = rec_check_args(text, n, lines_per_record, sequence_line, flags);
+    if (rc == FZ_OK) rc = batch_upload_admit(ctx);
     if (rc) return rc;
-    if (ctx->devs.size() != 1 || ctx->snapshot || comm_multi_process(ctx))
-        return fail(FZ_EUNSUPPORTED, "batches are searched by single-device, non-collective contexts");
-    if (ctx->npend || ctx->stream_inflight) return fail(FZ_EINVAL, "a search of this context is in flight");
-    const auto t_call = std::chrono::steady_clock::now();
-    const char *what = (flags & FZ_REC_FASTQ_CHECKS) ? "fastq" : "lines";
+    Ingest in(ctx, "records");
+    DevState &d = in.d;
     if (flags & FZ_REC_FASTQ_CHECKS) n = rec_trim(text, n);
-    DevState &d = ctx->devs[0];
-    HIP_TRY(hipSetDevice(d.device));
-    const bool timed = ctx->timing;
-    if (timed) for (auto &ev : d.rec_ev) if (!ev) HIP_TRY(hipEventCreate(&ev));
-    auto mark = [&](int i) { if (timed) (void)hipEventRecord(d.rec_ev[i], d.stream); };
-    RecTmp tmp;
-    const uint64_t ntiles = (n + FZ_TILE_BYTES - 1) / FZ_TILE_BYTES;
-    uint64_t n_nl = 0;
-    // 1. the text, whole tiles (zeros behind it are no newlines); newlines per tile; their exclusive scan, the total behind it
-    mark(0);
-    if (n) {
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&tmp.raw), ntiles * FZ_TILE_BYTES));
-        if (ntiles * FZ_TILE_BYTES > n) HIP_TRY(hipMemsetAsync(tmp.raw + n, 0, ntiles * FZ_TILE_BYTES - n, d.stream));
-        HIP_TRY(hipMemcpyAsync(tmp.raw, text, n, hipMemcpyHostToDevice, d.stream));
-    }
-    mark(1);
-    if (n) {
-        if ((rc = rec_malloc(&tmp.counts, ntiles + 1))) return rc;
-        if ((rc = rec_malloc(&tmp.scratch, rec_scan_scratch(ntiles + 1)))) return rc;
-        HIP_TRY(hipMemsetAsync(tmp.counts + ntiles, 0, sizeof(uint64_t), d.stream));
-        hipLaunchKernelGGL(fz_rec_count_kernel, dim3(rec_grid(d, ntiles)), dim3(FZ_REC_THREADS), 0, d.stream, tmp.raw, ntiles, tmp.counts);
-        rec_scan(d, tmp.counts, ntiles + 1, tmp.scratch);
-    }
-    mark(2);
-    if (n) {
-        HIP_TRY(hipMemcpyAsync(&n_nl, tmp.counts + ntiles, sizeof(uint64_t), hipMemcpyDeviceToHost, d.stream));
-        HIP_TRY(hipStreamSynchronize(d.stream));
-        if (n_nl > n) return fail(FZ_EDEVICE, "records: the newline count is outside the text");
-    }
-    const uint64_t n_lines = fz_rec_n_lines(text, n, n_nl);
+    // 1. the line table (a text with newlines and no whole record gets it too, before it is refused or comes out empty)
+    uint64_t n_nl = 0, n_lines = 0;
+    if ((rc = in.line_table(text, n, &n_nl, &n_lines))) return rc;
     const uint64_t n_seqs = fz_rec_n_seqs(n_lines, lines_per_record, sequence_line);
     if (info) { info->n_lines = n_lines; info->n_seqs = n_seqs; }
     if (n_seqs >= (1ull << 32)) return fail(FZ_EUNSUPPORTED, "more than 2^32 - 1 sequences in a batch");
-    // 2. the line table; one lane per record; the scan of the lengths
+    // 2. one lane per record; the scan of the lengths
     uint64_t key = fz_rec_count_key(n_lines, lines_per_record, flags), total = 0, longest = 0;
-    mark(3);
     if (n_seqs) {
-        if ((rc = rec_malloc(&tmp.nl, n_nl))) return rc;
-        if ((rc = rec_malloc(&tmp.starts, n_seqs))) return rc;
-        if ((rc = rec_malloc(&tmp.at, n_seqs + 1))) return rc;
-        if ((rc = rec_malloc(&tmp.info, 2))) return rc;
-        if (rec_scan_scratch(n_seqs + 1) > rec_scan_scratch(ntiles + 1)) {
-            (void)hipFree(tmp.scratch);
-            tmp.scratch = nullptr;
-            if ((rc = rec_malloc(&tmp.scratch, rec_scan_scratch(n_seqs + 1)))) return rc;
-        }
-        HIP_TRY(hipMemsetAsync(tmp.info, 0xff, sizeof(uint64_t), d.stream));
-        HIP_TRY(hipMemsetAsync(tmp.info + 1, 0, sizeof(uint64_t), d.stream));
-        if (n_nl) hipLaunchKernelGGL(fz_rec_lines_kernel, dim3(rec_grid(d, ntiles)), dim3(FZ_REC_THREADS), 0, d.stream, tmp.raw, ntiles, tmp.counts, tmp.nl);
+        if ((rc = rec_malloc(&in.starts, n_seqs))) return rc;
+        if ((rc = rec_malloc(&in.at, n_seqs + 1))) return rc;
+        if ((rc = in.arm_verdict())) return rc;
         hipLaunchKernelGGL(fz_rec_measure_kernel, dim3(rec_grid(d, (n_seqs + FZ_REC_THREADS - 1) / FZ_REC_THREADS)), dim3(FZ_REC_THREADS), 0, d.stream,
-                           tmp.raw, n, tmp.nl, n_nl, n_lines, lines_per_record, sequence_line, flags, n_seqs, tmp.starts, tmp.at, tmp.info);
-        rec_scan(d, tmp.at, n_seqs + 1, tmp.scratch);
+                           in.raw, n, in.nl, n_nl, n_lines, lines_per_record, sequence_line, flags, n_seqs, in.starts, in.at, in.info);
+        if ((rc = in.scan(in.at, n_seqs + 1))) return rc;
     }
-    mark(4);
-    if (n_seqs) {
-        unsigned long long got[2] = {0, 0};
-        HIP_TRY(hipMemcpyAsync(got, tmp.info, sizeof(got), hipMemcpyDeviceToHost, d.stream));
-        HIP_TRY(hipMemcpyAsync(&total, tmp.at + n_seqs, sizeof(uint64_t), hipMemcpyDeviceToHost, d.stream));
-        HIP_TRY(hipStreamSynchronize(d.stream));
-        key = got[0];
-        longest = got[1];
-        if (total > n || longest > total) return fail(FZ_EDEVICE, "records: the packed length is outside the text");
-    }
-    if (key != FZ_REC_NO_ERROR) return rec_report(what, key, info);
+    in.mark();
+    if (n_seqs && (rc = in.read_verdict(n_seqs, &key, &total, &longest))) return rc;
+    if (key != FZ_REC_NO_ERROR) return rec_report((flags & FZ_REC_FASTQ_CHECKS) ? "fastq" : "lines", key, info);
     if (info) info->packed_bytes = total;
-    // 3. the handle of fz_batch_upload, its bytes gathered on the device
+    // 3. the handle, its bytes gathered on the device
     fz_seq *seq = nullptr;
-    double d2h_ms = 0;
-    rc = rec_make_handle(ctx, n_seqs, total, longest, tmp.at, tmp.starts, 5, &d2h_ms, &seq, [&](uint8_t *d_buf) {
+    rc = in.handle(n_seqs, total, longest, &seq, [&](uint8_t *d_buf) {
         hipLaunchKernelGGL(fz_rec_gather_kernel, dim3(rec_grid(d, (total + FZ_TILE_BYTES - 1) / FZ_TILE_BYTES)), dim3(FZ_REC_THREADS), 0, d.stream,
-                           tmp.raw, tmp.starts, tmp.at, n_seqs, total, d_buf);
+                           in.raw, in.starts, in.at, n_seqs, total, d_buf);
     });
     if (rc) return rc;
-    if (timed) {
-        ctx->rec_ms[0] = span_ms(d.rec_ev[0], d.rec_ev[1]);
-        ctx->rec_ms[1] = span_ms(d.rec_ev[1], d.rec_ev[2]) + span_ms(d.rec_ev[3], d.rec_ev[4]) + span_ms(d.rec_ev[5], d.rec_ev[6]);
-        ctx->rec_ms[2] = d2h_ms;
-    }
-    ctx->rec_ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
-    ctx->live.push_back(seq);
-    *out = seq;
-    return FZ_OK;
+    return in.finish(seq, out);
 }
 
 int fz_debug_records_ms(fz_ctx *ctx, double *ms4) {
@@ -2991,14 +3067,8 @@ int fz_debug_records_split(const uint8_t *text, uint64_t n, uint32_t lines_per_r
     int rc = rec_check_args(text, n, lines_per_record, sequence_line, flags);
     if (rc) return rc;
     if (flags & FZ_REC_FASTQ_CHECKS) n = rec_trim(text, n);
-    std::vector<uint64_t> nl;                             // the line table, by the kernels' byte mask word by word
-    uint64_t i = 0;
-    for (; i + 4 <= n; i += 4) {
-        uint32_t w;
-        memcpy(&w, text + i, 4);
-        for (uint32_t m = fz_rec_nl_mask(w); m; m &= m - 1u) nl.push_back(i + ((uint32_t)__builtin_ctz(m) >> 3));
-    }
-    for (; i < n; ++i) if (text[i] == '\n') nl.push_back(i);
+    std::vector<uint64_t> nl;
+    host_line_table(text, n, nl);
     const uint64_t n_nl = nl.size();
     const uint64_t n_lines = fz_rec_n_lines(text, n, n_nl);
     const uint64_t n_seqs = fz_rec_n_seqs(n_lines, lines_per_record, sequence_line);
@@ -3014,10 +3084,7 @@ int fz_debug_records_split(const uint8_t *text, uint64_t n, uint32_t lines_per_r
     if (key != FZ_REC_NO_ERROR) return rec_report((flags & FZ_REC_FASTQ_CHECKS) ? "fastq" : "lines", key, info);
     if (info) info->packed_bytes = total;
     void *ms = nullptr, *me = nullptr, *mp = nullptr;
-    rc = alloc_out(n_seqs, sizeof(uint64_t), &ms);
-    if (rc == FZ_OK) rc = alloc_out(n_seqs, sizeof(uint64_t), &me);
-    if (rc == FZ_OK) rc = alloc_out(total, 1, &mp);
-    if (rc) { release_out(ms); release_out(me); release_out(mp); return rc; }
+    if ((rc = alloc_split_out(n_seqs, sizeof(uint64_t), total, &ms, &me, &mp))) return rc;
     uint64_t at = 0;
     for (uint64_t r = 0; r < n_seqs; ++r) {
         static_cast<uint64_t *>(ms)[r] = recs[r].start;
@@ -3036,15 +3103,6 @@ int fz_debug_records_split(const uint8_t *text, uint64_t n, uint32_t lines_per_r
 namespace {
 static_assert(sizeof(FzFaRow) == sizeof(fz_fasta_row) && sizeof(fz_fasta_row) == 48, "fz_fasta_row is FzFaRow");
 
-const char *fa_reason_text(uint32_t reason) {
-    switch (reason) {
-    case FZ_FA_E_START: return "the text does not start with '>'";
-    case FZ_FA_E_EMPTY: return "an empty line inside the sequence";
-    case FZ_FA_E_WIDTH: return "the sequence lines are not of one length and width (all but the last, which may be shorter)";
-    }
-    return "malformed";
-}
-
 int fa_check_args(const uint8_t *text, uint64_t n, uint32_t flags) {
     if (!text && n) return fail(FZ_EINVAL, "null argument");
     if (flags & ~FZ_FA_UPPER) return fail(FZ_EINVAL, "unknown fasta flags");
@@ -3052,19 +3110,6 @@ int fa_check_args(const uint8_t *text, uint64_t n, uint32_t flags) {
     return FZ_OK;
 }
 
-int fa_report(uint64_t key, fz_records_info *info) {
-    if (info) { info->bad_record = fz_rec_err_record(key); info->bad_reason = fz_rec_err_reason(key); }
-    return fail(FZ_EINVAL, "fasta: record %llu: %s", (unsigned long long)fz_rec_err_record(key), fa_reason_text(fz_rec_err_reason(key)));
-}
-
-struct FaTmp {                                            // the call's transient device memory besides RecTmp's
-    uint64_t *rank = nullptr, *head = nullptr;
-    FzFaRow *rows = nullptr;
-    ~FaTmp() {
-        for (void *p : {(void *)rank, (void *)head, (void *)rows})
-            if (p) (void)hipFree(p);
-    }
-};
 }  // namespace
 
 int fz_batch_upload_fasta(fz_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t flags, fz_seq **out, fz_records_info *info) {
@@ -3072,67 +3117,24 @@ int fz_batch_upload_fasta(fz_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t
     *out = nullptr;
     if (info) *info = fz_records_info{};
     int rc = fa_check_args(text, n, flags);
+    if (rc == FZ_OK) rc = batch_upload_admit(ctx);
     if (rc) return rc;
-    if (ctx->devs.size() != 1 || ctx->snapshot || comm_multi_process(ctx))
-        return fail(FZ_EUNSUPPORTED, "batches are searched by single-device, non-collective contexts");
-    if (ctx->npend || ctx->stream_inflight) return fail(FZ_EINVAL, "a search of this context is in flight");
-    const auto t_call = std::chrono::steady_clock::now();
+    Ingest in(ctx, "fasta");
+    DevState &d = in.d;
     n = rec_trim(text, n);
-    DevState &d = ctx->devs[0];
-    HIP_TRY(hipSetDevice(d.device));
-    const bool timed = ctx->timing;
-    if (timed) for (auto &ev : d.rec_ev) if (!ev) HIP_TRY(hipEventCreate(&ev));
-    auto mark = [&](int i) { if (timed) (void)hipEventRecord(d.rec_ev[i], d.stream); };
-    RecTmp tmp;
-    FaTmp fa;
-    const uint64_t ntiles = (n + FZ_TILE_BYTES - 1) / FZ_TILE_BYTES;
-    uint64_t n_nl = 0, scratch_items = rec_scan_scratch(ntiles + 1);
-    auto scan = [&](uint64_t *data, uint64_t items) -> int {   // the exclusive scan, its scratch grown when this one needs more
-        if (rec_scan_scratch(items) > scratch_items) {
-            (void)hipFree(tmp.scratch);
-            tmp.scratch = nullptr;
-            scratch_items = rec_scan_scratch(items);
-            if (int r = rec_malloc(&tmp.scratch, scratch_items)) return r;
-        }
-        rec_scan(d, data, items, tmp.scratch);
-        return FZ_OK;
-    };
-    // 1. as fz_batch_upload_records: the text in whole tiles, the newlines per tile, their scan
-    mark(0);
-    if (n) {
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&tmp.raw), ntiles * FZ_TILE_BYTES));
-        if (ntiles * FZ_TILE_BYTES > n) HIP_TRY(hipMemsetAsync(tmp.raw + n, 0, ntiles * FZ_TILE_BYTES - n, d.stream));
-        HIP_TRY(hipMemcpyAsync(tmp.raw, text, n, hipMemcpyHostToDevice, d.stream));
-    }
-    mark(1);
-    if (n) {
-        if ((rc = rec_malloc(&tmp.counts, ntiles + 1))) return rc;
-        if ((rc = rec_malloc(&tmp.scratch, scratch_items))) return rc;
-        HIP_TRY(hipMemsetAsync(tmp.counts + ntiles, 0, sizeof(uint64_t), d.stream));
-        hipLaunchKernelGGL(fz_rec_count_kernel, dim3(rec_grid(d, ntiles)), dim3(FZ_REC_THREADS), 0, d.stream, tmp.raw, ntiles, tmp.counts);
-        rec_scan(d, tmp.counts, ntiles + 1, tmp.scratch);
-    }
-    mark(2);
-    if (n) {
-        HIP_TRY(hipMemcpyAsync(&n_nl, tmp.counts + ntiles, sizeof(uint64_t), hipMemcpyDeviceToHost, d.stream));
-        HIP_TRY(hipStreamSynchronize(d.stream));
-        if (n_nl > n) return fail(FZ_EDEVICE, "fasta: the newline count is outside the text");
-    }
-    const uint64_t n_lines = fz_rec_n_lines(text, n, n_nl);
-    // 2. the line table; one lane per line flags the headers; the scan of the flags ranks every line into its record
-    uint64_t n_seqs = 0;
-    mark(3);
+    // 1. the line table
+    uint64_t n_nl = 0, n_lines = 0, n_seqs = 0;
+    if ((rc = in.line_table(text, n, &n_nl, &n_lines))) return rc;
+    // 2. one lane per line flags the headers; the scan of the flags ranks every line into its record
     if (n_lines) {
-        if ((rc = rec_malloc(&tmp.nl, n_nl))) return rc;
-        if ((rc = rec_malloc(&fa.rank, n_lines + 1))) return rc;
-        if (n_nl) hipLaunchKernelGGL(fz_rec_lines_kernel, dim3(rec_grid(d, ntiles)), dim3(FZ_REC_THREADS), 0, d.stream, tmp.raw, ntiles, tmp.counts, tmp.nl);
-        hipLaunchKernelGGL(fz_fa_heads_kernel, dim3(rec_grid(d, n_lines / FZ_REC_THREADS + 1)), dim3(FZ_REC_THREADS), 0, d.stream, tmp.raw, tmp.nl,
-                           n_lines, fa.rank, (uint64_t *)nullptr);
-        if ((rc = scan(fa.rank, n_lines + 1))) return rc;
+        if ((rc = rec_malloc(&in.rank, n_lines + 1))) return rc;
+        hipLaunchKernelGGL(fz_fa_heads_kernel, dim3(rec_grid(d, n_lines / FZ_REC_THREADS + 1)), dim3(FZ_REC_THREADS), 0, d.stream, in.raw, in.nl,
+                           n_lines, in.rank, (uint64_t *)nullptr);
+        if ((rc = in.scan(in.rank, n_lines + 1))) return rc;
     }
-    mark(4);
+    in.mark();
     if (n_lines) {
-        HIP_TRY(hipMemcpyAsync(&n_seqs, fa.rank + n_lines, sizeof(uint64_t), hipMemcpyDeviceToHost, d.stream));
+        HIP_TRY(hipMemcpyAsync(&n_seqs, in.rank + n_lines, sizeof(uint64_t), hipMemcpyDeviceToHost, d.stream));
         HIP_TRY(hipStreamSynchronize(d.stream));
         if (n_seqs > n_lines) return fail(FZ_EDEVICE, "fasta: the header count is outside the text");
     }
@@ -3140,56 +3142,36 @@ int fz_batch_upload_fasta(fz_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t
     if (n_seqs >= (1ull << 32)) return fail(FZ_EUNSUPPORTED, "more than 2^32 - 1 sequences in a batch");
     // 3. every header's line; one lane per record; one lane per line; the scan of the lengths
     uint64_t key = fz_fa_text_key(text, n), total = 0, longest = 0;
-    mark(5);
+    in.mark();
     if (n_seqs) {
-        if ((rc = rec_malloc(&fa.head, n_seqs + 1))) return rc;
-        if ((rc = rec_malloc(&fa.rows, n_seqs))) return rc;
-        if ((rc = rec_malloc(&tmp.starts, n_seqs))) return rc;
-        if ((rc = rec_malloc(&tmp.at, n_seqs + 1))) return rc;
-        if ((rc = rec_malloc(&tmp.info, 2))) return rc;
-        HIP_TRY(hipMemsetAsync(tmp.info, 0xff, sizeof(uint64_t), d.stream));
-        HIP_TRY(hipMemsetAsync(tmp.info + 1, 0, sizeof(uint64_t), d.stream));
-        hipLaunchKernelGGL(fz_fa_heads_kernel, dim3(rec_grid(d, n_lines / FZ_REC_THREADS + 1)), dim3(FZ_REC_THREADS), 0, d.stream, tmp.raw, tmp.nl,
-                           n_lines, fa.rank, fa.head);
+        if ((rc = rec_malloc(&in.head, n_seqs + 1))) return rc;
+        if ((rc = rec_malloc(&in.rows, n_seqs))) return rc;
+        if ((rc = rec_malloc(&in.starts, n_seqs))) return rc;
+        if ((rc = rec_malloc(&in.at, n_seqs + 1))) return rc;
+        if ((rc = in.arm_verdict())) return rc;
+        hipLaunchKernelGGL(fz_fa_heads_kernel, dim3(rec_grid(d, n_lines / FZ_REC_THREADS + 1)), dim3(FZ_REC_THREADS), 0, d.stream, in.raw, in.nl,
+                           n_lines, in.rank, in.head);
         hipLaunchKernelGGL(fz_fa_measure_kernel, dim3(rec_grid(d, (n_seqs + FZ_REC_THREADS - 1) / FZ_REC_THREADS)), dim3(FZ_REC_THREADS), 0, d.stream,
-                           tmp.raw, n, tmp.nl, n_nl, fa.head, n_seqs, fa.rows, tmp.starts, tmp.at, tmp.info);
+                           in.raw, n, in.nl, n_nl, in.head, n_seqs, in.rows, in.starts, in.at, in.info);
         hipLaunchKernelGGL(fz_fa_check_kernel, dim3(rec_grid(d, (n_lines + FZ_REC_THREADS - 1) / FZ_REC_THREADS)), dim3(FZ_REC_THREADS), 0, d.stream,
-                           tmp.raw, n, tmp.nl, n_nl, n_lines, fa.rank, fa.head, fa.rows, tmp.info);
-        if ((rc = scan(tmp.at, n_seqs + 1))) return rc;
+                           in.raw, n, in.nl, n_nl, n_lines, in.rank, in.head, in.rows, in.info);
+        if ((rc = in.scan(in.at, n_seqs + 1))) return rc;
     }
-    mark(6);
-    if (n_seqs) {
-        unsigned long long got[2] = {0, 0};
-        HIP_TRY(hipMemcpyAsync(got, tmp.info, sizeof(got), hipMemcpyDeviceToHost, d.stream));
-        HIP_TRY(hipMemcpyAsync(&total, tmp.at + n_seqs, sizeof(uint64_t), hipMemcpyDeviceToHost, d.stream));
-        HIP_TRY(hipStreamSynchronize(d.stream));
-        key = std::min<uint64_t>(key, got[0]);
-        longest = got[1];
-        if (key == FZ_REC_NO_ERROR && (total > n || longest > total)) return fail(FZ_EDEVICE, "fasta: the packed length is outside the text");
-    }
-    if (key != FZ_REC_NO_ERROR) return fa_report(key, info);
+    in.mark();
+    if (n_seqs && (rc = in.read_verdict(n_seqs, &key, &total, &longest))) return rc;
+    if (key != FZ_REC_NO_ERROR) return rec_report("fasta", key, info);
     if (info) info->packed_bytes = total;
-    // 4. the handle of fz_batch_upload, its bases gathered on the device; the index rows stay with it
+    // 4. the handle, its bases gathered on the device; the index rows stay with it
     fz_seq *seq = nullptr;
-    double d2h_ms = 0;
-    rc = rec_make_handle(ctx, n_seqs, total, longest, tmp.at, tmp.starts, 7, &d2h_ms, &seq, [&](uint8_t *d_buf) {
+    rc = in.handle(n_seqs, total, longest, &seq, [&](uint8_t *d_buf) {
         hipLaunchKernelGGL(fz_fa_gather_kernel, dim3(rec_grid(d, (total + FZ_TILE_BYTES - 1) / FZ_TILE_BYTES)), dim3(FZ_REC_THREADS), 0, d.stream,
-                           tmp.raw, fa.rows, tmp.at, n_seqs, total, flags, d_buf);
+                           in.raw, in.rows, in.at, n_seqs, total, flags, d_buf);
     });
     if (rc) return rc;
-    seq->d_fa_rows = fa.rows;
-    fa.rows = nullptr;
+    seq->d_fa_rows = in.rows;
+    in.rows = nullptr;
     seq->is_fasta = true;
-    if (timed) {
-        ctx->rec_ms[0] = span_ms(d.rec_ev[0], d.rec_ev[1]);
-        ctx->rec_ms[1] = span_ms(d.rec_ev[1], d.rec_ev[2]) + span_ms(d.rec_ev[3], d.rec_ev[4]) + span_ms(d.rec_ev[5], d.rec_ev[6]) +
-                         span_ms(d.rec_ev[7], d.rec_ev[8]);
-        ctx->rec_ms[2] = d2h_ms;
-    }
-    ctx->rec_ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
-    ctx->live.push_back(seq);
-    *out = seq;
-    return FZ_OK;
+    return in.finish(seq, out);
 }
 
 int fz_batch_fasta_index(const fz_seq *batch, fz_fasta_row *rows) {
@@ -3210,7 +3192,7 @@ int fz_debug_fasta_split(const uint8_t *text, uint64_t n, uint32_t flags, fz_fas
     if (rc) return rc;
     n = rec_trim(text, n);
     std::vector<uint64_t> nl;
-    for (uint64_t i = 0; i < n; ++i) if (text[i] == '\n') nl.push_back(i);
+    host_line_table(text, n, nl);
     const uint64_t n_nl = nl.size();
     const uint64_t n_lines = fz_rec_n_lines(text, n, n_nl);
     std::vector<uint64_t> rank(n_lines + 1), head;       // the kernels' tables: the scanned flags, every header's line
@@ -3237,13 +3219,10 @@ int fz_debug_fasta_split(const uint8_t *text, uint64_t n, uint32_t flags, fz_fas
         const uint32_t why = fz_fa_line_check(text, n, nl.data(), n_nl, i, i + 1 == head[c], recs[c - 1].linebases, recs[c - 1].linewidth);
         if (why != FZ_REC_OK) key = std::min(key, fz_rec_err_key(c - 1, why));
     }
-    if (key != FZ_REC_NO_ERROR) return fa_report(key, info);
+    if (key != FZ_REC_NO_ERROR) return rec_report("fasta", key, info);
     if (info) info->packed_bytes = total;
     void *mr = nullptr, *me = nullptr, *mp = nullptr;
-    rc = alloc_out(n_seqs, sizeof(fz_fasta_row), &mr);
-    if (rc == FZ_OK) rc = alloc_out(n_seqs, sizeof(uint64_t), &me);
-    if (rc == FZ_OK) rc = alloc_out((total + 3) / 4 * 4, 1, &mp);
-    if (rc) { release_out(mr); release_out(me); release_out(mp); return rc; }
+    if ((rc = alloc_split_out(n_seqs, sizeof(fz_fasta_row), (total + 3) / 4 * 4, &mr, &me, &mp))) return rc;
     uint8_t *dst = static_cast<uint8_t *>(mp);
     uint64_t at = 0;
     for (uint64_t r = 0; r < n_seqs; ++r) {
@@ -3709,12 +3688,6 @@ struct BatchScope {
     ~BatchScope() { c->batch_call = false; }
 };
 
-static int batch_single_device(fz_ctx *ctx, fz_seq *batch) {
-    if (ctx->devs.size() != 1 || ctx->snapshot || comm_multi_process(ctx) || (batch && batch->is_batch && batch->shards.size() != 1))
-        return fail(FZ_EUNSUPPORTED, "batches are searched by single-device, non-collective contexts");
-    return FZ_OK;
-}
-
 // What every list-of-patterns call checks before anything is searched: the handles, the state of the context, the lists,
 // and every pattern through the single call's checks (lev_plan / subs_plan).  batch_call: the name of a call that takes a
 // batch handle (fz_batch_search_multi, fz_batch_assign), null for the calls of a whole sequence (fz_*_ngrams_multi*).
@@ -3838,7 +3811,7 @@ static int multi_impl(fz_ctx *ctx, fz_seq *seq, uint32_t mode, const uint8_t *pa
         rows[i].assign(one, one + n_one);
         release_out(one);
         tot.rows += n_one;
-        return (int)FZ_OK;
+        return FZ_OK;
     });
     if (rc) return rc;
     for (const MpGroup &g : groups) {

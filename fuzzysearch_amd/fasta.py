@@ -24,13 +24,10 @@ import numpy as np
 
 from . import _native
 from .batch import BatchSequences, _single_device
-from .records import RecordSequences, _open_source
+from .records import RecordSequences, _line_spans, _open_source, _refuse
 
 __all__ = ['resident_fasta', 'FastaBatch', 'split_fasta']
 
-_REASONS = {5: "the text does not start with '>'",
-            6: 'an empty line inside the sequence',
-            7: 'the sequence lines are not of one length and width (all but the last, which may be shorter)'}
 _LOOP_LINES = 64                                    # slices of at most this many lines are cut line by line
 
 
@@ -195,15 +192,7 @@ def resident_fasta(source, upper=False, engine=None):
 def split_fasta(source, upper=False):
     """The split on the host, in plain Python (engines the batched call does not serve) -> (rows, the contigs as a list)."""
     data = bytes(source)
-    lines = data.split(b'\n')
-    if lines[-1] == b'':
-        lines.pop()
-    spans, pos = [], 0                              # (start, content length, width)
-    for ln in lines:
-        spans.append((pos, len(ln) - (1 if ln.endswith(b'\r') else 0), min(len(ln) + 1, len(data) - pos)))
-        pos += len(ln) + 1
-    while spans and spans[-1][1] == 0:
-        spans.pop()
+    spans = _line_spans(data)                       # (start, content length, width)
     bad, records = [], []
     if spans and data[:1] != b'>':
         bad.append((0, 5))
@@ -227,7 +216,5 @@ def split_fasta(source, upper=False):
         contig = b''.join(data[s:s + n] for s, n, _w in body)
         rows[r]['length'] = len(contig)
         contigs.append(contig.upper() if upper else contig)
-    if bad:
-        r, why = min(bad)
-        raise ValueError('fasta: record %d: %s' % (r, _REASONS[why]))
+    _refuse('fasta', bad)
     return rows, contigs

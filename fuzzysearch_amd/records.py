@@ -25,10 +25,14 @@ from .batch import BatchSequences, _single_device
 
 __all__ = ['resident_records', 'RecordBatch', 'split_records']
 
+# why a record is refused: the reasons of fz_batch_upload_records (1-4) and fz_batch_upload_fasta (5-7), in the library's words
 _REASONS = {1: 'the number of lines is not a multiple of 4 (truncated record)',
             2: "the header line does not start with '@'",
             3: "the separator line does not start with '+'",
-            4: 'the quality line is not as long as the sequence line'}
+            4: 'the quality line is not as long as the sequence line',
+            5: "the text does not start with '>'",
+            6: 'an empty line inside the sequence',
+            7: 'the sequence lines are not of one length and width (all but the last, which may be shorter)'}
 
 
 class RecordSequences(object):
@@ -104,20 +108,34 @@ def _open_source(source):
     return source
 
 
-def split_records(source, format):
-    """The split on the host, in plain Python (engines the batched call does not serve) -> (starts, lengths)."""
-    period, phase, flags = _native.RECORD_FORMATS[format]
-    data = bytes(source)
+def _line_spans(data, trim=True):
+    """The lines of ``data`` (bytes) as a list of (start, content length, width): the content leaves out one ``\\r`` in front
+    of the line's end, the width reaches to the next line's first byte.  ``trim``: trailing empty lines are no lines."""
     lines = data.split(b'\n')
     if lines[-1] == b'':
         lines.pop()
     spans, pos = [], 0
     for ln in lines:
-        spans.append((pos, len(ln) - (1 if ln.endswith(b'\r') else 0)))
+        spans.append((pos, len(ln) - (1 if ln.endswith(b'\r') else 0), min(len(ln) + 1, len(data) - pos)))
         pos += len(ln) + 1
+    while trim and spans and spans[-1][1] == 0:
+        spans.pop()
+    return spans
+
+
+def _refuse(format, bad):
+    """``bad``: (record, reason) pairs; the smallest one is the one reported, in the library's words."""
+    if bad:
+        r, why = min(bad)
+        raise ValueError('%s: record %d: %s' % (format, r, _REASONS[why]))
+
+
+def split_records(source, format):
+    """The split on the host, in plain Python (engines the batched call does not serve) -> (starts, lengths)."""
+    period, phase, flags = _native.RECORD_FORMATS[format]
+    data = bytes(source)
+    spans = [(s, n) for s, n, _w in _line_spans(data, trim=bool(flags & _native.REC_FASTQ_CHECKS))]
     if flags & _native.REC_FASTQ_CHECKS:
-        while spans and spans[-1][1] == 0:
-            spans.pop()
         bad = []
         if len(spans) % 4:
             bad.append((len(spans) // 4, 1))
@@ -131,9 +149,7 @@ def split_records(source, format):
                 bad.append((r, 4))
             if bad and bad[-1][0] == r:
                 break
-        if bad:
-            r, why = min(bad)
-            raise ValueError('%s: record %d: %s' % (format, r, _REASONS[why]))
+        _refuse(format, bad)
     kept = spans[phase::period]
     starts = np.fromiter((s for s, _ in kept), dtype=np.uint64, count=len(kept))
     lengths = np.fromiter((n for _, n in kept), dtype=np.uint64, count=len(kept))

@@ -199,3 +199,37 @@ def test_record_sequences_view_is_lazy_and_indexable():
     with pytest.raises(IndexError):
         view[4]
     assert not records.RecordSequences(b'', np.zeros(0, np.uint64), np.zeros(0, np.uint64))
+
+
+# one minimal malformed text per reason of the library's table: FASTQ 1-4, FASTA 5-7
+MINIMAL = [(1, 'fastq', b'@h\nAC\n'), (2, 'fastq', b'h\nAC\n+\nII\n'), (3, 'fastq', b'@h\nAC\n-\nII\n'), (4, 'fastq', b'@h\nAC\n+\nI\n'),
+           (5, 'fasta', b'AC\n'), (6, 'fasta', b'>a\nAC\n\nAC\n'), (7, 'fasta', b'>a\nAC\nA\nAC\n')]
+
+
+@pytest.mark.parametrize("reason,fmt,text", MINIMAL)
+def test_the_python_splitters_refuse_in_the_library_s_words(reason, fmt, text):
+    """records._REASONS restates the library's table: the host twin's message and the plain-Python splitter's are one text."""
+    from fuzzysearch_amd import fasta
+    with pytest.raises(ValueError) as native:
+        _native.fasta_split(text) if fmt == 'fasta' else _native.records_split(text, *FORMATS[fmt])
+    with pytest.raises(ValueError) as plain:
+        fasta.split_fasta(text) if fmt == 'fasta' else records.split_records(text, fmt)
+    assert (native.value.info['bad_record'], native.value.info['bad_reason']) == (0, reason)
+    assert str(plain.value) == str(native.value) == '%s: record 0: %s' % (fmt, records._REASONS[reason])
+    assert sorted(records._REASONS) == [r for r, _f, _t in MINIMAL] and not hasattr(fasta, '_REASONS')
+
+
+@pytest.mark.parametrize("text", [b'a\nbc\n', b'a\r\nbc\r\n', b'a\nbc', b'a\r\nbc\r', b'a\n\nbc\n\n\r\n\n', b'\n', b''])
+def test_line_spans_against_bytes_split(text):
+    lines = text.split(b'\n')
+    if lines[-1] == b'':                             # the text ended with a terminator (or is empty): no line behind it
+        lines.pop()
+    spans = records._line_spans(text, trim=False)
+    assert len(spans) == len(lines)
+    assert [text[s:s + n] for s, n, _w in spans] == [ln[:-1] if ln.endswith(b'\r') else ln for ln in lines]
+    assert b''.join(text[s:s + w] for s, _n, w in spans) == text
+    assert [s for s, _n, _w in spans] == [sum(len(ln) + 1 for ln in lines[:i]) for i in range(len(lines))]
+    kept = len(lines)
+    while kept and lines[kept - 1] in (b'', b'\r'):
+        kept -= 1
+    assert records._line_spans(text) == spans[:kept]
