@@ -13,7 +13,8 @@ many patterns can be searched without re-crossing PCIe; ``find_near_matches_mult
 sequence and ``find_near_matches_batch`` one subsequence in many sequences (``resident_batch`` keeps them in HBM), each
 in one pass; ``find_near_matches_multi_batch`` searches many subsequences in many sequences, a pass per group of up to 64;
 ``resident_records`` makes such a batch from a FASTQ file or a file of lines and ``resident_fasta`` from the contigs of a
-FASTA file, split on the device.  The multi-pattern
+FASTA file, split on the device; ``derive_batch`` (``batch.derive(...)``) makes a batch of cuts of a resident batch — selected,
+trimmed, reversed, complemented — without leaving the device.  The multi-pattern
 calls take ``classes=IUPAC_DNA`` (or any mapping of pattern byte -> accepted sequence bytes) for degenerate patterns.
 """
 import io
@@ -33,6 +34,7 @@ from .assign import find_best_matches_batch, BestMatches
 from .records import resident_records, RecordBatch
 from .fasta import resident_fasta, FastaBatch
 from .classes import IUPAC_DNA
+from .derive import derive_batch, DerivedBatch, DNA_COMPLEMENT
 
 __version__ = '0.1.0'
 
@@ -52,6 +54,9 @@ __all__ = [
     'RecordBatch',
     'resident_fasta',
     'FastaBatch',
+    'derive_batch',
+    'DerivedBatch',
+    'DNA_COMPLEMENT',
     'cache_info',
     'cache_clear',
     'UnsupportedSearch',

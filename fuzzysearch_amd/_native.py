@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = (
     "fz_batch_upload_fasta", "fz_batch_fasta_index", "fz_debug_fasta_split", "fz_debug_fasta_upper4", "fz_debug_fasta_src",
     "fz_subs_ngrams_multi_cls", "fz_subs_ngrams_multi_best_cls", "fz_batch_search_multi_cls", "fz_batch_assign_cls",
     "fz_debug_multi_plan_cls",
+    "fz_batch_derive", "fz_debug_derive_plan", "fz_debug_derive_ms",
 )
 
 
@@ -48,6 +49,11 @@ class FzMatch(ctypes.Structure):
 class FzRecordsInfo(ctypes.Structure):
     _fields_ = [("n_lines", ctypes.c_uint64), ("n_seqs", ctypes.c_uint64), ("packed_bytes", ctypes.c_uint64),
                 ("bad_record", ctypes.c_uint64), ("bad_reason", ctypes.c_uint32)]
+
+
+class FzDeriveInfo(ctypes.Structure):
+    _fields_ = [("n_out", ctypes.c_uint64), ("packed_bytes", ctypes.c_uint64), ("longest", ctypes.c_uint64),
+                ("bad_item", ctypes.c_uint64), ("bad_reason", ctypes.c_uint32)]
 
 
 class FzStats(ctypes.Structure):
@@ -207,6 +213,14 @@ def load_library():
             L.fz_debug_scan_items.argtypes = []
             L.fz_debug_records_ms.restype = ci
             L.fz_debug_records_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
+        if hasattr(L, "fz_batch_derive"):
+            dip = ctypes.POINTER(FzDeriveInfo)
+            L.fz_batch_derive.restype = ci
+            L.fz_batch_derive.argtypes = [vp, vp, vp, vp, vp, u64, u32, vp, ctypes.POINTER(vp), dip]
+            L.fz_debug_derive_plan.restype = ci
+            L.fz_debug_derive_plan.argtypes = [vp, u64, vp, vp, vp, u64, vp, vp, dip]
+            L.fz_debug_derive_ms.restype = ci
+            L.fz_debug_derive_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
         if hasattr(L, "fz_batch_upload_fasta"):             # (absent from builds of earlier rounds named by FUZZYSEARCH_HIP_LIB for an A/B)
             rip = ctypes.POINTER(FzRecordsInfo)
             L.fz_batch_upload_fasta.restype = ci
@@ -586,6 +600,54 @@ def _raise_records(rc, info):
         raise
 
 
+DERIVE_REVERSE = 1                                # FZ_DERIVE_REVERSE
+
+
+def _derive_info(info):
+    return {'n_out': int(info.n_out), 'packed_bytes': int(info.packed_bytes), 'longest': int(info.longest),
+            'bad_item': int(info.bad_item), 'bad_reason': int(info.bad_reason)}
+
+
+def _raise_derive(rc, info):
+    """A bad item raises as Python's own indexing would: reason 1 (no such sequence) IndexError, 2 and 3 ValueError; the
+    info dict rides on the exception as ``.info``."""
+    try:
+        _raise(rc)
+    except ValueError as e:
+        if info['bad_reason'] == 1:
+            e = IndexError(str(e))
+        e.info = info
+        raise e
+
+
+def _derive_tables(index, starts, ends, n_out):
+    """The three optional tables as contiguous arrays of the C-ABI's types -> (arrays, their addresses or None)."""
+    import numpy as np
+    arrs = [None if t is None else np.ascontiguousarray(t, dtype=dt) for t, dt in ((index, np.uint32), (starts, np.uint64), (ends, np.uint64))]
+    for a in arrs:
+        if a is not None and a.shape != (n_out,):
+            raise ValueError('a table of %d entries for %d outputs' % (a.size, n_out))
+    return arrs, [None if a is None else a.ctypes.data for a in arrs]
+
+
+def derive_plan(offs, index, starts, ends, n_out):
+    """fz_debug_derive_plan (no device): the measure step and the scan of fz_batch_derive on the host, through the function
+    its kernel runs.  offs: the parent's len + 1 offsets -> (src, at, info dict); a bad item raises as derive does."""
+    import numpy as np
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    keep, addrs = _derive_tables(index, starts, ends, n_out)
+    src = np.zeros(n_out, dtype=np.uint64)
+    at = np.zeros(n_out + 1, dtype=np.uint64)
+    info = FzDeriveInfo()
+    rc = load_library().fz_debug_derive_plan(offs.ctypes.data, len(offs) - 1, addrs[0], addrs[1], addrs[2], n_out, src.ctypes.data,
+                                             at.ctypes.data, ctypes.byref(info))
+    del keep
+    d = _derive_info(info)
+    if rc != FZ_OK:
+        _raise_derive(rc, d)
+    return src, at, d
+
+
 def assign_dtype():
     """The numpy dtype of an fz_assign row (include/fzhip.h): pattern (-1: nothing matched), dist, tied, start, end."""
     global _ASSIGN_DTYPE
@@ -854,6 +916,42 @@ class Engine(object):
         with self._lock:
             _check(self._lib.fz_debug_batch_bytes(batch._h, buf, batch.nbytes))
         return buf.raw[:batch.nbytes]
+
+    def derive_batch(self, batch, index=None, starts=None, ends=None, n_out=None, reverse=False, translate=None):
+        """fz_batch_derive: out[j] = X(batch[index[j]][starts[j]:ends[j]]) made on the device from a batch handle of this
+        engine -> a ResidentSequence like upload_records', with `.n_seqs` and `.info` (n_out, packed_bytes, longest).
+        index: uint32, starts / ends: uint64 arrays of n_out entries, or None for the defaults; translate: 256 bytes or None.
+        A bad item raises IndexError (no such sequence) or ValueError naming it (`.info`: bad_item, bad_reason)."""
+        if getattr(batch, '_h', None) is None or getattr(batch, 'n_seqs', None) is None:
+            raise ValueError('derive_batch takes a batch handle that has not been released')
+        if n_out is None:
+            n_out = batch.n_seqs if index is None else len(index)
+        keep, addrs = _derive_tables(index, starts, ends, n_out)
+        taddr = None
+        if translate is not None:
+            taddr, tn, tkeep = _buffer_address(translate)
+            if tn != 256:
+                raise ValueError('translate is a table of 256 bytes')
+        h = ctypes.c_void_p()
+        info = FzDeriveInfo()
+        with self._lock:
+            rc = self._lib.fz_batch_derive(self._h, batch._h, addrs[0], addrs[1], addrs[2], n_out, DERIVE_REVERSE if reverse else 0,
+                                           taddr, ctypes.byref(h), ctypes.byref(info))
+        del keep
+        d = _derive_info(info)
+        if rc != FZ_OK:
+            _raise_derive(rc, d)
+        seq = ResidentSequence(self, h, d['packed_bytes'])
+        seq.n_seqs = d['n_out']
+        seq.info = d
+        return seq
+
+    def derive_ms(self):
+        """fz_debug_derive_ms: {tables_h2d, measure_scan, gather, ends_d2h, call} milliseconds of this engine's last derive_batch."""
+        ms = (ctypes.c_double * 5)()
+        with self._lock:
+            _check(self._lib.fz_debug_derive_ms(self._h, ms))
+        return {'tables_h2d': ms[0], 'measure_scan': ms[1], 'gather': ms[2], 'ends_d2h': ms[3], 'call': ms[4]}
 
     def records_ms(self):
         """fz_debug_records_ms: {h2d, kernels, ends_d2h, call} milliseconds of this engine's last upload_records / upload_fasta."""

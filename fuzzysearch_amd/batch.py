@@ -93,6 +93,8 @@ class BatchSequences(object):
     search over them is the per-sequence loop.  ``len()``, indexing and ``matched`` come from the original objects, which
     are kept alive."""
 
+    released = False                                # release() has been called: nothing can be derived from it any more
+
     def __init__(self, sequences, engine=None):
         self.sequences = list(sequences)
         self.engine = engine or _native.default_engine()
@@ -109,10 +111,16 @@ class BatchSequences(object):
         return self.sequences[item]
 
     def release(self):
+        self.released = True
         if self.handle is not None:
             self.handle.release()
             self.handle = None
             self.kind = None
+
+    def derive(self, index=None, starts=None, ends=None, reverse=False, translate=None):
+        """derive_batch(self, ...): a batch of cuts of these sequences, made on the device (derive.py)."""
+        from .derive import derive_batch
+        return derive_batch(self, index, starts, ends, reverse, translate)
 
 
 def resident_batch(sequences, engine=None):

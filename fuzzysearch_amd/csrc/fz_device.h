@@ -1688,3 +1688,51 @@ FZ_HD uint32_t fz_fa_upper4(uint32_t w) {
     const uint32_t ge_a = x + 0x1f1f1f1fu, gt_z = x + 0x05050505u;
     return w ^ ((ge_a & ~gt_z & ~w & 0x80808080u) >> 2);
 }
+
+// ---------------------------------------------------------------------------------------------
+// Derived batches (fz_batch_derive; fz_kernels.h: fz_derive_*_kernel): a batch is made from a batch where it lies.
+//     out[j] = X(parent[i_j][a_j : b_j]),  i_j = index[j] (null: j),  a_j = starts[j] (null: 0),  b_j = ends[j] (null: the
+//     length of parent sequence i_j),  X = byte by byte through a 256-byte table (null: identity), then reversed (REV).
+// offs = the parent's scanned length table (n_src + 1 entries, the first 0; not read when n_src == 0).  An item is bad when
+// i_j >= n_src (1), a_j > b_j (2) or b_j > the parent sequence's length (3); the smallest error key (j << 8 | reason,
+// fz_rec_err_key) is the one reported.  A bad item has no bytes.
+#define FZ_DRV_REVERSE 1u              // = FZ_DERIVE_REVERSE (include/fzhip.h)
+#define FZ_DRV_E_INDEX 1u
+#define FZ_DRV_E_ORDER 2u
+#define FZ_DRV_E_END 3u
+
+// item -> (src: its lowest byte in the parent's packed bytes, len, verdict)
+struct FzDrvItem { uint64_t src, len; uint32_t reason; };
+FZ_HD FzDrvItem fz_derive_item(const uint64_t *offs, uint64_t n_src, const uint32_t *index, const uint64_t *starts, const uint64_t *ends,
+                               uint64_t j) {
+    FzDrvItem o;
+    o.src = 0; o.len = 0; o.reason = FZ_REC_OK;
+    const uint64_t i = index ? index[j] : j;
+    if (i >= n_src) { o.reason = FZ_DRV_E_INDEX; return o; }
+    const uint64_t lo = offs[i], n = offs[i + 1u] - lo;
+    const uint64_t a = starts ? starts[j] : 0u, b = ends ? ends[j] : n;
+    if (a > b) { o.reason = FZ_DRV_E_ORDER; return o; }
+    if (b > n) { o.reason = FZ_DRV_E_END; return o; }
+    o.src = lo + a; o.len = b - a;
+    return o;
+}
+
+// The gather's address rule.  Output bytes [o, o + cnt) of an item (src, len), o + cnt <= len, are the cnt source bytes that
+// start at fz_derive_piece_lo: in ascending order, or (rev) in descending order: output byte o + q is source byte
+// lo + cnt - 1 - q.  Every one of them lies in [src, src + len).  fz_derive_byte_src: the source of output byte o alone.
+FZ_HD uint64_t fz_derive_piece_lo(uint64_t src, uint64_t len, uint64_t o, uint32_t cnt, bool rev) {
+    return rev ? src + len - o - cnt : src + o;
+}
+FZ_HD uint64_t fz_derive_byte_src(uint64_t src, uint64_t len, uint64_t o, bool rev) { return rev ? src + len - 1u - o : src + o; }
+
+// Sixteen bytes in four little-endian dwords, their order reversed: the bytes swapped inside every dword, the dwords swapped.
+FZ_HD void fz_derive_rev16(uint32_t &x, uint32_t &y, uint32_t &z, uint32_t &w) {
+    const uint32_t a = __builtin_bswap32(w), b = __builtin_bswap32(z), c = __builtin_bswap32(y), d = __builtin_bswap32(x);
+    x = a; y = b; z = c; w = d;
+}
+
+// Four bytes through the table.
+FZ_HD uint32_t fz_derive_xlat4(const uint8_t *table, uint32_t v) {
+    return (uint32_t)table[v & 0xffu] | ((uint32_t)table[(v >> 8) & 0xffu] << 8) | ((uint32_t)table[(v >> 16) & 0xffu] << 16) |
+           ((uint32_t)table[v >> 24] << 24);
+}

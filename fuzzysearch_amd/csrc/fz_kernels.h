@@ -2699,3 +2699,97 @@ __global__ __launch_bounds__(FZ_REC_THREADS) void fz_fa_gather_kernel(const uint
         __syncthreads();
     }
 }
+
+// ---------------------------------------------------------------------------------------------
+// Derived batches (fz_batch_derive; fz_device.h: fz_derive_*): a batch made from a batch, without leaving the device.
+//   fz_derive_measure_kernel   one lane per output: its source sequence from index[], the cut from starts[] / ends[] (null:
+//                              the defaults), checked against the parent's scanned length table; src[] and the lengths for
+//                              the records path's scan, the longest length, the smallest bad (item, reason)
+//   fz_derive_gather_kernel    packed[] by 16-byte pieces of the DESTINATION, as fz_rec_gather_kernel (which IS the instance
+//                              that neither reverses nor translates, launched over the parent's packed bytes)
+// info as fz_rec_measure_kernel's.  offs = the parent's d_ends_base (not read when n_src == 0).
+__global__ __launch_bounds__(FZ_REC_THREADS) void fz_derive_measure_kernel(const uint64_t *__restrict__ offs, uint64_t n_src,
+                                                                           const uint32_t *__restrict__ index,
+                                                                           const uint64_t *__restrict__ starts,
+                                                                           const uint64_t *__restrict__ ends, uint64_t n_out,
+                                                                           uint64_t *__restrict__ src, uint64_t *__restrict__ lens,
+                                                                           unsigned long long *__restrict__ info) {
+    const uint64_t stride = (uint64_t)gridDim.x * FZ_REC_THREADS;
+    unsigned long long longest = 0;
+    for (uint64_t j = (uint64_t)blockIdx.x * FZ_REC_THREADS + threadIdx.x; j < n_out; j += stride) {
+        const FzDrvItem o = fz_derive_item(offs, n_src, index, starts, ends, j);
+        src[j] = o.src;
+        lens[j] = o.len;
+        longest = o.len > longest ? o.len : longest;
+        if (o.reason != FZ_REC_OK) (void)atomicMin(&info[0], (unsigned long long)fz_rec_err_key(j, o.reason));
+    }
+#pragma unroll
+    for (uint32_t d = 32; d; d >>= 1) {
+        const unsigned long long o = __shfl_xor(longest, d, 64);
+        longest = o > longest ? o : longest;
+    }
+    if ((threadIdx.x & 63u) == 0 && longest > __hip_atomic_load(&info[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+        (void)atomicMax(&info[1], longest);
+    if (blockIdx.x == 0 && threadIdx.x == 0) lens[n_out] = 0;
+}
+
+// at[j] = where output j starts in packed[] (n_seqs + 1 entries, at[n_seqs] = total > 0), src[j] = its lowest byte in raw,
+// the parent's packed bytes.  A piece inside one output is one unaligned 16-byte load and one aligned 16-byte store: REV
+// takes the 16 bytes that END where the piece's first byte comes from (fz_derive_piece_lo) and turns them round in registers
+// (fz_derive_rev16); XLAT sends every byte through the table, which the workgroup holds in LDS as 64 dwords.  With 32 banks
+// table bytes c and c ^ 0x80 share a bank, so two lanes that read such a pair may cost a second LDS cycle; lanes that read
+// the same dword are one broadcast.  (Not measured with counters.)  A piece across an output's end goes byte by byte
+// (fz_derive_byte_src).
+// The over-read guard is the address rule's: every load covers exactly the source bytes of the piece's own output bytes,
+// which lie inside [src[j], src[j] + len) — parent sequences lie back to back, and a neighbour's bytes are never loaded.
+template <bool REV, bool XLAT>
+__global__ __launch_bounds__(FZ_REC_THREADS) void fz_derive_gather_kernel(const uint8_t *__restrict__ raw, const uint64_t *__restrict__ src,
+                                                                          const uint64_t *__restrict__ at, uint64_t n_seqs, uint64_t total,
+                                                                          const uint32_t *__restrict__ table, uint8_t *__restrict__ packed) {
+    __shared__ uint64_t bound[2];
+    __shared__ uint32_t xl[64];
+    const uint8_t *xb = reinterpret_cast<const uint8_t *>(xl);
+    const uint64_t *ends = at + 1;
+    const uint64_t ntiles = (total + FZ_TILE_BYTES - 1u) / FZ_TILE_BYTES;
+    if (XLAT && threadIdx.x < 64u) xl[threadIdx.x] = table[threadIdx.x];   // (the first tile's barrier orders it)
+    for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const uint64_t p0 = t * (uint64_t)FZ_TILE_BYTES;
+        const uint64_t p1 = p0 + FZ_TILE_BYTES < total ? p0 + FZ_TILE_BYTES : total;
+        if (threadIdx.x < 2u) {                            // the outputs of the tile's first and last byte
+            const uint64_t target = threadIdx.x ? p1 - 1u : p0;
+            uint64_t lo = 0, hi = n_seqs - 1u;
+            while (lo < hi) {                              // first j with ends[j] > target (target < total = ends[n_seqs - 1])
+                const uint64_t mid = lo + ((hi - lo) >> 1);
+                if (ends[mid] > target) hi = mid; else lo = mid + 1u;
+            }
+            bound[threadIdx.x] = lo;
+        }
+        __syncthreads();
+        const uint64_t jlo = bound[0], jhi = bound[1];
+        for (uint32_t q = 0; q < FZ_TILE_BYTES / 16u / FZ_REC_THREADS; ++q) {
+            uint64_t p = p0 + (uint64_t)(q * FZ_REC_THREADS + threadIdx.x) * 16u;
+            if (p >= p1) continue;
+            uint64_t lo = jlo, hi = jhi;
+            while (lo < hi) {
+                const uint64_t mid = lo + ((hi - lo) >> 1);
+                if (ends[mid] > p) hi = mid; else lo = mid + 1u;
+            }
+            uint64_t j = lo;
+            if (p + 16u <= ends[j]) {                      // the piece lies inside output j
+                uint4 v;
+                __builtin_memcpy(&v, raw + fz_derive_piece_lo(src[j], ends[j] - at[j], p - at[j], 16u, REV), 16);
+                if (REV) fz_derive_rev16(v.x, v.y, v.z, v.w);
+                if (XLAT) { v.x = fz_derive_xlat4(xb, v.x); v.y = fz_derive_xlat4(xb, v.y); v.z = fz_derive_xlat4(xb, v.z); v.w = fz_derive_xlat4(xb, v.w); }
+                *reinterpret_cast<uint4 *>(packed + p) = v;
+            } else {
+                const uint64_t pe = p + 16u < total ? p + 16u : total;
+                for (; p < pe; ++p) {
+                    while (ends[j] <= p) ++j;              // (p < total: such a j exists; empty outputs are passed)
+                    const uint8_t c = raw[fz_derive_byte_src(src[j], ends[j] - at[j], p - at[j], REV)];
+                    packed[p] = XLAT ? xb[c] : c;
+                }
+            }
+        }
+        __syncthreads();
+    }
+}

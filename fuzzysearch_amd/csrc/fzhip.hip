@@ -424,6 +424,7 @@ struct fz_ctx {
     // searches are collective (every rank gets the merged global stream)
     bool any_found = false;                      // result of the last has_near_match_* (fz_*_any) search
     double rec_ms[4] = {0, 0, 0, 0};             // fz_debug_records_ms: the last fz_batch_upload_records
+    double drv_ms[5] = {0, 0, 0, 0, 0};          // fz_debug_derive_ms: the last fz_batch_derive
     bool batch_call = false;                     // inside fz_batch_search: the one caller a batch handle is valid for (validate)
     // sharded searches: where every shard's (rank's) records end in the collected vector, and the shards in ascending
     // order of the index range they own (emit_matches orders shard by shard)
@@ -3246,6 +3247,165 @@ uint32_t fz_debug_fasta_upper4(uint32_t w) { return fz_fa_upper4(w); }
 
 uint64_t fz_debug_fasta_src(uint64_t offset, uint64_t linebases, uint64_t linewidth, uint64_t q) {
     return linebases ? fz_fa_src(offset, linebases, linewidth, q) : offset;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Derived batches (fz_batch_derive): a third producer for batch_make_handle, next to the two text uploads.  It uploads the
+// caller's tables and no text: one lane per output measures and checks its cut of the parent (fz_kernels.h:
+// fz_derive_measure_kernel), the records path's scan places the outputs, and the gather fills the new handle from the
+// parent's packed bytes where they lie.
+
+namespace {
+static_assert(sizeof(fz_derive_info) == 40, "fz_derive_info");
+
+const char *drv_reason_text(uint32_t reason) {
+    switch (reason) {
+    case FZ_DRV_E_INDEX: return "the index is not a sequence of the parent batch";
+    case FZ_DRV_E_ORDER: return "the start lies behind the end";
+    case FZ_DRV_E_END: return "the end lies behind the end of the parent sequence";
+    }
+    return "bad item";
+}
+
+int drv_report(uint64_t key, fz_derive_info *info) {
+    if (info) { info->bad_item = fz_rec_err_record(key); info->bad_reason = fz_rec_err_reason(key); }
+    return fail(FZ_EINVAL, "derive: item %llu: %s", (unsigned long long)fz_rec_err_record(key), drv_reason_text(fz_rec_err_reason(key)));
+}
+
+int drv_check_args(uint64_t n_src, bool has_index, uint64_t n_out, uint32_t flags) {
+    if (flags & ~FZ_DERIVE_REVERSE) return fail(FZ_EINVAL, "unknown derive flags");
+    if (n_out >= (1ull << 32)) return fail(FZ_EUNSUPPORTED, "more than 2^32 - 1 sequences in a batch");
+    if (!has_index && n_out != n_src) return fail(FZ_EINVAL, "without an index the derived batch has the parent's number of sequences");
+    return FZ_OK;
+}
+
+// The caller's tables on the device for the length of one call.
+struct DrvTables {
+    uint32_t *index = nullptr, *xlat = nullptr;
+    uint64_t *starts = nullptr, *ends = nullptr;
+    ~DrvTables() {
+        for (void *p : {(void *)index, (void *)xlat, (void *)starts, (void *)ends})
+            if (p) (void)hipFree(p);
+    }
+};
+
+int drv_upload_bytes(DevState &d, void **dst, const void *src, uint64_t bytes) {
+    if (!src || !bytes) return FZ_OK;
+    if (int rc = rec_malloc_bytes(dst, bytes)) return rc;
+    HIP_TRY(hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, d.stream));
+    return FZ_OK;
+}
+#define drv_upload(d, pp, src, count) drv_upload_bytes(d, reinterpret_cast<void **>(pp), src, (count) * sizeof(**(pp)))
+}  // namespace
+
+int fz_batch_derive(fz_ctx *ctx, fz_seq *batch, const uint32_t *index, const uint64_t *starts, const uint64_t *ends, uint64_t n_out,
+                    uint32_t flags, const uint8_t *translate, fz_seq **out, fz_derive_info *info) {
+    if (!ctx || !batch || !out) return fail(FZ_EINVAL, "null argument");
+    *out = nullptr;
+    if (info) *info = fz_derive_info{};
+    int rc = batch_upload_admit(ctx);
+    if (rc) return rc;
+    if (std::find(ctx->live.begin(), ctx->live.end(), batch) == ctx->live.end())
+        return fail(FZ_EINVAL, "fz_batch_derive takes a live batch handle of this context");
+    if (!batch->is_batch) return fail(FZ_EINVAL, "fz_batch_derive takes a batch handle");
+    if (batch->shards.size() != 1) return fail(FZ_EUNSUPPORTED, "batches are derived on one device");
+    const uint64_t n_src = batch->n_seqs;
+    if ((rc = drv_check_args(n_src, index != nullptr, n_out, flags))) return rc;
+    if (info) info->n_out = n_out;
+    Ingest in(ctx, "derive");
+    DevState &d = in.d;
+    DrvTables tb;
+    HIP_TRY(hipSetDevice(d.device));
+    if (in.timed) for (auto &ev : d.rec_ev) if (!ev) HIP_TRY(hipEventCreate(&ev));
+    // 1. the tables
+    in.mark();
+    if (n_out) {
+        if ((rc = drv_upload(d, &tb.index, index, n_out))) return rc;
+        if ((rc = drv_upload(d, &tb.starts, starts, n_out))) return rc;
+        if ((rc = drv_upload(d, &tb.ends, ends, n_out))) return rc;
+        if ((rc = drv_upload(d, &tb.xlat, translate, 64))) return rc;
+    }
+    in.mark();
+    // 2. one lane per output; the scan of the lengths.  The packed length is at most n_out times the parent's longest.
+    uint64_t key = FZ_REC_NO_ERROR, total = 0, longest = 0;
+    in.n = (batch->max_seq_len && n_out > ~0ull / batch->max_seq_len) ? ~0ull : n_out * batch->max_seq_len;
+    if (n_out) {
+        if ((rc = rec_malloc(&in.starts, n_out))) return rc;
+        if ((rc = rec_malloc(&in.at, n_out + 1))) return rc;
+        if ((rc = in.arm_verdict())) return rc;
+        hipLaunchKernelGGL(fz_derive_measure_kernel, dim3(rec_grid(d, (n_out + FZ_REC_THREADS - 1) / FZ_REC_THREADS)), dim3(FZ_REC_THREADS), 0, d.stream,
+                           batch->d_ends_base, n_src, tb.index, tb.starts, tb.ends, n_out, in.starts, in.at, in.info);
+        if ((rc = in.scan(in.at, n_out + 1))) return rc;
+    }
+    in.mark();
+    if (n_out && (rc = in.read_verdict(n_out, &key, &total, &longest))) return rc;
+    if (key != FZ_REC_NO_ERROR) return drv_report(key, info);
+    if (total >= (1ull << FZ_IDX_BITS)) return fail(FZ_EUNSUPPORTED, "sequence too long");
+    if (info) { info->packed_bytes = total; info->longest = longest; }
+    // 3. the handle, its bytes gathered from the parent's
+    const uint8_t *raw = batch->shards[0].d_buf;
+    const bool rev = (flags & FZ_DERIVE_REVERSE) != 0;
+    fz_seq *seq = nullptr;
+    rc = batch_make_handle(ctx, n_out, total, longest, nullptr, in.at, &in.d2h_ms, &seq, [&](uint8_t *d_buf) {
+        const dim3 grid(rec_grid(d, (total + FZ_TILE_BYTES - 1) / FZ_TILE_BYTES)), block(FZ_REC_THREADS);
+        in.mark();
+        if (total) {
+            if (tb.xlat && rev)
+                hipLaunchKernelGGL((fz_derive_gather_kernel<true, true>), grid, block, 0, d.stream, raw, in.starts, in.at, n_out, total, tb.xlat, d_buf);
+            else if (tb.xlat)
+                hipLaunchKernelGGL((fz_derive_gather_kernel<false, true>), grid, block, 0, d.stream, raw, in.starts, in.at, n_out, total, tb.xlat, d_buf);
+            else if (rev)
+                hipLaunchKernelGGL((fz_derive_gather_kernel<true, false>), grid, block, 0, d.stream, raw, in.starts, in.at, n_out, total, tb.xlat, d_buf);
+            else                                          // neither: the records gather, the parent's bytes as its text
+                hipLaunchKernelGGL(fz_rec_gather_kernel, grid, block, 0, d.stream, raw, in.starts, in.at, n_out, total, d_buf);
+        }
+        in.mark();
+        // a timed call waits for the gather here, so that the host clock around the D2H of ends[] (batch_make_handle) holds
+        // the copy and not the gather in front of it on the stream
+        if (in.timed) HIP_TRY(hipStreamSynchronize(d.stream));
+        return FZ_OK;
+    });
+    if (rc) return rc;
+    if (n_out) { seq->d_src_starts = in.starts; in.starts = nullptr; }
+    for (int i = 0; i < 4; ++i) ctx->drv_ms[i] = 0;       // (an untimed call leaves no spans of an earlier one behind)
+    if (in.timed) {
+        ctx->drv_ms[0] = span_ms(d.rec_ev[0], d.rec_ev[1]);
+        ctx->drv_ms[1] = span_ms(d.rec_ev[1], d.rec_ev[2]);
+        ctx->drv_ms[2] = span_ms(d.rec_ev[3], d.rec_ev[4]);
+        ctx->drv_ms[3] = in.d2h_ms;
+    }
+    ctx->drv_ms[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - in.t_call).count();
+    ctx->live.push_back(seq);
+    *out = seq;
+    return FZ_OK;
+}
+
+int fz_debug_derive_ms(fz_ctx *ctx, double *ms5) {
+    if (!ctx || !ms5) return fail(FZ_EINVAL, "null argument");
+    for (int i = 0; i < 5; ++i) ms5[i] = ctx->drv_ms[i];
+    return FZ_OK;
+}
+
+int fz_debug_derive_plan(const uint64_t *offs, uint64_t n_src, const uint32_t *index, const uint64_t *starts, const uint64_t *ends,
+                         uint64_t n_out, uint64_t *src, uint64_t *at, fz_derive_info *info) {
+    if ((!offs && n_src) || ((!src || !at) && n_out) || !info) return fail(FZ_EINVAL, "null argument");
+    *info = fz_derive_info{};
+    if (int rc = drv_check_args(n_src, index != nullptr, n_out, 0)) return rc;
+    info->n_out = n_out;
+    uint64_t key = FZ_REC_NO_ERROR, total = 0, longest = 0;
+    for (uint64_t j = 0; j < n_out; ++j) {
+        const FzDrvItem o = fz_derive_item(offs, n_src, index, starts, ends, j);
+        if (o.reason != FZ_REC_OK) key = std::min(key, fz_rec_err_key(j, o.reason));
+        src[j] = o.src;
+        at[j] = total;
+        total += o.len;
+        longest = std::max(longest, o.len);
+    }
+    if (at) at[n_out] = total;
+    if (key != FZ_REC_NO_ERROR) return drv_report(key, info);
+    if (total >= (1ull << FZ_IDX_BITS)) return fail(FZ_EUNSUPPORTED, "sequence too long");
+    info->packed_bytes = total; info->longest = longest;
+    return FZ_OK;
 }
 
 int fz_search_exact(fz_ctx *ctx, fz_seq *seq, const uint8_t *p, uint32_t m, uint64_t lo, uint64_t hi,

@@ -370,7 +370,8 @@ int fz_batch_upload_records(fz_ctx *ctx, const uint8_t *text, uint64_t n, uint32
                             uint32_t flags, fz_seq **out, fz_records_info *info);
 
 /* The tables of a batch handle, n_seqs entries each (either may be NULL): src_starts[j] = offset of sequence j's first byte
- * in the text it was cut from (a handle of fz_batch_upload: offs[j]), ends[j] = its end in the packed bytes. */
+ * in the text it was cut from (a handle of fz_batch_upload: offs[j]; of fz_batch_derive: its lowest source byte in the parent's
+ * packed bytes), ends[j] = its end in the packed bytes. */
 int fz_batch_tables(const fz_seq *batch, uint64_t *src_starts, uint64_t *ends);
 
 /* Test hooks.  fz_debug_batch_bytes: the packed bytes of a batch handle back from the device (cap >= fz_seq_len).
@@ -418,6 +419,40 @@ int fz_debug_fasta_split(const uint8_t *text, uint64_t n, uint32_t flags, fz_fas
                          fz_records_info *info);
 uint32_t fz_debug_fasta_upper4(uint32_t w);
 uint64_t fz_debug_fasta_src(uint64_t offset, uint64_t linebases, uint64_t linewidth, uint64_t q);
+
+/* Derived batches: a batch made from a batch where it lies, in device memory.  The rule:
+ *     out[j] = X(batch[i_j][a_j : b_j])   for j < n_out
+ *     i_j = index[j] (index NULL: j, and n_out must be the batch's number of sequences), a_j = starts[j] (NULL: 0),
+ *     b_j = ends[j] (NULL: the length of sequence i_j); starts / ends are per OUTPUT and local to sequence i_j;
+ *     X = every byte through the 256-byte table `translate` (NULL: as it is), then, with FZ_DERIVE_REVERSE, the bytes in
+ *     reverse order.
+ *   index may repeat and need not ascend, so the derived batch may be larger than its parent; empty outputs are sequences.
+ *   An item is bad when i_j is no sequence of the batch (reason 1), a_j > b_j (2) or b_j > the length of sequence i_j (3).  The
+ *   smallest bad j is an error: FZ_EINVAL, *out = NULL, info->bad_item / bad_reason filled in, nothing left allocated.
+ * On the device (fz_kernels.h: fz_derive_*_kernel): the given tables are uploaded, one lane per output measures and checks
+ * it, the lengths are scanned as fz_batch_upload_records scans them, and the bytes are gathered from the batch's packed bytes
+ * by 16-byte pieces of the destination.  No text crosses PCIe; ends[] of the new handle comes back.
+ * `batch`: a live batch handle of this context (fz_batch_upload, _records, _fasta or fz_batch_derive), which stays as it is
+ * and may be released before the derived one.  Refusals as the uploads': several devices or a communicator, a search in
+ * flight, n_out of 2^32 or more, a packed length of 2^48 bytes or more (FZ_EUNSUPPORTED).  The handle is a batch handle like
+ * any other; its fz_batch_tables src_starts[j] is the offset of output j's lowest source byte in the PARENT's packed bytes. */
+#define FZ_DERIVE_REVERSE 1u
+typedef struct {
+    uint64_t n_out, packed_bytes, longest, bad_item;
+    uint32_t bad_reason;
+} fz_derive_info;
+
+int fz_batch_derive(fz_ctx *ctx, fz_seq *batch, const uint32_t *index, const uint64_t *starts, const uint64_t *ends, uint64_t n_out,
+                    uint32_t flags, const uint8_t *translate, fz_seq **out, fz_derive_info *info);
+/* Test hooks.  fz_debug_derive_plan: no device; the measure step and the scan on the host through the function the kernel
+ * runs (fz_device.h: fz_derive_item).  offs = the parent's n_src + 1 offsets; src[] (n_out entries) and at[] (n_out + 1: the
+ * outputs' starts in the packed bytes, the total last) are the caller's; the verdict as above, in *info.
+ * fz_debug_derive_ms: device and host spans of the context's last fz_batch_derive, milliseconds: {the tables' H2D copies,
+ * measure + scan, the gather (hipEvents on the stream), the D2H of ends[] (host clock, started once the gather has finished),
+ * whole call}.  With timing off (fz_set_timing) the first four are 0 and the call does not wait for the gather on its own. */
+int fz_debug_derive_plan(const uint64_t *offs, uint64_t n_src, const uint32_t *index, const uint64_t *starts, const uint64_t *ends,
+                         uint64_t n_out, uint64_t *src, uint64_t *at, fz_derive_info *info);
+int fz_debug_derive_ms(fz_ctx *ctx, double *ms5);
 
 /* has_near_match_* (substitutions_only.py:139-145, :218-233; generic_search.py:240-253): *found = 1 iff the
  * corresponding search would return at least one record.  Nothing is ordered or copied, and device work that starts
