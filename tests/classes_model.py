@@ -34,14 +34,27 @@ def windows_within(p, text, k, A):
 
 def raw_rows(p, text, k, A):
     """The raw stream of one pattern: (start, end, dist, block) for every window within k and every n-gram block
-    [g * L, g * L + L) of the pattern (L = len(p) // (k + 1)) that the window class-matches exactly; by (block, start)."""
-    m = len(p)
+    [g * L, g * L + L) of the pattern (L = len(p) // (k + 1)) that the window class-matches exactly; by (block, start).
+    (window_matches() column by column - does text byte i + q match pattern position q? - summed and and-ed as vectors over
+    the windows, without the [windows, len(p)] array: the seam sweeps run this over texts of megabytes.)"""
+    p = bytes(p)
+    m, n = len(p), len(text)
+    if m == 0 or n < m:
+        return []
     L = m // (k + 1)
-    acc = window_matches(p, text, A)
-    dist = m - acc.sum(axis=1)
+    nw = n - m + 1
+    t = np.frombuffer(bytes(text), dtype=np.uint8)
+    accepted = {c: A[c][t] for c in set(p)}                 # per pattern symbol: which text bytes it matches
+    matches = np.zeros(nw, dtype=np.int32)
+    for q, c in enumerate(p):
+        matches += accepted[c][q:q + nw]
+    dist = m - matches
+    within = dist <= k
     rows = []
     for g in range(m // L):
-        ok = (dist <= k) & acc[:, g * L:g * L + L].all(axis=1)
+        ok = within.copy()
+        for q in range(g * L, g * L + L):
+            ok &= accepted[p[q]][q:q + nw]
         rows += [(int(i), int(i) + m, int(dist[i]), g) for i in np.nonzero(ok)[0]]
     return rows
 

@@ -14,6 +14,23 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
+def force_pass():
+    """A fixture's body (`force_pass = pytest.fixture(gpu_cases.force_pass)`): -> a function that sets / clears
+    FZ_MP_FORCE_PASS and has the library read its switches again; cleared afterwards."""
+    from fuzzysearch_amd import _native
+    lib = _native.load_library()
+
+    def switch(on):
+        if on:
+            os.environ["FZ_MP_FORCE_PASS"] = "1"
+        else:
+            os.environ.pop("FZ_MP_FORCE_PASS", None)
+        lib.fz_debug_reload_switches()
+
+    yield switch
+    switch(False)
+
+
 def edited(rnd, p, n_edits, alpha):
     v = bytearray(p)
     for _ in range(n_edits):
@@ -363,6 +380,178 @@ def run_batch_noisy(engine, route, n_cus, tiles=3, side=None):
         assert on_device >= hits, (route.name, "the device lists fewer n-gram hits than the oracle verifies", on_device, hits)
         assert (on_device > bc.WF_COMPACT_MIN) == (side == "compact"), (route.name, side, on_device)
     return rows, hits, on_device
+
+
+# -- the multi-pattern seam sweep (tests/mp_seam_case.py) ----------------------------------------------------------------------
+def mp_search(engine, h, r, pats):
+    """One multi-pattern call of the route's mode over resident `h` -> the raw stream of every pattern of the list."""
+    from tests import mp_seam_case as mc
+    if r.mode == "lev":
+        return engine.lev_ngrams_multi(h, pats, r.k)
+    if r.mode == "subs":
+        return engine.subs_ngrams_multi(h, pats, r.k)
+    return engine.subs_ngrams_multi_classes(h, pats, r.k, mc.tables())
+
+
+def check_mp_streams(r, pats, got, want, st, what, raw_matches=None):
+    """Every pattern's full ordered stream against `want`; the call rode a pass and counted its raw rows (`raw_matches`: how
+    many, where `want` is not the raw stream)."""
+    from tests import mp_seam_case as mc
+    assert len(got) == len(want) == len(pats)
+    for i, (g, w) in enumerate(zip(got, want)):
+        if g != w:
+            bad = next((j for j, (a, b) in enumerate(zip(g, w)) if a != b), min(len(g), len(w)))
+            raise AssertionError("%s %s, pattern %d (m = %d): %d rows against %d expected, first difference at row %d: %r / %r" % (
+                r.name, what, i, len(pats[i]), len(g), len(w), bad, g[bad:bad + 2], w[bad:bad + 2]))
+    assert st["verify_form"] == mc.FORM_KERNEL, (r.name, what, "verify_form", st["verify_form"])
+    n_raw = sum(len(w) for w in want) if raw_matches is None else raw_matches
+    assert st["raw_matches"] == n_raw, (r.name, what, "raw_matches", st["raw_matches"], n_raw)
+    return sum(len(w) for w in want)
+
+
+def check_mp_case(engine, case, want, what):
+    """Upload the case's text, one call for the whole list, check_mp_streams.  -> rows compared."""
+    h = engine.upload(case.text)
+    try:
+        got = mp_search(engine, h, case.route, case.patterns)
+        st = engine.stats()
+    finally:
+        h.release()
+    return check_mp_streams(case.route, case.patterns, got, want, st, what)
+
+
+def run_mp_shard_cut(engine, r, cut, n):
+    """The sweep of every carrier across a shard cut at byte `cut` of an n-byte text (seam_case's class `first` with the cut
+    for its seam: one text per carrier and phase): the text whole, and as two shards with the halo the mode needs - m + k for
+    Levenshtein, m for substitutions and classes.  Per pattern the two shards' rows together, by (block, start), are the
+    whole text's rows and the oracle's.  -> (coverage per carrier, texts, rows)."""
+    from tests import mp_seam_case as mc
+    from tests import seam_case as sc
+    pats, carriers = mc.list_of(r)
+    halo = max(len(p) for p in pats) + (r.k if r.mode == "lev" else 0)
+    covers, texts, rows, straddling = {}, 0, 0, 0
+    for i in carriers:
+        m = len(pats[i])
+        per = []
+        for ph in range(sc.phases("first", m, r.k)):
+            case = mc.build(r, n, 1, specs=[(i, ("first",), ph, cut)], seed=17 + ph)
+            want = mc.expected(case)
+            mc.check_exact_copies_found(case, want)
+            text = case.text.tobytes()
+            whole = engine.upload(text)
+            a = engine.upload_shard(text[:cut + halo], 0, 0, cut, n)
+            b = engine.upload_shard(text[cut - halo:], cut - halo, cut, n, n)
+            try:
+                got = mp_search(engine, whole, r, pats)
+                check_mp_streams(r, pats, got, want, engine.stats(), "whole, carrier %d phase %d" % (i, ph))
+                ra = mp_search(engine, a, r, pats)
+                sa = engine.stats()
+                rb = mp_search(engine, b, r, pats)
+                sb = engine.stats()
+            finally:
+                for h in (whole, a, b):
+                    h.release()
+            both = [sorted(x + y, key=lambda row: (row[3], row[0])) for x, y in zip(ra, rb)]
+            assert sa["raw_matches"] == sum(len(x) for x in ra) and sb["raw_matches"] == sum(len(x) for x in rb)
+            assert sa["verify_form"] == sb["verify_form"] == mc.FORM_KERNEL
+            sb["raw_matches"] += sa["raw_matches"]
+            rows += check_mp_streams(r, pats, both, want, sb, "two shards, carrier %d phase %d, d = %s" % (
+                i, ph, [pl.d for pl in case.plants]))
+            straddling += sum(1 for w in want for row in w if row[0] < cut < row[1])
+            per.append(case.coverage[i])
+            texts += 1
+        covers[i] = sc.merge_coverage(per)
+        mc.check_edge_coverage(covers[i], m, r.k)
+    assert straddling > 0
+    return covers, texts, rows
+
+
+def mp_batch_expected(r, pats, seqs, caches):
+    """The oracle (lev, subs) or the class model (cls) per (pattern, sequence) -> per pattern (raw rows, reduced rows) as
+    (sequence, start, end, dist[, block]).  `caches`: one dict per pattern, by sequence bytes."""
+    from fuzzysearch_amd import _native
+    from tests import batch_seam_case as bc
+    from tests import classes_model
+    from tests import seam_case as sc
+    out = []
+    for p, cache in zip(pats, caches):
+        if r.mode != "cls":
+            out.append(bc.expected(bc.MODE[r.mode], p, seqs, r.k, cache))
+            continue
+        raw, red = [], []
+        for j, s in enumerate(seqs):
+            if len(s) < len(p):
+                continue
+            hit = cache.get(s)
+            if hit is None:
+                rows = classes_model.raw_rows(p, s, r.k, sc.iupac_accept())
+                hit = cache[s] = (rows, [tuple(x)[:3] for x in _native.group_best(rows)] if rows else [])
+            raw += [(j,) + row for row in hit[0]]
+            red += [(j,) + row for row in hit[1]]
+        out.append((raw, red))
+    return out
+
+
+def run_mp_batch_seams(engine, r):
+    """The seam classes of tests/batch_seam_case.py for every carrier of the route's list, each batch searched with the WHOLE
+    list through fz_batch_search_multi (classes: fz_batch_search_multi_cls), raw and reduced: every (pattern, sequence) slice
+    against the oracle run on that sequence alone, no row outside its sequence.  -> (line, searches, rows compared)."""
+    import numpy as np
+    from tests import batch_seam_case as bc
+    from tests import mp_seam_case as mc
+    from tests import seam_case as sc
+    pats, carriers = mc.list_of(r)
+    caches = [{} for _ in pats]
+    rnd = random.Random(23)
+    n_search = n_rows = 0
+    parts = []
+    for i in carriers:
+        rr = sc._r("%s-m%d" % (r.name, len(pats[i])), "lev" if r.mode == "lev" else "subs", len(pats[i]), r.k, sc.FORM_KERNEL, alpha=r.alpha)
+        assert bc.tier(rr) == 0
+        for cls, seqs, plants, cover in bc.batches(rr, pats[i]):
+            bc.check_coverage(rr, cls, cover, seqs)
+            if r.mode == "cls":                                 # every copy as one of its spellings
+                blob = bytearray(b"".join(seqs))
+                for pl in plants:
+                    blob[pl.start:pl.start + len(pl.data)] = mc.spell(rnd, pl.data)
+                ends = np.cumsum([len(s) for s in seqs]).tolist()
+                seqs = [bytes(blob[lo:hi]) for lo, hi in zip([0] + ends[:-1], ends)]
+            blob, offs = bc.pack(seqs)
+            want = mp_batch_expected(r, pats, seqs, caches)
+            h = engine.upload_batch(blob, offs)
+            try:
+                if r.mode == "cls":
+                    raw = engine.batch_search_multi_classes(h, pats, r.k, mc.tables(), reduced=False)
+                    st_raw = engine.stats()
+                    red = engine.batch_search_multi_classes(h, pats, r.k, mc.tables(), reduced=True)
+                else:
+                    raw = engine.batch_search_multi(h, mc.MODES[r.mode], pats, r.k, reduced=False)
+                    st_raw = engine.stats()
+                    red = engine.batch_search_multi(h, mc.MODES[r.mode], pats, r.k, reduced=True)
+                st_red = engine.stats()
+            finally:
+                h.release()
+            what = "%s carrier %d" % (cls, i)
+            got_raw = [batch_flat(*x) for x in raw]
+            n_raw = check_mp_streams(r, pats, got_raw, [w[0] for w in want], st_raw, what + ", raw")
+            # (the reduced call reduces the same raw rows: its own stats count them, and name the pass)
+            got_red = [[g[:4] for g in batch_flat(*x)] for x in red]
+            check_mp_streams(r, pats, got_red, [w[1] for w in want], st_red, what + ", reduced", raw_matches=n_raw)
+            for g in got_raw:
+                assert all(0 <= row[1] <= row[2] <= len(seqs[row[0]]) for row in g), (r.name, what, "a row leaves its sequence")
+            assert sum(len(w[0]) for w in want) > 0, (r.name, what)
+            n_search += 2
+            n_rows += sum(len(w[0]) + len(w[1]) for w in want)
+        parts.append("m %d: %s" % (len(pats[i]), ", ".join(bc.classes_of(rr))))
+    return "mp batch seams %-12s %d patterns | %s" % (r.name, len(pats), "; ".join(parts)), n_search, n_rows
+
+
+def batch_flat(rows, seq_of):
+    """(rows, seq_of) of one pattern of a batch call -> [(sequence, start, end, dist, block)]; seq_of is non-decreasing."""
+    import numpy as np
+    assert len(rows) == len(seq_of)
+    assert np.all(np.diff(seq_of.astype(np.int64)) >= 0), "seq_of is non-decreasing within a pattern's slice"
+    return [(int(j),) + tuple(int(x) for x in row) for j, row in zip(seq_of.tolist(), rows.tolist())]
 
 
 # -- the file stream (tests/file_seam_case.py) -------------------------------------------------------------------------------

@@ -161,15 +161,19 @@ def quiet_alphabet(p):
 
 
 def build(p, k, n, n_cus, background="quiet", subs_only=False, classes=MANY, phase=0, seed=1, copies=2, shares_chip=0,
-          text=None, bg=None, tile_base=0, pattern_alphabet=None, tile_pool=None, limits=None, keep=(), first_seam=None, dry=False):
+          text=None, bg=None, tile_base=0, pattern_alphabet=None, tile_pool=None, limits=None, keep=(), first_seam=None, dry=False,
+          plan=None, spell=None):
     """-> Case.  `classes`: which seam classes are planted; `phase`: which slice of the few-seam classes' sweeps (see the
     module docstring); `copies`: 2 = an exact and an edited copy per d for the many-seam classes, 1 = exact only;
     `text` / `bg`: a text built earlier for the same (n, background) whose plants were restored; `tile_base`: byte of the
     text where the device buffer's tile 0 starts; `tile_pool`: the tiles whose seams the class `tile` may use (default:
     all, drawn so that iterations 0, 1 and last occur); `keep`: plants (of other patterns) that `text` holds already -
     they stay, and the case's plant list, which the sparse oracle works from, includes them; `first_seam`: the one seam of
-    the class `first` (default: the end of tile 0); `dry`: no text is built, plants and coverage only.  The Case carries
-    the Background, whose restore() takes the plants out of the text again."""
+    the class `first` (default: the end of tile 0); `dry`: no text is built, plants and coverage only; `plan`: (grid, form,
+    overlapped, regions) of a launch that is not the single-pattern scan's (tests/mp_seam_case.py: the multi-pattern
+    filter's) instead of the plan hook's answer; `spell`: (rnd, bytes) -> bytes, applied to every copy on its way into the
+    text (a pattern with symbol classes is planted as one of its spellings).  The Case carries the Background, whose
+    restore() takes the plants out of the text again."""
     p = bytes(p)
     m = len(p)
     rnd = random.Random(seed * 1000003 + phase)
@@ -180,7 +184,7 @@ def build(p, k, n, n_cus, background="quiet", subs_only=False, classes=MANY, pha
         text = bg.fill(n)
     assert dry or len(text) == n
     ntiles = (n - tile_base + TILE - 1) // TILE
-    grid, form, overlapped, regions = scan_plan(p, k, n - tile_base, n_cus, shares_chip)
+    grid, form, overlapped, regions = plan or scan_plan(p, k, n - tile_base, n_cus, shares_chip)
     occupied = np.zeros(n // GRAIN + 2, dtype=bool)
     plants = list(keep)
     for pl in keep:
@@ -204,8 +208,11 @@ def build(p, k, n, n_cus, background="quiet", subs_only=False, classes=MANY, pha
             cover[cls]["tiles"].add(tile_owner((seam - tile_base) // TILE, ntiles, grid, regions))
         return True
 
+    def spelled(data):
+        return spell(rnd, data) if spell else data
+
     def variant(exact):
-        return p if exact else edited_copy(rnd, p, k, alpha, subs_only, limits)
+        return spelled(p if exact else edited_copy(rnd, p, k, alpha, subs_only, limits))
 
     offs = sweep_offsets(m, k)
     reach = m + 2 * k + 2
@@ -222,7 +229,7 @@ def build(p, k, n, n_cus, background="quiet", subs_only=False, classes=MANY, pha
                 data = variant(exact)
                 ok = put(d if cls == "start" else n - d - len(data), data, cls, d, 0 if cls == "start" else n, exact)
             else:
-                data = p[-d:] if cls == "start" else p[:m + d]
+                data = spelled(p[-d:] if cls == "start" else p[:m + d])
                 ok = put(0 if cls == "start" else n - len(data), data, cls, d, 0 if cls == "start" else n, True, whole=False)
             assert ok, (cls, d)
             continue
@@ -282,8 +289,24 @@ def build(p, k, n, n_cus, background="quiet", subs_only=False, classes=MANY, pha
 
 
 # -- expected streams --------------------------------------------------------------------------------------------------------
+_iupac = []
+
+
+def iupac_accept():
+    """The acceptance table of fuzzysearch_amd.IUPAC_DNA (tests/classes_model.py), built once."""
+    if not _iupac:
+        import fuzzysearch_amd
+        from tests import classes_model
+        _iupac.append(classes_model.accept_table(fuzzysearch_amd.IUPAC_DNA))
+    return _iupac[0]
+
+
 def oracle_fn(kind, p, k):
-    """kind: 'lev', 'subs', 'exact' or ('generic', max_subs, max_ins, max_dels) -> text bytes -> rows."""
+    """kind: 'lev', 'subs', 'exact', 'cls' (substitutions under the IUPAC classes: the model of tests/classes_model.py) or
+    ('generic', max_subs, max_ins, max_dels) -> text bytes -> rows."""
+    if kind == "cls":
+        from tests import classes_model
+        return lambda t: classes_model.raw_rows(p, t, k, iupac_accept())
     if kind == "lev":
         return lambda t: oracle.lev_ngrams_raw(p, t, k)
     if kind == "subs":
@@ -332,7 +355,7 @@ def check_exact_copies_found(kind, case, rows):
     if kind == "exact":
         have = set(rows)
         missing = [pl.start for pl in case.plants if pl.exact and pl.whole and pl.start not in have]
-    elif kind in ("lev", "subs"):
+    elif kind in ("lev", "subs", "cls"):
         have = set(r[:3] for r in rows)
         missing = [pl.start for pl in case.plants if pl.exact and pl.whole and (pl.start, pl.start + m, 0) not in have]
     else:

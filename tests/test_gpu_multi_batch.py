@@ -18,20 +18,7 @@ EXACT, LEV, SUBS = 0, 1, 2
 FORM_KERNEL = 5
 
 
-@pytest.fixture
-def force_pass():
-    """-> a function that sets / clears FZ_MP_FORCE_PASS and has the library read its switches again; cleared afterwards."""
-    lib = _native.load_library()
-
-    def switch(on):
-        if on:
-            os.environ["FZ_MP_FORCE_PASS"] = "1"
-        else:
-            os.environ.pop("FZ_MP_FORCE_PASS", None)
-        lib.fz_debug_reload_switches()
-
-    yield switch
-    switch(False)
+force_pass = pytest.fixture(gpu_cases.force_pass)
 
 
 def _rand(rnd, alpha, n):
