@@ -116,8 +116,8 @@ def main():
             want = _native.group_best([(s, s + m, d, -1) for s, d in sorted(merged.items())]) if merged else []
             assert sorted(tuple(r)[:3] for r in best_c[i].tolist()) == sorted(tuple(r)[:3] for r in want), "pattern %d: reduced rows differ" % i
             n_rows += len(merged)
-        run_c = lambda: eng._multi_call_classes("fz_subs_ngrams_multi_best_cls", h, pats, k, tables)
-        run_e = lambda: eng._multi_call(eng._lib.fz_subs_ngrams_multi_best, h, exp, k)
+        run_c = lambda: eng._multi_call("fz_subs_ngrams_multi_best", h, pats, k, tables)
+        run_e = lambda: eng._multi_call("fz_subs_ngrams_multi_best", h, exp, k)
 
         def once(run):
             box = []

@@ -14,32 +14,6 @@ LIB_PATH = os.environ.get("FUZZYSEARCH_HIP_LIB") or os.path.join(_HERE, "libfzhi
 FZ_OK, FZ_EINVAL, FZ_ENOMEM, FZ_EDEVICE, FZ_EUNSUPPORTED, FZ_EHALO, FZ_ETIMEOUT = 0, -1, -2, -3, -4, -5, -6
 UINT64_MAX = (1 << 64) - 1
 
-# every symbol include/fzhip.h declares (tests check the library exports exactly these)
-EXPORTED_SYMBOLS = (
-    "fz_abi_version", "fz_last_error", "fz_device_count", "fz_create", "fz_destroy",
-    "fz_seq_upload", "fz_seq_upload_shard", "fz_seq_new", "fz_seq_add_shard", "fz_seq_len", "fz_seq_release",
-    "fz_search_exact", "fz_lev_ngrams", "fz_lev_ngrams_begin", "fz_lev_ngrams_end", "fz_subs_ngrams", "fz_generic_ngrams",
-    "fz_subs_ngrams_begin", "fz_generic_ngrams_begin", "fz_search_end",
-    "fz_lev_lp", "fz_subs_lp", "fz_generic_lp", "fz_subs_ngrams_any", "fz_subs_lp_any", "fz_generic_ngrams_any", "fz_generic_ngrams_consolidated",
-    "fz_lev_ngrams_consolidated", "fz_subs_ngrams_best",
-    "fz_stream_open", "fz_stream_buffer", "fz_stream_submit", "fz_stream_read_fd", "fz_stream_finish", "fz_stream_close",
-    "fz_consolidate", "fz_group_best", "fz_merge_ranks", "fz_wire_pack", "fz_wire_merge", "fz_debug_launch_plan", "fz_debug_order_records", "fz_debug_order_records_bounded", "fz_debug_order_segments", "fz_stats", "fz_mem_info", "fz_set_timing", "fz_set_streams", "fz_device_ms", "fz_free",
-    "fz_comm_unique_id", "fz_comm_init_rank", "fz_comm_init_all", "fz_comm_info", "fz_comm_set_collective",
-    "fz_comm_allgather", "fz_comm_max_f64", "fz_comm_barrier", "fz_comm_destroy", "fz_comm_gather_ms", "fz_comm_backend", "fz_debug_reload_switches", "fz_debug_gather_merge", "fz_debug_scan_regions",
-    "fz_debug_scan_plan",
-    "fz_lev_ngrams_multi", "fz_lev_ngrams_multi_consolidated", "fz_debug_multi_plan",
-    "fz_subs_ngrams_multi", "fz_subs_ngrams_multi_best", "fz_debug_multi_plan_mode",
-    "fz_batch_upload", "fz_batch_search", "fz_debug_batch_segment",
-    "fz_batch_search_multi",
-    "fz_batch_assign", "fz_debug_assign_fold",
-    "fz_batch_upload_records", "fz_batch_tables", "fz_debug_batch_bytes", "fz_debug_records_split", "fz_debug_scan_items",
-    "fz_debug_records_ms",
-    "fz_batch_upload_fasta", "fz_batch_fasta_index", "fz_debug_fasta_split", "fz_debug_fasta_upper4", "fz_debug_fasta_src",
-    "fz_subs_ngrams_multi_cls", "fz_subs_ngrams_multi_best_cls", "fz_batch_search_multi_cls", "fz_batch_assign_cls",
-    "fz_debug_multi_plan_cls",
-    "fz_batch_derive", "fz_debug_derive_plan", "fz_debug_derive_ms",
-)
-
 
 class FzMatch(ctypes.Structure):
     _fields_ = [("start", ctypes.c_int64), ("end", ctypes.c_int64),
@@ -76,12 +50,145 @@ class CollectiveTimeout(HipEngineError):
     """A collective of the context's communicator did not complete within FZ_COMM_TIMEOUT_MS (a rank never arrived)."""
 
 
+# The C types of the prototypes.  vp: a handle or any untyped pointer; bp: bytes (a bytes object, an address or None).
+vp = bp = ctypes.c_void_p
+u32, u64, i64, ci, f64, cs = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int, ctypes.c_double, ctypes.c_char_p
+vpp, cip, f64p = ctypes.POINTER(vp), ctypes.POINTER(ci), ctypes.POINTER(f64)
+u32p, u64p, mp = ctypes.POINTER(u32), ctypes.POINTER(u64), ctypes.POINTER(FzMatch)
+u32pp, u64pp, mpp = ctypes.POINTER(u32p), ctypes.POINTER(u64p), ctypes.POINTER(mp)
+rip, dip, stp = ctypes.POINTER(FzRecordsInfo), ctypes.POINTER(FzDeriveInfo), ctypes.POINTER(FzStats)
+
+_SEARCH = (ci, (vp, vp, bp, u32, u32, mpp, u64p))                          # (ctx, seq, p, m, k, &rows, &n)
+_GENERIC = (ci, (vp, vp, bp, u32, u32, u32, u32, u32, mpp, u64p))          # (ctx, seq, p, m, subs, ins, dels, l, &rows, &n)
+_BEGIN = (ci, (vp, vp, bp, u32, u32))
+_END = (ci, (vp, mpp, u64p))
+_ANY = (ci, (vp, vp, bp, u32, u32, cip))
+_MULTI = (ci, (vp, vp, bp, u64p, u32, u32, mpp, u64pp))                    # (ctx, seq, pats, offs, n_pats, k, &rows, &offsets)
+_MULTI_CLS = (ci, (vp, vp, bp, u64p, u32, u32, bp, bp, mpp, u64pp))        # ... with pmask, tmask behind k
+_REDUCE = (ci, (mp, u64, mpp, u64p))
+
+# Every symbol include/fzhip.h declares, in its order: name -> (restype, argtypes).  load_library() declares exactly
+# these; tests/test_binding_host.py holds every line against the header's prototype.
+PROTOTYPES = {
+    "fz_abi_version": (ci, ()),
+    "fz_last_error": (cs, ()),
+    "fz_device_count": (ci, (cip,)),
+    "fz_create": (ci, (cip, ci, vpp)),
+    "fz_destroy": (None, (vp,)),
+    "fz_seq_upload": (ci, (vp, bp, u64, vpp)),
+    "fz_seq_upload_shard": (ci, (vp, bp, u64, u64, u64, u64, u64, vpp)),
+    "fz_seq_new": (ci, (vp, u64, vpp)),
+    "fz_seq_add_shard": (ci, (vp, ci, bp, u64, u64, u64, u64)),
+    "fz_seq_len": (u64, (vp,)),
+    "fz_seq_release": (None, (vp,)),
+    "fz_search_exact": (ci, (vp, vp, bp, u32, u64, u64, u64pp, u64p)),
+    "fz_lev_ngrams": _SEARCH,
+    "fz_lev_ngrams_begin": _BEGIN,
+    "fz_lev_ngrams_end": _END,
+    "fz_subs_ngrams_begin": _BEGIN,
+    "fz_generic_ngrams_begin": (ci, (vp, vp, bp, u32, u32, u32, u32, u32, ci)),
+    "fz_search_end": _END,
+    "fz_subs_ngrams": _SEARCH,
+    "fz_generic_ngrams": _GENERIC,
+    "fz_generic_ngrams_consolidated": _GENERIC,
+    "fz_lev_ngrams_consolidated": _SEARCH,
+    "fz_subs_ngrams_best": _SEARCH,
+    "fz_lev_ngrams_multi": _MULTI,
+    "fz_lev_ngrams_multi_consolidated": _MULTI,
+    "fz_debug_multi_plan": (ci, (bp, u64p, u32, u32, u32p, u32p)),
+    "fz_subs_ngrams_multi": _MULTI,
+    "fz_subs_ngrams_multi_best": _MULTI,
+    "fz_debug_multi_plan_mode": (ci, (u32, bp, u64p, u32, u32, u32p, u32p)),
+    "fz_batch_upload": (ci, (vp, bp, u64p, u64, vpp)),
+    "fz_batch_search": (ci, (vp, vp, u32, bp, u32, u32, ci, mpp, u32pp, u64p)),
+    "fz_batch_search_multi": (ci, (vp, vp, u32, bp, u64p, u32, u32, ci, mpp, u32pp, u64pp)),
+    "fz_batch_assign": (ci, (vp, vp, u32, bp, u64p, u32, u32, vpp)),
+    "fz_debug_assign_fold": (ci, (vp, u64, vp, u64, u32, vp, u32, vp, u32, u32, vp)),
+    "fz_subs_ngrams_multi_cls": _MULTI_CLS,
+    "fz_subs_ngrams_multi_best_cls": _MULTI_CLS,
+    "fz_batch_search_multi_cls": (ci, (vp, vp, bp, u64p, u32, u32, bp, bp, ci, mpp, u32pp, u64pp)),
+    "fz_batch_assign_cls": (ci, (vp, vp, bp, u64p, u32, u32, bp, bp, vpp)),
+    "fz_debug_multi_plan_cls": (ci, (bp, u64p, u32, u32, bp, bp, u32p, u32p, u32p, u32p)),
+    "fz_debug_batch_segment": (ci, (u64p, u64, u64, u64p, u64p, u64p)),
+    "fz_batch_upload_records": (ci, (vp, bp, u64, u32, u32, u32, vpp, rip)),
+    "fz_batch_tables": (ci, (vp, vp, vp)),
+    "fz_debug_batch_bytes": (ci, (vp, vp, u64)),
+    "fz_debug_records_split": (ci, (bp, u64, u32, u32, u32, vpp, vpp, vpp, rip)),
+    "fz_debug_scan_items": (u32, ()),
+    "fz_debug_records_ms": (ci, (vp, f64p)),
+    "fz_batch_upload_fasta": (ci, (vp, bp, u64, u32, vpp, rip)),
+    "fz_batch_fasta_index": (ci, (vp, vp)),
+    "fz_debug_fasta_split": (ci, (bp, u64, u32, vpp, vpp, vpp, rip)),
+    "fz_debug_fasta_upper4": (u32, (u32,)),
+    "fz_debug_fasta_src": (u64, (u64, u64, u64, u64)),
+    "fz_batch_derive": (ci, (vp, vp, vp, vp, vp, u64, u32, bp, vpp, dip)),
+    "fz_debug_derive_plan": (ci, (vp, u64, vp, vp, vp, u64, vp, vp, dip)),
+    "fz_debug_derive_ms": (ci, (vp, f64p)),
+    "fz_subs_ngrams_any": _ANY,
+    "fz_subs_lp_any": _ANY,
+    "fz_generic_ngrams_any": (ci, (vp, vp, bp, u32, u32, u32, u32, u32, cip)),
+    "fz_lev_lp": _SEARCH,
+    "fz_subs_lp": _SEARCH,
+    "fz_generic_lp": _GENERIC,
+    "fz_comm_unique_id": (ci, (vp, u64)),
+    "fz_comm_init_rank": (ci, (vp, vp, ci, ci)),
+    "fz_comm_init_all": (ci, (vp,)),
+    "fz_comm_info": (ci, (vp, cip, cip, cip)),
+    "fz_comm_set_collective": (ci, (vp, ci)),
+    "fz_comm_allgather": (ci, (vp, vp, u64, vp)),
+    "fz_comm_max_f64": (ci, (vp, f64p)),
+    "fz_comm_barrier": (ci, (vp,)),
+    "fz_comm_destroy": (None, (vp,)),
+    "fz_comm_gather_ms": (ci, (vp, f64p)),
+    "fz_comm_backend": (ci, ()),
+    "fz_consolidate": _REDUCE,
+    "fz_group_best": _REDUCE,
+    "fz_merge_ranks": (ci, (vp, vp, vp, u32, u32, vp)),
+    "fz_wire_pack": (ci, (vp, u64, u64, vp)),
+    "fz_wire_merge": (ci, (vp, u32, u64, u64, vp, u64, u64p, u64p)),
+    "fz_stream_open": (ci, (vp, u32, bp, u32, u32, u32, u32, u32, u64, u32, u32, u64, vpp)),
+    "fz_stream_buffer": (ci, (vp, vpp, u64p)),
+    "fz_stream_submit": (ci, (vp, u64, ci)),
+    "fz_stream_read_fd": (ci, (vp, ci, i64, ci, u64p)),
+    "fz_stream_finish": (ci, (vp, mpp, u32pp, u64p)),
+    "fz_stream_close": (None, (vp,)),
+    "fz_debug_reload_switches": (None, ()),
+    "fz_debug_launch_plan": (ci, (bp, u32, u32, u32p, u32, u32p)),
+    "fz_debug_order_records": (ci, (vp, u64, u32, mpp, u64p)),
+    "fz_debug_order_records_bounded": (ci, (vp, u64, u32, u64, u32, mpp, u64p)),
+    "fz_debug_order_segments": (ci, (vp, vp, u32, u32, mpp, u64p)),
+    "fz_debug_scan_regions": (ci, (u64, u64, u32, ci, f64, ci, u32p, vp)),
+    "fz_debug_scan_plan": (ci, (cs, u32, u32, u64, u32, ci, u32p, u32p, cip, u32p, vp)),
+    "fz_debug_gather_merge": (ci, (vp, u32, u64, vp, u32, mpp, u64p, u64p)),
+    "fz_stats": (ci, (vp, stp)),
+    "fz_mem_info": (ci, (vp, u64p, u64p)),
+    "fz_set_timing": (ci, (vp, ci)),
+    "fz_set_streams": (ci, (vp, ci)),
+    "fz_device_ms": (ci, (vp, f64p, ci)),
+    "fz_free": (None, (vp,)),
+}
+EXPORTED_SYMBOLS = tuple(PROTOTYPES)
+
+# Entry points that may be missing: a build of an earlier state of the library, named by FUZZYSEARCH_HIP_LIB for an A/B
+# run, lacks them.  load_library() passes over an absent one and _entry() refuses the call that needs it; every other
+# symbol is mandatory at load time.
+OPTIONAL = frozenset((
+    "fz_batch_search_multi", "fz_batch_assign", "fz_debug_assign_fold",
+    "fz_subs_ngrams_multi_cls", "fz_subs_ngrams_multi_best_cls", "fz_batch_search_multi_cls", "fz_batch_assign_cls",
+    "fz_debug_multi_plan_cls",
+    "fz_batch_upload_records", "fz_batch_tables", "fz_debug_batch_bytes", "fz_debug_records_split", "fz_debug_scan_items",
+    "fz_debug_records_ms",
+    "fz_batch_upload_fasta", "fz_batch_fasta_index", "fz_debug_fasta_split", "fz_debug_fasta_upper4", "fz_debug_fasta_src",
+    "fz_batch_derive", "fz_debug_derive_plan", "fz_debug_derive_ms",
+    "fz_debug_scan_plan", "fz_mem_info",
+))
+
 _lib = None
 _lib_lock = threading.Lock()
 
 
 def load_library():
-    """Load libfzhip.so and declare the C-ABI.  Raises HipEngineError if it is not built."""
+    """Load libfzhip.so and declare the C-ABI (PROTOTYPES).  Raises HipEngineError if it is not built."""
     global _lib
     with _lib_lock:
         if _lib is not None:
@@ -91,211 +198,11 @@ def load_library():
                 "fuzzysearch_amd: %s is missing. Build it with `python -m fuzzysearch_amd.build` "
                 "(hipcc, --offload-arch=gfx950). There is no CPU fallback." % LIB_PATH)
         L = ctypes.CDLL(LIB_PATH)
-        vp, u8p = ctypes.c_void_p, ctypes.c_void_p
-        u32, u64, ci = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int
-        mpp = ctypes.POINTER(ctypes.POINTER(FzMatch))
-        u64p = ctypes.POINTER(u64)
-        L.fz_abi_version.restype = ci
-        L.fz_abi_version.argtypes = []
-        L.fz_last_error.restype = ctypes.c_char_p
-        L.fz_last_error.argtypes = []
-        L.fz_device_count.restype = ci
-        L.fz_device_count.argtypes = [ctypes.POINTER(ci)]
-        L.fz_create.restype = ci
-        L.fz_create.argtypes = [ctypes.POINTER(ci), ci, ctypes.POINTER(vp)]
-        L.fz_destroy.restype = None
-        L.fz_destroy.argtypes = [vp]
-        L.fz_seq_upload.restype = ci
-        L.fz_seq_upload.argtypes = [vp, u8p, u64, ctypes.POINTER(vp)]
-        L.fz_seq_upload_shard.restype = ci
-        L.fz_seq_upload_shard.argtypes = [vp, u8p, u64, u64, u64, u64, u64, ctypes.POINTER(vp)]
-        L.fz_seq_new.restype = ci
-        L.fz_seq_new.argtypes = [vp, u64, ctypes.POINTER(vp)]
-        L.fz_seq_add_shard.restype = ci
-        L.fz_seq_add_shard.argtypes = [vp, ci, u8p, u64, u64, u64, u64]
-        L.fz_device_ms.restype = ci
-        L.fz_device_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ci]
-        L.fz_comm_unique_id.restype = ci
-        L.fz_comm_unique_id.argtypes = [vp, u64]
-        L.fz_comm_init_rank.restype = ci
-        L.fz_comm_init_rank.argtypes = [vp, vp, ci, ci]
-        L.fz_comm_init_all.restype = ci
-        L.fz_comm_init_all.argtypes = [vp]
-        L.fz_comm_info.restype = ci
-        L.fz_comm_info.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci)]
-        L.fz_comm_set_collective.restype = ci
-        L.fz_comm_set_collective.argtypes = [vp, ci]
-        L.fz_comm_allgather.restype = ci
-        L.fz_comm_allgather.argtypes = [vp, vp, u64, vp]
-        L.fz_comm_max_f64.restype = ci
-        L.fz_comm_max_f64.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
-        L.fz_comm_barrier.restype = ci
-        L.fz_comm_barrier.argtypes = [vp]
-        L.fz_comm_destroy.restype = None
-        L.fz_comm_destroy.argtypes = [vp]
-        L.fz_debug_reload_switches.restype = None
-        L.fz_debug_reload_switches.argtypes = []
-        L.fz_comm_backend.restype = ci
-        L.fz_comm_backend.argtypes = []
-        L.fz_comm_gather_ms.restype = ci
-        L.fz_comm_gather_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
-        L.fz_debug_scan_regions.restype = ci
-        L.fz_debug_scan_regions.argtypes = [u64, u64, u32, ci, ctypes.c_double, ci, ctypes.POINTER(u32), ctypes.c_void_p]
-        if hasattr(L, "fz_debug_scan_plan"):
-            L.fz_debug_scan_plan.restype = ci
-            L.fz_debug_scan_plan.argtypes = [ctypes.c_char_p, u32, u32, u64, u32, ci, ctypes.POINTER(u32), ctypes.POINTER(u32),
-                                             ctypes.POINTER(ci), ctypes.POINTER(u32), ctypes.c_void_p]
-        L.fz_debug_gather_merge.restype = ci
-        L.fz_debug_gather_merge.argtypes = [ctypes.c_void_p, u32, u64, ctypes.c_void_p, u32, mpp, u64p, u64p]
-        L.fz_seq_len.restype = u64
-        L.fz_seq_len.argtypes = [vp]
-        L.fz_seq_release.restype = None
-        L.fz_seq_release.argtypes = [vp]
-        L.fz_search_exact.restype = ci
-        L.fz_search_exact.argtypes = [vp, vp, u8p, u32, u64, u64, ctypes.POINTER(u64p), u64p]
-        L.fz_lev_ngrams.restype = ci
-        L.fz_lev_ngrams.argtypes = [vp, vp, u8p, u32, u32, mpp, u64p]
-        L.fz_lev_ngrams_begin.restype = ci
-        L.fz_lev_ngrams_begin.argtypes = [vp, vp, u8p, u32, u32]
-        L.fz_lev_ngrams_end.restype = ci
-        L.fz_lev_ngrams_end.argtypes = [vp, mpp, u64p]
-        L.fz_search_end.restype = ci
-        L.fz_search_end.argtypes = [vp, mpp, u64p]
-        L.fz_subs_ngrams_begin.restype = ci
-        L.fz_subs_ngrams_begin.argtypes = [vp, vp, u8p, u32, u32]
-        L.fz_generic_ngrams_begin.restype = ci
-        L.fz_generic_ngrams_begin.argtypes = [vp, vp, u8p, u32, u32, u32, u32, u32, ci]
-        L.fz_subs_ngrams.restype = ci
-        L.fz_subs_ngrams.argtypes = [vp, vp, u8p, u32, u32, mpp, u64p]
-        L.fz_generic_ngrams.restype = ci
-        L.fz_generic_ngrams.argtypes = [vp, vp, u8p, u32, u32, u32, u32, u32, mpp, u64p]
-        L.fz_lev_lp.restype = ci
-        L.fz_lev_lp.argtypes = [vp, vp, u8p, u32, u32, mpp, u64p]
-        L.fz_subs_lp.restype = ci
-        L.fz_subs_lp.argtypes = [vp, vp, u8p, u32, u32, mpp, u64p]
-        L.fz_generic_lp.restype = ci
-        L.fz_generic_lp.argtypes = [vp, vp, u8p, u32, u32, u32, u32, u32, mpp, u64p]
-        L.fz_lev_ngrams_consolidated.restype = ci
-        L.fz_lev_ngrams_consolidated.argtypes = [vp, vp, u8p, u32, u32, mpp, u64p]
-        for fn in (L.fz_lev_ngrams_multi, L.fz_lev_ngrams_multi_consolidated, L.fz_subs_ngrams_multi, L.fz_subs_ngrams_multi_best):
-            fn.restype = ci
-            fn.argtypes = [vp, vp, u8p, u64p, u32, u32, mpp, ctypes.POINTER(u64p)]
-        L.fz_debug_multi_plan.restype = ci
-        L.fz_debug_multi_plan.argtypes = [u8p, u64p, u32, u32, ctypes.POINTER(u32), ctypes.POINTER(u32)]
-        L.fz_debug_multi_plan_mode.restype = ci
-        L.fz_debug_multi_plan_mode.argtypes = [u32, u8p, u64p, u32, u32, ctypes.POINTER(u32), ctypes.POINTER(u32)]
-        L.fz_batch_upload.restype = ci
-        L.fz_batch_upload.argtypes = [vp, u8p, u64p, u64, ctypes.POINTER(vp)]
-        L.fz_batch_search.restype = ci
-        L.fz_batch_search.argtypes = [vp, vp, u32, u8p, u32, u32, ci, mpp, ctypes.POINTER(ctypes.POINTER(u32)), u64p]
-        if hasattr(L, "fz_batch_search_multi"):             # (absent from builds of earlier rounds named by FUZZYSEARCH_HIP_LIB for an A/B)
-            L.fz_batch_search_multi.restype = ci
-            L.fz_batch_search_multi.argtypes = [vp, vp, u32, u8p, u64p, u32, u32, ci, mpp, ctypes.POINTER(ctypes.POINTER(u32)),
-                                                ctypes.POINTER(u64p)]
-        if hasattr(L, "fz_batch_assign"):                   # (absent from builds of earlier rounds named by FUZZYSEARCH_HIP_LIB for an A/B)
-            L.fz_batch_assign.restype = ci
-            L.fz_batch_assign.argtypes = [vp, vp, u32, u8p, u64p, u32, u32, ctypes.POINTER(vp)]
-            L.fz_debug_assign_fold.restype = ci
-            L.fz_debug_assign_fold.argtypes = [vp, u64, vp, u64, u32, vp, u32, vp, u32, u32, vp]
-        L.fz_debug_batch_segment.restype = ci
-        L.fz_debug_batch_segment.argtypes = [u64p, u64, u64, u64p, u64p, u64p]
-        if hasattr(L, "fz_batch_upload_records"):           # (absent from builds of earlier rounds named by FUZZYSEARCH_HIP_LIB for an A/B)
-            rip = ctypes.POINTER(FzRecordsInfo)
-            L.fz_batch_upload_records.restype = ci
-            L.fz_batch_upload_records.argtypes = [vp, vp, u64, u32, u32, u32, ctypes.POINTER(vp), rip]
-            L.fz_batch_tables.restype = ci
-            L.fz_batch_tables.argtypes = [vp, vp, vp]
-            L.fz_debug_batch_bytes.restype = ci
-            L.fz_debug_batch_bytes.argtypes = [vp, vp, u64]
-            L.fz_debug_records_split.restype = ci
-            L.fz_debug_records_split.argtypes = [vp, u64, u32, u32, u32, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), rip]
-            L.fz_debug_scan_items.restype = u32
-            L.fz_debug_scan_items.argtypes = []
-            L.fz_debug_records_ms.restype = ci
-            L.fz_debug_records_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
-        if hasattr(L, "fz_batch_derive"):
-            dip = ctypes.POINTER(FzDeriveInfo)
-            L.fz_batch_derive.restype = ci
-            L.fz_batch_derive.argtypes = [vp, vp, vp, vp, vp, u64, u32, vp, ctypes.POINTER(vp), dip]
-            L.fz_debug_derive_plan.restype = ci
-            L.fz_debug_derive_plan.argtypes = [vp, u64, vp, vp, vp, u64, vp, vp, dip]
-            L.fz_debug_derive_ms.restype = ci
-            L.fz_debug_derive_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
-        if hasattr(L, "fz_batch_upload_fasta"):             # (absent from builds of earlier rounds named by FUZZYSEARCH_HIP_LIB for an A/B)
-            rip = ctypes.POINTER(FzRecordsInfo)
-            L.fz_batch_upload_fasta.restype = ci
-            L.fz_batch_upload_fasta.argtypes = [vp, vp, u64, u32, ctypes.POINTER(vp), rip]
-            L.fz_batch_fasta_index.restype = ci
-            L.fz_batch_fasta_index.argtypes = [vp, vp]
-            L.fz_debug_fasta_split.restype = ci
-            L.fz_debug_fasta_split.argtypes = [vp, u64, u32, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), rip]
-            L.fz_debug_fasta_upper4.restype = u32
-            L.fz_debug_fasta_upper4.argtypes = [u32]
-            L.fz_debug_fasta_src.restype = u64
-            L.fz_debug_fasta_src.argtypes = [u64, u64, u64, u64]
-        if hasattr(L, "fz_subs_ngrams_multi_cls"):          # (absent from builds of earlier rounds named by FUZZYSEARCH_HIP_LIB for an A/B)
-            for fn in (L.fz_subs_ngrams_multi_cls, L.fz_subs_ngrams_multi_best_cls):
-                fn.restype = ci
-                fn.argtypes = [vp, vp, u8p, u64p, u32, u32, u8p, u8p, mpp, ctypes.POINTER(u64p)]
-            L.fz_batch_search_multi_cls.restype = ci
-            L.fz_batch_search_multi_cls.argtypes = [vp, vp, u8p, u64p, u32, u32, u8p, u8p, ci, mpp, ctypes.POINTER(ctypes.POINTER(u32)),
-                                                    ctypes.POINTER(u64p)]
-            L.fz_batch_assign_cls.restype = ci
-            L.fz_batch_assign_cls.argtypes = [vp, vp, u8p, u64p, u32, u32, u8p, u8p, ctypes.POINTER(vp)]
-            L.fz_debug_multi_plan_cls.restype = ci
-            L.fz_debug_multi_plan_cls.argtypes = [u8p, u64p, u32, u32, u8p, u8p, ctypes.POINTER(u32), ctypes.POINTER(u32),
-                                                  ctypes.POINTER(u32), ctypes.POINTER(u32)]
-        L.fz_subs_ngrams_best.restype = ci
-        L.fz_subs_ngrams_best.argtypes = [vp, vp, u8p, u32, u32, mpp, u64p]
-        L.fz_generic_ngrams_consolidated.restype = ci
-        L.fz_generic_ngrams_consolidated.argtypes = [vp, vp, u8p, u32, u32, u32, u32, u32, mpp, u64p]
-        L.fz_subs_ngrams_any.restype = ci
-        L.fz_subs_ngrams_any.argtypes = [vp, vp, u8p, u32, u32, ctypes.POINTER(ci)]
-        L.fz_subs_lp_any.restype = ci
-        L.fz_subs_lp_any.argtypes = [vp, vp, u8p, u32, u32, ctypes.POINTER(ci)]
-        L.fz_generic_ngrams_any.restype = ci
-        L.fz_generic_ngrams_any.argtypes = [vp, vp, u8p, u32, u32, u32, u32, u32, ctypes.POINTER(ci)]
-        L.fz_stream_open.restype = ci
-        L.fz_stream_open.argtypes = [vp, u32, u8p, u32, u32, u32, u32, u32, u64, u32, u32, u64, ctypes.POINTER(vp)]
-        L.fz_stream_buffer.restype = ci
-        L.fz_stream_buffer.argtypes = [vp, ctypes.POINTER(vp), u64p]
-        L.fz_stream_submit.restype = ci
-        L.fz_stream_submit.argtypes = [vp, u64, ci]
-        L.fz_stream_read_fd.restype = ci
-        L.fz_stream_read_fd.argtypes = [vp, ci, ctypes.c_int64, ci, u64p]
-        L.fz_stream_finish.restype = ci
-        L.fz_stream_finish.argtypes = [vp, mpp, ctypes.POINTER(ctypes.POINTER(u32)), u64p]
-        L.fz_stream_close.restype = None
-        L.fz_stream_close.argtypes = [vp]
-        L.fz_consolidate.restype = ci
-        L.fz_consolidate.argtypes = [ctypes.POINTER(FzMatch), u64, mpp, u64p]
-        L.fz_group_best.restype = ci
-        L.fz_group_best.argtypes = [ctypes.POINTER(FzMatch), u64, mpp, u64p]
-        L.fz_wire_pack.restype = ci
-        L.fz_wire_pack.argtypes = [ctypes.c_void_p, u64, u64, ctypes.c_void_p]
-        L.fz_wire_merge.restype = ci
-        L.fz_wire_merge.argtypes = [ctypes.c_void_p, u32, u64, u64, ctypes.c_void_p, u64, u64p, u64p]
-        L.fz_debug_launch_plan.restype = ci
-        L.fz_debug_launch_plan.argtypes = [u8p, u32, u32, ctypes.POINTER(u32), u32, ctypes.POINTER(u32)]
-        L.fz_debug_order_records.restype = ci
-        L.fz_debug_order_records.argtypes = [ctypes.c_void_p, u64, u32, mpp, u64p]
-        L.fz_debug_order_records_bounded.restype = ci
-        L.fz_debug_order_records_bounded.argtypes = [ctypes.c_void_p, u64, u32, u64, u32, mpp, u64p]
-        L.fz_debug_order_segments.restype = ci
-        L.fz_debug_order_segments.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u32, u32, mpp, u64p]
-        L.fz_merge_ranks.restype = ci
-        L.fz_merge_ranks.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, u32, u32, ctypes.c_void_p]
-        L.fz_stats.restype = ci
-        L.fz_stats.argtypes = [vp, ctypes.POINTER(FzStats)]
-        if hasattr(L, "fz_mem_info"):                       # (absent from builds of earlier rounds named by FUZZYSEARCH_HIP_LIB for an A/B)
-            L.fz_mem_info.restype = ci
-            L.fz_mem_info.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
-        L.fz_set_timing.restype = ci
-        L.fz_set_timing.argtypes = [vp, ci]
-        L.fz_set_streams.restype = ci
-        L.fz_set_streams.argtypes = [vp, ci]
-        L.fz_free.restype = None
-        L.fz_free.argtypes = [vp]
+        for name, (restype, argtypes) in PROTOTYPES.items():
+            if name in OPTIONAL and not hasattr(L, name):
+                continue
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         if L.fz_abi_version() != 1:
             raise HipEngineError("libfzhip.so ABI version mismatch")
         _lib = L
@@ -308,6 +215,14 @@ class UnsupportedSearch(NotImplementedError):
     more than 255 distinct symbols in a subsequence that is neither bytes nor latin-1 text, automaton candidate sets
     beyond 2^18 entries.  Nothing was searched and there is no CPU fallback: a caller that needs such a search
     catches this and routes it to the reference implementation."""
+
+
+def _entry(lib, name):
+    """Entry point `name` of the loaded library.  A build without it (OPTIONAL) cannot make the call: there is no fallback."""
+    fn = getattr(lib, name, None)
+    if fn is None:
+        raise UnsupportedSearch("this libfzhip.so has no %s: it was built before that entry point existed" % name)
+    return fn
 
 
 def _raise(rc):
@@ -402,48 +317,75 @@ class _ResultBuffer(object):
                 pass
 
 
-def _take_matches_array(L, ptr, n):
-    """-> numpy structured array (start, end, dist, block).  Small results: one memcpy, then the C buffer is
-    freed.  Large ones (>= 256 KiB: e.g. the 2.1e5 rows of a generic search over 1 GiB of text) are viewed in
-    place — no second 5 MB buffer to fault in and fill — and handed back to the library (which recycles such
-    buffers) when the last view dies."""
+def _take_rows(lib, addr, n, dtype=None):
+    """A result buffer of the library (its address or a ctypes pointer; n rows of `dtype`, None: fz_match rows) -> numpy
+    structured array.  Small results: one memcpy, then the C buffer is freed.  Large ones (>= 256 KiB: e.g. the 2.1e5 rows
+    of a generic search over 1 GiB of text) are viewed in place — no second 5 MB buffer to fault in and fill — and handed
+    back to the library (which recycles such buffers) when the last view dies."""
     import numpy as np
-    nbytes = n * ctypes.sizeof(FzMatch)
+    if dtype is None:
+        dtype = _match_dtype()
+    nbytes = n * dtype.itemsize
     if nbytes >= (256 << 10):
-        addr = ctypes.cast(ptr, ctypes.c_void_p).value
+        addr = ctypes.cast(addr, ctypes.c_void_p).value
         raw = (ctypes.c_char * nbytes).from_address(addr)
-        raw._owner = _ResultBuffer(L, addr)                     # lives as long as the ctypes view numpy holds on to
-        return np.frombuffer(raw, dtype=_match_dtype(), count=n)
-    arr = np.empty(n, dtype=_match_dtype())
+        raw._owner = _ResultBuffer(lib, addr)                   # lives as long as the ctypes view numpy holds on to
+        return np.frombuffer(raw, dtype=dtype, count=n)
+    arr = np.empty(n, dtype=dtype)
     if n:
-        ctypes.memmove(arr.ctypes.data, ptr, nbytes)
-    L.fz_free(ptr)
+        ctypes.memmove(arr.ctypes.data, addr, nbytes)
+    lib.fz_free(addr)
     return arr
 
 
+def _take_matches_array(L, ptr, n):
+    """-> numpy structured array (start, end, dist, block) over or from the library's buffer (_take_rows)."""
+    return _take_rows(L, ptr, n)
+
+
 def _take_matches(L, ptr, n):
-    return _take_matches_array(L, ptr, n).tolist()
+    return _take_rows(L, ptr, n).tolist()
 
 
-def _array_call(fn, raw):
+def _take_copy(lib, ptr, n, dtype):
+    """The library's buffer of n plain items -> a numpy array of its own; the buffer is freed."""
+    import numpy as np
+    arr = np.empty(n, dtype=dtype)
+    if n:
+        ctypes.memmove(arr.ctypes.data, ptr, n * arr.itemsize)
+    lib.fz_free(ptr)
+    return arr
+
+
+def _take_bounds(lib, optr, n_pats):
+    """The library's per-pattern row offsets (n_pats + 1 entries) -> a list; the buffer is freed."""
+    bounds = optr[:n_pats + 1]
+    lib.fz_free(optr)
+    return bounds
+
+
+def _struct_dict(s):
+    return {name: getattr(s, name) for name, _ in s._fields_}
+
+
+def _array_call(name, raw):
     L = load_library()
     arr, n = matches_to_array(raw)
-    ptr = ctypes.POINTER(FzMatch)()
-    cnt = ctypes.c_uint64(0)
-    _check(fn(L)(ctypes.cast(arr.ctypes.data, ctypes.POINTER(FzMatch)), n, ctypes.byref(ptr), ctypes.byref(cnt)))
-    return _take_matches_array(L, ptr, cnt.value)
+    ptr, cnt = mp(), u64(0)
+    _check(getattr(L, name)(ctypes.cast(arr.ctypes.data, mp), n, ctypes.byref(ptr), ctypes.byref(cnt)))
+    return _take_rows(L, ptr, cnt.value)
 
 
 def consolidate_array(raw):
     """consolidate_overlapping_matches (common.py:185-189) on an fz_match array (or rows) -> fz_match array;
     no per-record Python work."""
-    return _array_call(lambda L: L.fz_consolidate, raw)
+    return _array_call("fz_consolidate", raw)
 
 
 def group_best_array(raw):
     """[get_best_match_in_group(g) for g in group_matches(ms)] in group-list order
     (substitutions_only.py:279-282) on an fz_match array (or rows) -> fz_match array."""
-    return _array_call(lambda L: L.fz_group_best, raw)
+    return _array_call("fz_group_best", raw)
 
 
 def consolidate(raw):
@@ -482,26 +424,23 @@ def multi_plan(patterns, k, mode=MODE_LEV):
     return [None if group_of[i] == 0xffffffff else group_of[i] for i in range(n)], ng.value
 
 
-def _class_entry(L, name):
-    """The class form `name` of the loaded library; a build without it cannot search classes (there is no fallback)."""
-    fn = getattr(L, name, None)
-    if fn is None:
-        raise HipEngineError("this libfzhip.so has no %s: it was built before symbol classes" % name)
-    return fn
-
-
 def multi_plan_classes(patterns, k, tables):
     """fz_debug_multi_plan_cls (no device): -> (group of every pattern, table entries of every pattern, entries of every
     group) of a class call with tables = (pmask, tmask), two bytes objects of 256.  Raises what the class calls raise."""
     L = load_library()
     blob, offs = pack_patterns(patterns)
     n = len(patterns)
-    group_of = (ctypes.c_uint32 * max(1, n))()
-    per_pat = (ctypes.c_uint32 * max(1, n))()
-    per_group = (ctypes.c_uint32 * max(1, n))()
+    group_of, per_pat, per_group = ((ctypes.c_uint32 * max(1, n))() for _ in range(3))
     ng = ctypes.c_uint32(0)
-    _check(_class_entry(L, "fz_debug_multi_plan_cls")(blob, offs, n, k, tables[0], tables[1], group_of, ctypes.byref(ng), per_pat, per_group))
+    _check(_entry(L, "fz_debug_multi_plan_cls")(blob, offs, n, k, tables[0], tables[1], group_of, ctypes.byref(ng), per_pat, per_group))
     return list(group_of[:n]), list(per_pat[:n]), list(per_group[:ng.value])
+
+
+def _class_tables(mode, tables):
+    """-> (pmask, tmask) of a class call; the class entry points take no mode because they count mismatches only."""
+    if mode != MODE_SUBS:
+        raise ValueError("symbol classes are searched in substitutions mode (MODE_SUBS) only")
+    return tables[0], tables[1]
 
 
 def batch_segment(offs, idx):
@@ -509,7 +448,7 @@ def batch_segment(offs, idx):
     lie at offs[j] .. offs[j + 1].  `offs`: a C-contiguous numpy uint64 array (kept by the caller across calls)."""
     L = load_library()
     j, sa, se = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
-    _check(L.fz_debug_batch_segment(offs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), len(offs) - 1, idx,
+    _check(L.fz_debug_batch_segment(offs.ctypes.data_as(u64p), len(offs) - 1, idx,
                                     ctypes.byref(j), ctypes.byref(sa), ctypes.byref(se)))
     return j.value, sa.value, se.value
 
@@ -524,7 +463,7 @@ RECORD_FORMATS = {'fastq': (4, 1, REC_FASTQ_CHECKS), 'lines': (1, 0, 0)}
 
 def scan_items():
     """fz_debug_scan_items: the items one workgroup of the device's exclusive scan handles."""
-    return int(load_library().fz_debug_scan_items())
+    return int(_entry(load_library(), 'fz_debug_scan_items')())
 
 
 def records_split(text, lines_per_record, sequence_line, flags):
@@ -557,12 +496,12 @@ def fasta_split(text, flags=0):
 
 def fasta_upper4(w):
     """fz_debug_fasta_upper4: the gather's fold of four bytes (a 32-bit word)."""
-    return int(load_library().fz_debug_fasta_upper4(w))
+    return int(_entry(load_library(), 'fz_debug_fasta_upper4')(w))
 
 
 def fasta_src(offset, linebases, linewidth, q):
     """fz_debug_fasta_src: where base q of a record with that offset, linebases and linewidth lies in the text."""
-    return int(load_library().fz_debug_fasta_src(offset, linebases, linewidth, q))
+    return int(_entry(load_library(), 'fz_debug_fasta_src')(offset, linebases, linewidth, q))
 
 
 def _split_twin(entry, text, args, row_dtype):
@@ -573,9 +512,9 @@ def _split_twin(entry, text, args, row_dtype):
     addr, n, keep = _buffer_address(text)
     pr, pe, pp = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
     info = FzRecordsInfo()
-    rc = getattr(L, entry)(addr, n, *args, ctypes.byref(pr), ctypes.byref(pe), ctypes.byref(pp), ctypes.byref(info))
+    rc = _entry(L, entry)(addr, n, *args, ctypes.byref(pr), ctypes.byref(pe), ctypes.byref(pp), ctypes.byref(info))
     del keep
-    d = _records_info(info)
+    d = _struct_dict(info)
     if rc != FZ_OK:
         _raise_records(rc, d)
     ns = d['n_seqs']
@@ -587,11 +526,6 @@ def _split_twin(entry, text, args, row_dtype):
     return rows, ends, packed, d
 
 
-def _records_info(info):
-    return {'n_lines': int(info.n_lines), 'n_seqs': int(info.n_seqs), 'packed_bytes': int(info.packed_bytes),
-            'bad_record': int(info.bad_record), 'bad_reason': int(info.bad_reason)}
-
-
 def _raise_records(rc, info):
     try:
         _raise(rc)
@@ -601,11 +535,6 @@ def _raise_records(rc, info):
 
 
 DERIVE_REVERSE = 1                                # FZ_DERIVE_REVERSE
-
-
-def _derive_info(info):
-    return {'n_out': int(info.n_out), 'packed_bytes': int(info.packed_bytes), 'longest': int(info.longest),
-            'bad_item': int(info.bad_item), 'bad_reason': int(info.bad_reason)}
 
 
 def _raise_derive(rc, info):
@@ -639,10 +568,10 @@ def derive_plan(offs, index, starts, ends, n_out):
     src = np.zeros(n_out, dtype=np.uint64)
     at = np.zeros(n_out + 1, dtype=np.uint64)
     info = FzDeriveInfo()
-    rc = load_library().fz_debug_derive_plan(offs.ctypes.data, len(offs) - 1, addrs[0], addrs[1], addrs[2], n_out, src.ctypes.data,
-                                             at.ctypes.data, ctypes.byref(info))
+    rc = _entry(load_library(), 'fz_debug_derive_plan')(offs.ctypes.data, len(offs) - 1, addrs[0], addrs[1], addrs[2], n_out,
+                                                        src.ctypes.data, at.ctypes.data, ctypes.byref(info))
     del keep
-    d = _derive_info(info)
+    d = _struct_dict(info)
     if rc != FZ_OK:
         _raise_derive(rc, d)
     return src, at, d
@@ -658,19 +587,8 @@ def assign_dtype():
 
 
 def _take_assign_array(L, addr, n):
-    """-> numpy structured array of fz_assign rows: viewed in place over the library's buffer when large (handed back when
-    the last view dies), copied and freed when small — as _take_matches_array does for fz_match rows."""
-    import numpy as np
-    nbytes = n * assign_dtype().itemsize
-    if nbytes >= (256 << 10):
-        raw = (ctypes.c_char * nbytes).from_address(addr)
-        raw._owner = _ResultBuffer(L, addr)
-        return np.frombuffer(raw, dtype=assign_dtype(), count=n)
-    arr = np.empty(n, dtype=assign_dtype())
-    if n:
-        ctypes.memmove(arr.ctypes.data, addr, nbytes)
-    L.fz_free(ctypes.c_void_p(addr))
-    return arr
+    """-> numpy structured array of fz_assign rows over or from the library's buffer (_take_rows)."""
+    return _take_rows(L, addr, n, assign_dtype())
 
 
 def assign_fold(offs, recs, L, pat_table, pat_m, k):
@@ -686,8 +604,8 @@ def assign_fold(offs, recs, L, pat_table, pat_m, k):
     pat_table = np.ascontiguousarray(pat_table, dtype=np.uint32).reshape(-1, 2)
     pat_m = np.ascontiguousarray(pat_m, dtype=np.uint32)
     out = np.empty(len(offs) - 1, dtype=assign_dtype())
-    _check(lib.fz_debug_assign_fold(offs.ctypes.data, len(offs) - 1, recs.ctypes.data, len(recs), L, pat_table.ctypes.data,
-                                    len(pat_table), pat_m.ctypes.data, len(pat_m), k, out.ctypes.data))
+    _check(_entry(lib, 'fz_debug_assign_fold')(offs.ctypes.data, len(offs) - 1, recs.ctypes.data, len(recs), L, pat_table.ctypes.data,
+                                               len(pat_table), pat_m.ctypes.data, len(pat_m), k, out.ctypes.data))
     return out
 
 
@@ -755,18 +673,11 @@ class FileStream(object):
 
     def finish(self):
         """-> (fz_match structured array in the reference's order, uint32 chunk number per record)."""
-        import numpy as np
-        ptr = ctypes.POINTER(FzMatch)()
-        seg = ctypes.POINTER(ctypes.c_uint32)()
-        cnt = ctypes.c_uint64(0)
+        ptr, seg, cnt = mp(), u32p(), u64(0)
         with self.engine._lock:
             _check(self._lib.fz_stream_finish(self._h, ctypes.byref(ptr), ctypes.byref(seg), ctypes.byref(cnt)))
-        n = cnt.value
-        segs = np.empty(n, dtype=np.uint32)
-        if n:
-            ctypes.memmove(segs.ctypes.data, seg, 4 * n)
-        self._lib.fz_free(seg)
-        return _take_matches_array(self._lib, ptr, n), segs
+        segs = _take_copy(self._lib, seg, cnt.value, 'uint32')
+        return _take_matches_array(self._lib, ptr, cnt.value), segs
 
     def close(self):
         with self.engine._lock:                    # the engine may be closed (fz_destroy) by another thread: test under the lock
@@ -857,7 +768,7 @@ class Engine(object):
         addr, n, keep = _buffer_address(data)
         h = ctypes.c_void_p()
         with self._lock:
-            _check(self._lib.fz_batch_upload(self._h, addr, offs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+            _check(self._lib.fz_batch_upload(self._h, addr, offs.ctypes.data_as(u64p),
                                              len(offs) - 1, ctypes.byref(h)))
         del keep
         seq = ResidentSequence(self, h, n)
@@ -868,12 +779,12 @@ class Engine(object):
         """fz_batch_upload_records: `text` (bytes-like: a FASTQ file, a file of lines) is copied to the device once and split
         there into a batch -> a ResidentSequence like upload_batch's, with `.n_seqs` and `.info` (n_lines, n_seqs,
         packed_bytes).  A malformed text raises ValueError naming the record (`.info` on the exception: bad_record, bad_reason)."""
-        return self._upload_text(self._lib.fz_batch_upload_records, text, lines_per_record, sequence_line, flags)
+        return self._upload_text(_entry(self._lib, 'fz_batch_upload_records'), text, lines_per_record, sequence_line, flags)
 
     def upload_fasta(self, text, flags=0):
         """fz_batch_upload_fasta: `text` (bytes-like: a FASTA file) is copied to the device once and split there into a batch of
         its contigs -> a ResidentSequence like upload_records'.  A malformed text raises ValueError naming the record."""
-        return self._upload_text(self._lib.fz_batch_upload_fasta, text, flags)
+        return self._upload_text(_entry(self._lib, 'fz_batch_upload_fasta'), text, flags)
 
     def _upload_text(self, entry, text, *args):
         """entry(ctx, text, n, *args, &handle, &info) -> the batch handle with `.n_seqs` and `.info`; a refusal raises with
@@ -884,7 +795,7 @@ class Engine(object):
         with self._lock:
             rc = entry(self._h, addr, n, *args, ctypes.byref(h), ctypes.byref(info))
         del keep
-        d = _records_info(info)
+        d = _struct_dict(info)
         if rc != FZ_OK:
             _raise_records(rc, d)
         seq = ResidentSequence(self, h, d['packed_bytes'])
@@ -897,7 +808,7 @@ class Engine(object):
         import numpy as np
         rows = np.zeros(batch.n_seqs, dtype=fasta_dtype())
         with self._lock:
-            _check(self._lib.fz_batch_fasta_index(batch._h, rows.ctypes.data))
+            _check(_entry(self._lib, 'fz_batch_fasta_index')(batch._h, rows.ctypes.data))
         return rows
 
     def batch_tables(self, batch):
@@ -907,14 +818,14 @@ class Engine(object):
         starts = np.zeros(batch.n_seqs, dtype=np.uint64)
         ends = np.zeros(batch.n_seqs, dtype=np.uint64)
         with self._lock:
-            _check(self._lib.fz_batch_tables(batch._h, starts.ctypes.data, ends.ctypes.data))
+            _check(_entry(self._lib, 'fz_batch_tables')(batch._h, starts.ctypes.data, ends.ctypes.data))
         return starts, ends
 
     def batch_bytes(self, batch):
         """fz_debug_batch_bytes: the packed bytes of a batch handle, back from the device."""
         buf = ctypes.create_string_buffer(max(1, batch.nbytes))
         with self._lock:
-            _check(self._lib.fz_debug_batch_bytes(batch._h, buf, batch.nbytes))
+            _check(_entry(self._lib, 'fz_debug_batch_bytes')(batch._h, buf, batch.nbytes))
         return buf.raw[:batch.nbytes]
 
     def derive_batch(self, batch, index=None, starts=None, ends=None, n_out=None, reverse=False, translate=None):
@@ -935,10 +846,10 @@ class Engine(object):
         h = ctypes.c_void_p()
         info = FzDeriveInfo()
         with self._lock:
-            rc = self._lib.fz_batch_derive(self._h, batch._h, addrs[0], addrs[1], addrs[2], n_out, DERIVE_REVERSE if reverse else 0,
-                                           taddr, ctypes.byref(h), ctypes.byref(info))
+            rc = _entry(self._lib, 'fz_batch_derive')(self._h, batch._h, addrs[0], addrs[1], addrs[2], n_out,
+                                                      DERIVE_REVERSE if reverse else 0, taddr, ctypes.byref(h), ctypes.byref(info))
         del keep
-        d = _derive_info(info)
+        d = _struct_dict(info)
         if rc != FZ_OK:
             _raise_derive(rc, d)
         seq = ResidentSequence(self, h, d['packed_bytes'])
@@ -950,118 +861,91 @@ class Engine(object):
         """fz_debug_derive_ms: {tables_h2d, measure_scan, gather, ends_d2h, call} milliseconds of this engine's last derive_batch."""
         ms = (ctypes.c_double * 5)()
         with self._lock:
-            _check(self._lib.fz_debug_derive_ms(self._h, ms))
+            _check(_entry(self._lib, 'fz_debug_derive_ms')(self._h, ms))
         return {'tables_h2d': ms[0], 'measure_scan': ms[1], 'gather': ms[2], 'ends_d2h': ms[3], 'call': ms[4]}
 
     def records_ms(self):
         """fz_debug_records_ms: {h2d, kernels, ends_d2h, call} milliseconds of this engine's last upload_records / upload_fasta."""
         ms = (ctypes.c_double * 4)()
         with self._lock:
-            _check(self._lib.fz_debug_records_ms(self._h, ms))
+            _check(_entry(self._lib, 'fz_debug_records_ms')(self._h, ms))
         return {'h2d': ms[0], 'kernels': ms[1], 'ends_d2h': ms[2], 'call': ms[3]}
 
     def _batch_call(self, batch, mode, pattern, k, reduced):
-        if type(pattern) is bytes:
-            paddr, m, keep = pattern, len(pattern), None
-        else:
-            paddr, m, keep = _buffer_address(pattern)
-        ptr = ctypes.POINTER(FzMatch)()
-        sptr = ctypes.POINTER(ctypes.c_uint32)()
-        cnt = ctypes.c_uint64(0)
+        paddr, m, keep = (pattern, len(pattern), None) if type(pattern) is bytes else _buffer_address(pattern)
+        ptr, sptr, cnt = mp(), u32p(), u64(0)
         with self._lock:
             _check(self._lib.fz_batch_search(self._h, batch._h, mode, paddr, m, k, 1 if reduced else 0,
                                              ctypes.byref(ptr), ctypes.byref(sptr), ctypes.byref(cnt)))
-        return ptr, sptr, cnt.value
-
-    def _take_seq_of(self, sptr, n):
-        """The library's seq_of buffer of n rows -> a uint32 array of its own; the buffer is freed."""
-        import numpy as np
-        seq_of = np.empty(n, dtype=np.uint32)
-        if n:
-            ctypes.memmove(seq_of.ctypes.data, sptr, 4 * n)
-        self._lib.fz_free(sptr)
-        return seq_of
+        return ptr, _take_copy(self._lib, sptr, cnt.value, 'uint32'), cnt.value
 
     def batch_search(self, batch, mode, pattern, k, reduced=False):
         """fz_batch_search -> (rows, seq_of): an fz_match structured array in the local coordinates of the rows' sequences,
         ordered by sequence, and the uint32 array of their sequence numbers."""
-        ptr, sptr, n = self._batch_call(batch, mode, pattern, k, reduced)
-        return _take_matches_array(self._lib, ptr, n), self._take_seq_of(sptr, n)
+        ptr, seq_of, n = self._batch_call(batch, mode, pattern, k, reduced)
+        return _take_matches_array(self._lib, ptr, n), seq_of
 
     def batch_rows_call(self, batch, mode, pattern, k, reduced=True):
         """The same as (OwnedRows, seq_of array), for callers that build Match objects in C straight from the result buffer."""
-        ptr, sptr, n = self._batch_call(batch, mode, pattern, k, reduced)
-        return OwnedRows(self._lib, ptr, n), self._take_seq_of(sptr, n)
+        ptr, seq_of, n = self._batch_call(batch, mode, pattern, k, reduced)
+        return OwnedRows(self._lib, ptr, n), seq_of
 
-    def _batch_multi_call(self, batch, mode, patterns, k, reduced):
-        """-> (rows pointer, seq_of array, per-pattern row offsets) of one fz_batch_search_multi call; the caller owns the pointer."""
+    def _batch_multi_call(self, batch, mode, patterns, k, reduced, tables=None):
+        """-> (rows pointer, seq_of array, per-pattern row offsets) of one fz_batch_search_multi call; the caller owns the pointer.
+        tables = (pmask, tmask): fz_batch_search_multi_cls, which has no mode and takes the masks in front of `reduced`."""
         blob, offs = pack_patterns(patterns)
-        ptr = ctypes.POINTER(FzMatch)()
-        sptr = ctypes.POINTER(ctypes.c_uint32)()
-        optr = ctypes.POINTER(ctypes.c_uint64)()
+        n, red = len(patterns), 1 if reduced else 0
+        if tables is None:
+            fn, args = _entry(self._lib, "fz_batch_search_multi"), (mode, blob, offs, n, k, red)
+        else:
+            pmask, tmask = _class_tables(mode, tables)
+            fn, args = _entry(self._lib, "fz_batch_search_multi_cls"), (blob, offs, n, k, pmask, tmask, red)
+        ptr, sptr, optr = mp(), u32p(), u64p()
         with self._lock:
-            _check(self._lib.fz_batch_search_multi(self._h, batch._h, mode, blob, offs, len(patterns), k, 1 if reduced else 0,
-                                                   ctypes.byref(ptr), ctypes.byref(sptr), ctypes.byref(optr)))
-        bounds = optr[:len(patterns) + 1]
-        self._lib.fz_free(optr)
-        return ptr, self._take_seq_of(sptr, bounds[-1]), bounds
+            _check(fn(self._h, batch._h, *args, ctypes.byref(ptr), ctypes.byref(sptr), ctypes.byref(optr)))
+        bounds = _take_bounds(self._lib, optr, n)
+        return ptr, _take_copy(self._lib, sptr, bounds[-1], 'uint32'), bounds
 
-    def batch_search_multi(self, batch, mode, patterns, k, reduced=False):
+    def batch_search_multi(self, batch, mode, patterns, k, reduced=False, tables=None):
         """[batch_search(batch, mode, p, k, reduced) for p in patterns] in as few passes over the batch as the patterns
-        allow (fz_batch_search_multi): a list of (rows, seq_of) per pattern."""
+        allow (fz_batch_search_multi; with tables, under the class distance): a list of (rows, seq_of) per pattern."""
         patterns = list(patterns)
-        ptr, seq_of, bounds = self._batch_multi_call(batch, mode, patterns, k, reduced)
+        ptr, seq_of, bounds = self._batch_multi_call(batch, mode, patterns, k, reduced, tables)
         rows = _take_matches_array(self._lib, ptr, bounds[-1])
         return [(rows[bounds[i]:bounds[i + 1]], seq_of[bounds[i]:bounds[i + 1]]) for i in range(len(patterns))]
 
-    def batch_multi_rows_call(self, batch, mode, patterns, k, reduced=True):
+    def batch_multi_rows_call(self, batch, mode, patterns, k, reduced=True, tables=None):
         """The same as (OwnedRows of all patterns' rows, seq_of array, row offsets per pattern), for callers that build Match
         objects in C straight from the result buffer: P x S lists are not a form for millions of reads."""
         patterns = list(patterns)
-        ptr, seq_of, bounds = self._batch_multi_call(batch, mode, patterns, k, reduced)
+        ptr, seq_of, bounds = self._batch_multi_call(batch, mode, patterns, k, reduced, tables)
         return OwnedRows(self._lib, ptr, bounds[-1]), seq_of, bounds
 
-    def batch_multi_rows_call_classes(self, batch, patterns, k, tables, reduced=True):
-        """batch_multi_rows_call in substitutions mode with symbol classes (fz_batch_search_multi_cls); tables = (pmask, tmask)."""
+    def batch_assign(self, batch, mode, patterns, k, tables=None):
+        """fz_batch_assign: the best pattern of the list per sequence of the batch -> a structured array (assign_dtype) of
+        one row per sequence over the library's buffer: pattern (-1: none), dist, tied, start, end (local coordinates).
+        tables = (pmask, tmask): fz_batch_assign_cls, the same under the class distance; it has no mode."""
         patterns = list(patterns)
-        fn = _class_entry(self._lib, "fz_batch_search_multi_cls")
         blob, offs = pack_patterns(patterns)
-        ptr = ctypes.POINTER(FzMatch)()
-        sptr = ctypes.POINTER(ctypes.c_uint32)()
-        optr = ctypes.POINTER(ctypes.c_uint64)()
+        if tables is None:
+            fn, args = _entry(self._lib, "fz_batch_assign"), (mode, blob, offs, len(patterns), k)
+        else:
+            pmask, tmask = _class_tables(mode, tables)
+            fn, args = _entry(self._lib, "fz_batch_assign_cls"), (blob, offs, len(patterns), k, pmask, tmask)
+        ptr = ctypes.c_void_p()
         with self._lock:
-            _check(fn(self._h, batch._h, blob, offs, len(patterns), k, tables[0], tables[1], 1 if reduced else 0,
-                      ctypes.byref(ptr), ctypes.byref(sptr), ctypes.byref(optr)))
-        bounds = optr[:len(patterns) + 1]
-        self._lib.fz_free(optr)
-        return OwnedRows(self._lib, ptr, bounds[-1]), self._take_seq_of(sptr, bounds[-1]), bounds
+            _check(fn(self._h, batch._h, *args, ctypes.byref(ptr)))
+        return _take_assign_array(self._lib, ptr.value, batch.n_seqs)     # (a plain handle was refused above)
+
+    # the class calls by their names of old: substitutions mode, tables = (pmask, tmask) of classes.class_tables
+    def batch_multi_rows_call_classes(self, batch, patterns, k, tables, reduced=True):
+        return self.batch_multi_rows_call(batch, MODE_SUBS, patterns, k, reduced, tables)
 
     def batch_search_multi_classes(self, batch, patterns, k, tables, reduced=False):
-        """The same as a list of (rows, seq_of) arrays per pattern."""
-        patterns = list(patterns)
-        rows, seq_of, bounds = self.batch_multi_rows_call_classes(batch, patterns, k, tables, reduced)
-        arr = rows.to_array()
-        return [(arr[bounds[i]:bounds[i + 1]], seq_of[bounds[i]:bounds[i + 1]]) for i in range(len(patterns))]
+        return self.batch_search_multi(batch, MODE_SUBS, patterns, k, reduced, tables)
 
     def batch_assign_classes(self, batch, patterns, k, tables):
-        """batch_assign in substitutions mode with symbol classes (fz_batch_assign_cls)."""
-        patterns = list(patterns)
-        fn = _class_entry(self._lib, "fz_batch_assign_cls")
-        blob, offs = pack_patterns(patterns)
-        ptr = ctypes.c_void_p()
-        with self._lock:
-            _check(fn(self._h, batch._h, blob, offs, len(patterns), k, tables[0], tables[1], ctypes.byref(ptr)))
-        return _take_assign_array(self._lib, ptr.value, batch.n_seqs)
-
-    def batch_assign(self, batch, mode, patterns, k):
-        """fz_batch_assign: the best pattern of the list per sequence of the batch -> a structured array (assign_dtype) of
-        one row per sequence over the library's buffer: pattern (-1: none), dist, tied, start, end (local coordinates)."""
-        patterns = list(patterns)
-        blob, offs = pack_patterns(patterns)
-        ptr = ctypes.c_void_p()
-        with self._lock:
-            _check(self._lib.fz_batch_assign(self._h, batch._h, mode, blob, offs, len(patterns), k, ctypes.byref(ptr)))
-        return _take_assign_array(self._lib, ptr.value, batch.n_seqs)     # (a plain handle was refused above)
+        return self.batch_assign(batch, MODE_SUBS, patterns, k, tables)
 
     def upload_shard(self, data, buf_global_off, own_lo, own_hi, global_n):
         addr, n, keep = _buffer_address(data)
@@ -1168,75 +1052,58 @@ class Engine(object):
     # -- searches (raw streams, tuples (start, end, dist, block)) ------------------------------
     def search_exact(self, seq, pattern, lo=0, hi=None, as_array=False):
         """Ascending start indices of every occurrence: a list of ints, or (as_array=True) a numpy int64 array."""
-        import numpy as np
         paddr, m, keep = _buffer_address(pattern)
-        ptr = ctypes.POINTER(ctypes.c_uint64)()
-        cnt = ctypes.c_uint64(0)
+        ptr, cnt = u64p(), u64(0)
         with self._lock:
             _check(self._lib.fz_search_exact(self._h, seq._h, paddr, m, max(0, lo),
                                              UINT64_MAX if hi is None else max(0, hi),
                                              ctypes.byref(ptr), ctypes.byref(cnt)))
-        n = cnt.value
-        arr = np.empty(n, dtype=np.int64)
-        if n:
-            ctypes.memmove(arr.ctypes.data, ptr, 8 * n)
-        self._lib.fz_free(ptr)
+        arr = _take_copy(self._lib, ptr, cnt.value, 'int64')
         return arr if as_array else arr.tolist()
 
-    def _match_call(self, fn, seq, pattern, *ints, **kw):
-        if type(pattern) is bytes:                 # ctypes passes a bytes object as a pointer to its buffer
-            paddr, m, keep = pattern, len(pattern), None
-        else:
-            paddr, m, keep = _buffer_address(pattern)
-        ptr = ctypes.POINTER(FzMatch)()
+    def rows_call(self, fn, seq, pattern, *ints, take=OwnedRows):
+        """One C-ABI search -> take(library, rows pointer, row count).  OwnedRows: the library's result buffer itself, for
+        callers that turn the rows into Match objects in C (common.matches_from_rows) — no numpy array, no second copy;
+        _take_rows: a structured array; _take_matches: a list of tuples."""
+        # (ctypes passes a bytes object as a pointer to its buffer; spelt out per method: a helper would be one more frame
+        # in the calls the benchmark times)
+        paddr, m, keep = (pattern, len(pattern), None) if type(pattern) is bytes else _buffer_address(pattern)
+        ptr = mp()
         cnt = ctypes.c_uint64(0)
         with self._lock:
             _check(fn(self._h, seq._h, paddr, m, *ints, ctypes.byref(ptr), ctypes.byref(cnt)))
-        if kw.get("as_array"):
-            return _take_matches_array(self._lib, ptr, cnt.value)
-        return _take_matches(self._lib, ptr, cnt.value)
-
-    def rows_call(self, fn, seq, pattern, *ints):
-        """One C-ABI search -> OwnedRows: the library's result buffer itself (address + row count), for callers that turn
-        the rows into Match objects in C (common.matches_from_rows) — no numpy array, no second copy."""
-        if type(pattern) is bytes:
-            paddr, m, keep = pattern, len(pattern), None
-        else:
-            paddr, m, keep = _buffer_address(pattern)
-        ptr = ctypes.POINTER(FzMatch)()
-        cnt = ctypes.c_uint64(0)
-        with self._lock:
-            _check(fn(self._h, seq._h, paddr, m, *ints, ctypes.byref(ptr), ctypes.byref(cnt)))
-        return OwnedRows(self._lib, ptr, cnt.value)
+        return take(self._lib, ptr, cnt.value)
 
     def lev_ngrams_consolidated(self, seq, pattern, k, as_array=False):
         """consolidate_overlapping_matches(find_near_matches_levenshtein_ngrams(...)) in one call (fz_lev_ngrams_consolidated)."""
-        return self._match_call(self._lib.fz_lev_ngrams_consolidated, seq, pattern, k, as_array=as_array)
+        return self.rows_call(self._lib.fz_lev_ngrams_consolidated, seq, pattern, k, take=_take_rows if as_array else _take_matches)
 
     def subs_ngrams_best(self, seq, pattern, k, as_array=False):
         """Best match of every overlap group of the substitutions-only n-gram stream, group-list order (fz_subs_ngrams_best)."""
-        return self._match_call(self._lib.fz_subs_ngrams_best, seq, pattern, k, as_array=as_array)
+        return self.rows_call(self._lib.fz_subs_ngrams_best, seq, pattern, k, take=_take_rows if as_array else _take_matches)
 
     def lev_ngrams(self, seq, pattern, k, as_array=False):
         """Raw stream of find_near_matches_levenshtein_ngrams: list of (start, end, dist, block)
         tuples, or a numpy structured array with those fields (as_array=True, no per-record
         Python objects)."""
-        return self._match_call(self._lib.fz_lev_ngrams, seq, pattern, k, as_array=as_array)
+        return self.rows_call(self._lib.fz_lev_ngrams, seq, pattern, k, take=_take_rows if as_array else _take_matches)
 
-    def _multi_call(self, fn, seq, patterns, k):
-        """-> (result pointer, per-pattern row offsets) of one fz_lev_ngrams_multi* call; the caller frees the pointer."""
+    def _multi_call(self, name, seq, patterns, k, tables=None):
+        """One multi-pattern call on a plain sequence -> (rows pointer, per-pattern row offsets); the caller owns the pointer.
+        tables = (pmask, tmask): the class form of entry point `name`, `name`_cls, which takes the masks behind k."""
         blob, offs = pack_patterns(patterns)
-        ptr = ctypes.POINTER(FzMatch)()
-        optr = ctypes.POINTER(ctypes.c_uint64)()
+        if tables is None:
+            fn, masks = getattr(self._lib, name), ()
+        else:
+            fn, masks = _entry(self._lib, name + "_cls"), (tables[0], tables[1])
+        ptr, optr = mp(), u64p()
         with self._lock:
-            _check(fn(self._h, seq._h, blob, offs, len(patterns), k, ctypes.byref(ptr), ctypes.byref(optr)))
-        bounds = optr[:len(patterns) + 1]
-        self._lib.fz_free(optr)
-        return ptr, bounds
+            _check(fn(self._h, seq._h, blob, offs, len(patterns), k, *masks, ctypes.byref(ptr), ctypes.byref(optr)))
+        return ptr, _take_bounds(self._lib, optr, len(patterns))
 
-    def _multi(self, fn, seq, patterns, k, as_array):
+    def _multi(self, name, seq, patterns, k, as_array, tables=None):
         patterns = list(patterns)
-        ptr, bounds = self._multi_call(fn, seq, patterns, k)
+        ptr, bounds = self._multi_call(name, seq, patterns, k, tables)
         rows = _take_matches_array(self._lib, ptr, bounds[-1])
         out = [rows[bounds[i]:bounds[i + 1]] for i in range(len(patterns))]
         return out if as_array else [r.tolist() for r in out]
@@ -1244,63 +1111,43 @@ class Engine(object):
     def lev_ngrams_multi(self, seq, patterns, k, as_array=False):
         """[lev_ngrams(seq, p, k) for p in patterns] in as few passes over the sequence as the patterns allow
         (fz_lev_ngrams_multi): a list with one raw stream per pattern, in the shapes lev_ngrams returns."""
-        return self._multi(self._lib.fz_lev_ngrams_multi, seq, patterns, k, as_array)
+        return self._multi("fz_lev_ngrams_multi", seq, patterns, k, as_array)
 
     def lev_ngrams_multi_consolidated(self, seq, patterns, k, as_array=False):
         """[lev_ngrams_consolidated(seq, p, k) for p in patterns] (fz_lev_ngrams_multi_consolidated)."""
-        return self._multi(self._lib.fz_lev_ngrams_multi_consolidated, seq, patterns, k, as_array)
+        return self._multi("fz_lev_ngrams_multi_consolidated", seq, patterns, k, as_array)
 
-    def subs_ngrams_multi(self, seq, patterns, k, as_array=False):
+    def subs_ngrams_multi(self, seq, patterns, k, as_array=False, tables=None):
         """[subs_ngrams(seq, p, k) for p in patterns] in as few passes over the sequence as the patterns allow
-        (fz_subs_ngrams_multi): a list with one raw stream per pattern."""
-        return self._multi(self._lib.fz_subs_ngrams_multi, seq, patterns, k, as_array)
+        (fz_subs_ngrams_multi): a list with one raw stream per pattern.  tables = (pmask, tmask): under their class distance."""
+        return self._multi("fz_subs_ngrams_multi", seq, patterns, k, as_array, tables)
 
-    def subs_ngrams_multi_best(self, seq, patterns, k, as_array=False):
+    def subs_ngrams_multi_best(self, seq, patterns, k, as_array=False, tables=None):
         """[subs_ngrams_best(seq, p, k) for p in patterns] (fz_subs_ngrams_multi_best)."""
-        return self._multi(self._lib.fz_subs_ngrams_multi_best, seq, patterns, k, as_array)
+        return self._multi("fz_subs_ngrams_multi_best", seq, patterns, k, as_array, tables)
 
-    def _multi_call_classes(self, name, seq, patterns, k, tables):
-        fn = _class_entry(self._lib, name)
-        blob, offs = pack_patterns(patterns)
-        ptr = ctypes.POINTER(FzMatch)()
-        optr = ctypes.POINTER(ctypes.c_uint64)()
-        with self._lock:
-            _check(fn(self._h, seq._h, blob, offs, len(patterns), k, tables[0], tables[1], ctypes.byref(ptr), ctypes.byref(optr)))
-        bounds = optr[:len(patterns) + 1]
-        self._lib.fz_free(optr)
-        return ptr, bounds
-
-    def subs_ngrams_multi_classes(self, seq, patterns, k, tables, best=False, as_array=False):
-        """fz_subs_ngrams_multi_cls (best: fz_subs_ngrams_multi_best_cls): one stream per pattern under the class distance of
-        tables = (pmask, tmask)."""
+    def multi_rows_call(self, seq, patterns, k, mode=MODE_LEV, tables=None):
+        """fz_lev_ngrams_multi_consolidated (MODE_LEV) or fz_subs_ngrams_multi_best (MODE_SUBS; with tables, its class form)
+        -> (OwnedRows of all patterns' rows, row offsets per pattern), for callers that build Match objects in C straight
+        from the result buffer."""
         patterns = list(patterns)
-        ptr, bounds = self._multi_call_classes("fz_subs_ngrams_multi_best_cls" if best else "fz_subs_ngrams_multi_cls", seq, patterns, k, tables)
-        rows = _take_matches_array(self._lib, ptr, bounds[-1])
-        out = [rows[bounds[i]:bounds[i + 1]] for i in range(len(patterns))]
-        return out if as_array else [r.tolist() for r in out]
+        name = "fz_subs_ngrams_multi_best" if mode == MODE_SUBS else "fz_lev_ngrams_multi_consolidated"
+        ptr, bounds = self._multi_call(name, seq, patterns, k, tables)
+        return OwnedRows(self._lib, ptr, bounds[-1]), bounds
+
+    # the class calls by their names of old: tables = (pmask, tmask) of classes.class_tables
+    def subs_ngrams_multi_classes(self, seq, patterns, k, tables, best=False, as_array=False):
+        return (self.subs_ngrams_multi_best if best else self.subs_ngrams_multi)(seq, patterns, k, as_array, tables)
 
     def multi_rows_call_classes(self, seq, patterns, k, tables):
-        """fz_subs_ngrams_multi_best_cls -> (OwnedRows of all patterns' rows, row offsets per pattern)."""
-        patterns = list(patterns)
-        ptr, bounds = self._multi_call_classes("fz_subs_ngrams_multi_best_cls", seq, patterns, k, tables)
-        return OwnedRows(self._lib, ptr, bounds[-1]), bounds
-
-    def multi_rows_call(self, seq, patterns, k, fn=None):
-        """fz_lev_ngrams_multi_consolidated (or `fn`: fz_subs_ngrams_multi_best) -> (OwnedRows of all patterns' rows, row
-        offsets per pattern), for callers that build Match objects in C straight from the result buffer."""
-        patterns = list(patterns)
-        ptr, bounds = self._multi_call(fn or self._lib.fz_lev_ngrams_multi_consolidated, seq, patterns, k)
-        return OwnedRows(self._lib, ptr, bounds[-1]), bounds
+        return self.multi_rows_call(seq, patterns, k, MODE_SUBS, tables)
 
     def lev_ngrams_begin(self, seq, pattern, k):
         """Launch lev_ngrams and return; lev_ngrams_end() delivers the result of the OLDEST search in flight.
         Up to two searches may be in flight per engine (the scan of search i + 1 runs while the host orders
         and consumes the records of search i); the host and other streams (a collective, a copy) can work
         meanwhile."""
-        if type(pattern) is bytes:
-            paddr, m, keep = pattern, len(pattern), None
-        else:
-            paddr, m, keep = _buffer_address(pattern)
+        paddr, m, keep = (pattern, len(pattern), None) if type(pattern) is bytes else _buffer_address(pattern)
         with self._lock:
             _check(self._lib.fz_lev_ngrams_begin(self._h, seq._h, paddr, m, k))
 
@@ -1323,36 +1170,36 @@ class Engine(object):
         return self.lev_ngrams_end(as_array=as_array)
 
     def lev_ngrams_end(self, as_array=False):
-        ptr = ctypes.POINTER(FzMatch)()
+        ptr = mp()
         cnt = ctypes.c_uint64(0)
         with self._lock:
             _check(self._lib.fz_lev_ngrams_end(self._h, ctypes.byref(ptr), ctypes.byref(cnt)))
         if as_array:
-            return _take_matches_array(self._lib, ptr, cnt.value)
+            return _take_rows(self._lib, ptr, cnt.value)
         return _take_matches(self._lib, ptr, cnt.value)
 
     def subs_ngrams(self, seq, pattern, k, as_array=False):
-        return self._match_call(self._lib.fz_subs_ngrams, seq, pattern, k, as_array=as_array)
+        return self.rows_call(self._lib.fz_subs_ngrams, seq, pattern, k, take=_take_rows if as_array else _take_matches)
 
     def generic_ngrams(self, seq, pattern, max_subs, max_ins, max_dels, max_l, as_array=False):
-        return self._match_call(self._lib.fz_generic_ngrams, seq, pattern, max_subs, max_ins, max_dels, max_l,
-                                as_array=as_array)
+        return self.rows_call(self._lib.fz_generic_ngrams, seq, pattern, max_subs, max_ins, max_dels, max_l,
+                              take=_take_rows if as_array else _take_matches)
 
     def generic_ngrams_consolidated(self, seq, pattern, max_subs, max_ins, max_dels, max_l, as_array=False):
         """consolidate_overlapping_matches(find_near_matches_generic_ngrams(...)) with the first stage of the consolidation
         on the device (fz_generic_ngrams_consolidated): rows (start, end, dist, block) sorted by (start, end, dist)."""
-        return self._match_call(self._lib.fz_generic_ngrams_consolidated, seq, pattern, max_subs, max_ins, max_dels, max_l,
-                                as_array=as_array)
+        return self.rows_call(self._lib.fz_generic_ngrams_consolidated, seq, pattern, max_subs, max_ins, max_dels, max_l,
+                              take=_take_rows if as_array else _take_matches)
 
     def lev_lp(self, seq, pattern, k, as_array=False):
-        return self._match_call(self._lib.fz_lev_lp, seq, pattern, k, as_array=as_array)
+        return self.rows_call(self._lib.fz_lev_lp, seq, pattern, k, take=_take_rows if as_array else _take_matches)
 
     def subs_lp(self, seq, pattern, k, as_array=False):
-        return self._match_call(self._lib.fz_subs_lp, seq, pattern, k, as_array=as_array)
+        return self.rows_call(self._lib.fz_subs_lp, seq, pattern, k, take=_take_rows if as_array else _take_matches)
 
     def generic_lp(self, seq, pattern, max_subs, max_ins, max_dels, max_l, as_array=False):
-        return self._match_call(self._lib.fz_generic_lp, seq, pattern, max_subs, max_ins, max_dels, max_l,
-                                as_array=as_array)
+        return self.rows_call(self._lib.fz_generic_lp, seq, pattern, max_subs, max_ins, max_dels, max_l,
+                              take=_take_rows if as_array else _take_matches)
 
     def _any_call(self, fn, seq, pattern, *ints):
         paddr, m, keep = _buffer_address(pattern)
@@ -1392,7 +1239,7 @@ class Engine(object):
         """(free, total) device memory in bytes: the minimum over the engine's devices."""
         f, t = ctypes.c_uint64(0), ctypes.c_uint64(0)
         with self._lock:
-            _check(self._lib.fz_mem_info(self._h, ctypes.byref(f), ctypes.byref(t)))
+            _check(_entry(self._lib, 'fz_mem_info')(self._h, ctypes.byref(f), ctypes.byref(t)))
         return f.value, t.value
 
     def kernel_ms(self):

@@ -15,7 +15,7 @@ subsequence — takes the per-pattern code inside the same call, with the result
 
 ``classes=`` (classes.py: IUPAC patterns) is answered by the pass alone: fz_subs_ngrams_multi_best_cls for the whole list.
 """
-from ._native import UnsupportedSearch
+from ._native import MODE_LEV, MODE_SUBS, UnsupportedSearch
 from .common import LevenshteinSearchParams, matches_from_rows_multi
 from .engine import DeviceSequence, is_byteslike, prepare_shared
 
@@ -105,8 +105,7 @@ def find_near_matches_multi(subsequences, sequence,
             for (i, _), raw in zip(batch, raws):
                 results[i] = _finish_ngrams(raw, pr.original, False)
         elif batch:
-            fn = pr.engine._lib.fz_subs_ngrams_multi_best if subs else None
-            rows, bounds = pr.engine.multi_rows_call(pr.handle, [pb for _, pb in batch], k, fn)
+            rows, bounds = pr.engine.multi_rows_call(pr.handle, [pb for _, pb in batch], k, MODE_SUBS if subs else MODE_LEV)
             for (i, _), matches in zip(batch, matches_from_rows_multi(rows, bounds, pr.original)):
                 results[i] = matches
         return results

@@ -443,12 +443,11 @@ def test_timing_totals(engine, force_pass):
     seqs = [_rand(rnd, b"ACGT", 200) for _ in range(20)]
     pats = [seqs[4][50:70], seqs[9][100:120], seqs[0][:20], seqs[19][180:], seqs[12][30:37]]
     blob, offs = _pack(seqs)
-    lib = _native.load_library()
     hb = engine.upload_batch(blob, offs)
     hs = engine.upload(blob)
 
     def plain(mode):
-        rows, bounds = engine.multi_rows_call(hs, pats, k, fn=None if mode == LEV else lib.fz_subs_ngrams_multi_best)
+        rows, bounds = engine.multi_rows_call(hs, pats, k, mode=mode)
         return rows.to_array().tolist(), list(bounds)
 
     def batch(mode):

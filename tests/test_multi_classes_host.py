@@ -314,9 +314,6 @@ class _StubEngine(object):
     """Logs which entry point a call reaches; every search finds nothing."""
     devices = [0]
 
-    class _lib(object):                                    # (find_near_matches_multi names the reduced entry by its symbol)
-        fz_subs_ngrams_multi_best = "fz_subs_ngrams_multi_best"
-
     def __init__(self, log):
         self.log = log
 
@@ -329,8 +326,8 @@ class _StubEngine(object):
         h.n_seqs = len(offs) - 1
         return h
 
-    def multi_rows_call(self, handle, patterns, k, fn=None):
-        self.log.append(("multi", list(patterns), k, fn))
+    def multi_rows_call(self, handle, patterns, k, mode=_native.MODE_LEV):
+        self.log.append(("multi", list(patterns), k, mode))
         return _NoRows(), [0] * (len(patterns) + 1)
 
     def multi_rows_call_classes(self, handle, patterns, k, tables):
@@ -377,7 +374,7 @@ def test_none_reaches_the_existing_entry_points_and_a_mapping_the_class_ones():
     assert multi_batch.find_near_matches_multi_batch(PATS, held, classes=None, **kw) == [[[], [], []]] * 2
     assert list(assign.find_best_matches_batch(PATS, held, classes=None, **kw).pattern) == [-1] * 3
     assert [e[0] for e in log] == ["multi", "multi", "batch", "assign"]
-    assert log[0] == log[1] == ("multi", PATS, 3, "fz_subs_ngrams_multi_best")
+    assert log[0] == log[1] == ("multi", PATS, 3, _native.MODE_SUBS)           # (the reduced substitutions entry, named by its mode)
     assert log[2][1] == log[3][1] == _native.MODE_SUBS
     del log[:]
     assert multi.find_near_matches_multi(PATS, seq, classes=IUPAC, **kw) == [[], []]
