@@ -3,7 +3,8 @@ of the library are process-wide statics read from the environment (FZ_FORCE_BIG_
 FZ_MAX_BLOCKS, FZ_NO_DIRECT), so a test that wants them set starts a fresh interpreter.  Prints "OK <n cases> <n records>".
 The seam sweeps of tests/seam_case.py run through here as well (`seams <route> <CUs>`: the route's small texts, then the
 text with several tiles per workgroup; in-process from tests/test_gpu_scan_seams.py for the routes that need no switch), and
-those of tests/batch_seam_case.py (`batch-seams <route> <CUs>`)."""
+those of tests/batch_seam_case.py (`batch-seams <route> <CUs>`) and the shard-cut sweep of tests/shard_cut_case.py
+(`shardcut <route>`: the route across a shard cut on a two-device engine and through two handles)."""
 import io
 import os
 import random
@@ -466,6 +467,139 @@ def run_mp_shard_cut(engine, r, cut, n):
     return covers, texts, rows
 
 
+# -- the shard-cut sweep of the single-pattern routes (tests/shard_cut_case.py) -------------------------------------------------
+def two_shards(eng2, text, cut, halo):
+    """A sharded sequence of a two-device engine: fz_seq_new and one fz_seq_add_shard per device, at halo `halo`."""
+    from tests import shard_cut_case as cc
+    seq = eng2.new_sequence(len(text))
+    try:
+        for dev, (buf, off, lo, hi) in enumerate(cc.buffers(text, cut, halo)):
+            eng2.add_shard(seq, dev, buf, off, lo, hi)
+    except Exception:
+        seq.release()
+        raise
+    return seq
+
+
+def differ(name, what, got, want):
+    if got != want:
+        bad = next((i for i, (a, b) in enumerate(zip(got, want)) if a != b), min(len(got), len(want)))
+        raise AssertionError("%s %s: %d rows against %d expected, first difference at row %d: %r / %r" % (
+            name, what, len(got), len(want), bad, got[bad:bad + 2], want[bad:bad + 2]))
+
+
+def shardcut_extras(eng, h, route, p, want, what, two_in_flight):
+    """On a handle whose raw stream was `want`: the consolidated rows (Levenshtein, generic), the flag (substitutions,
+    generic) and - `two_in_flight` - two searches begun before either is collected."""
+    import oracle
+    k = route.k
+    if route.kind == "lev":
+        differ(route.name, what + ", consolidated", [r[:3] for r in eng.lev_ngrams_consolidated(h, p, k)], oracle.consolidate(want))
+    elif route.kind == "subs":
+        assert eng.subs_ngrams_any(h, p, k) == bool(want), (route.name, what, "subs_ngrams_any")
+    elif route.kind != "exact":
+        lim = route.kind[1:] + (k,)
+        differ(route.name, what + ", consolidated", [r[:3] for r in eng.generic_ngrams_consolidated(h, p, *lim)], oracle.consolidate(want))
+        assert eng.generic_ngrams_any(h, p, *lim) == bool(want), (route.name, what, "generic_ngrams_any")
+    if two_in_flight and route.kind != "exact":
+        for _ in range(2):
+            if route.kind == "lev":
+                eng.lev_ngrams_begin(h, p, k)
+            elif route.kind == "subs":
+                eng.subs_ngrams_begin(h, p, k)
+            else:
+                eng.generic_ngrams_begin(h, p, *(route.kind[1:] + (k,)))
+        differ(route.name, what + ", older of two in flight", eng.search_end(), want)
+        differ(route.name, what + ", younger of two in flight", eng.search_end(), want)
+        return 1
+    return 0
+
+
+def run_shardcut_merged(eng2, route, cases, extras=True):
+    """(a) Every case on a two-device engine, the library merging the shards' streams: the ordered raw stream, verify_form and
+    raw_matches against the expected stream of the whole text; main-cut extras on the same handle.
+    -> (cases run, rows compared, searches with two in flight, expected rows of all cases)."""
+    from tests import shard_cut_case as cc
+    p = sc_pattern(route)
+    halo = cc.halo(route)
+    n_rows = n_flight = n_cases = 0
+    all_rows = []
+    for c in cases:
+        want = cc.expected(route, c)
+        what = "two devices, cut %d, d = %d %s" % (c.cut, c.d, "exact" if c.exact else "edited")
+        h = two_shards(eng2, c.case.text.tobytes(), c.cut, halo)
+        try:
+            got = seam_search(eng2, h, route.kind, p, route.k)
+            st = eng2.stats()
+            differ(route.name, what, got, want)
+            assert st["verify_form"] == route.form, (route.name, what, "verify_form", st["verify_form"])
+            assert st["raw_matches"] == len(want), (route.name, what, "raw_matches", st["raw_matches"], len(want))
+            if extras:
+                n_flight += shardcut_extras(eng2, h, route, p, want, what, c.exact and c.d == cc.straddling_d(route))
+        finally:
+            h.release()
+        n_rows += len(want)
+        n_cases += 1
+        all_rows += want
+    return n_cases, n_rows, n_flight, all_rows
+
+
+def run_shardcut_handles(engine, route, cases):
+    """(b) Each shard alone, as a handle of its own on a one-device engine (fz_seq_upload_shard): A's rows and B's rows
+    together, stably sorted by block (exact search: as they come), are the expected stream; raw_matches of both calls,
+    verify_form of a shard that owns a byte; the whole text through fz_seq_upload as the control.  -> (cases, rows)."""
+    from tests import shard_cut_case as cc
+    p = sc_pattern(route)
+    halo = cc.halo(route)
+    n_rows = n_cases = 0
+    for c in cases:
+        want = cc.expected(route, c)
+        what = "two handles, cut %d, d = %d %s" % (c.cut, c.d, "exact" if c.exact else "edited")
+        text = c.case.text.tobytes()
+        (a, a_off, a_lo, a_hi), (b, b_off, b_lo, b_hi) = cc.buffers(text, c.cut, halo)
+        hs = [engine.upload_shard(a, a_off, a_lo, a_hi, len(text)), engine.upload_shard(b, b_off, b_lo, b_hi, len(text)), engine.upload(text)]
+        try:
+            parts = []
+            for h, owns in ((hs[0], a_hi > a_lo), (hs[1], b_hi > b_lo)):
+                rows = seam_search(engine, h, route.kind, p, route.k)
+                st = engine.stats()
+                assert st["raw_matches"] == len(rows), (route.name, what, "raw_matches", st["raw_matches"], len(rows))
+                if owns:
+                    assert st["verify_form"] == route.form, (route.name, what, "verify_form", st["verify_form"])
+                parts.append(rows)
+            both = parts[0] + parts[1]
+            if route.kind != "exact":
+                both.sort(key=lambda r: r[3])                   # stable: block major, shard order keeps the index ascending
+            differ(route.name, what, both, want)
+            differ(route.name, what + ", the whole text", seam_search(engine, hs[2], route.kind, p, route.k), want)
+        finally:
+            for h in hs:
+                h.release()
+        n_rows += len(want)
+        n_cases += 1
+    return n_cases, n_rows
+
+
+def sc_pattern(route):
+    from tests import seam_case as sc
+    return sc.route_pattern(route)
+
+
+def run_shardcut_route(eng2, engine, route):
+    """(a) and (b) for one route: the main cut's full sweep and the secondary cuts on the two-device engine, the main cut
+    through two handles.  -> the coverage line that was asserted."""
+    from tests import shard_cut_case as cc
+    main = list(cc.texts(route))
+    n_main, rows, n_flight, all_rows = run_shardcut_merged(eng2, route, main)
+    cover, nb, across = cc.check_coverage(route, main, all_rows)
+    assert n_flight == (0 if route.kind == "exact" else 1)
+    n_sec, rows_sec, _f, _r = run_shardcut_merged(eng2, route, list(cc.secondary(route)) + [cc.both_sides(route)], extras=False)
+    n_two, rows_two = run_shardcut_handles(engine, route, main)
+    assert n_two == n_main and rows_two == rows
+    return "%s | secondary cuts: %d texts, %d rows; two handles: %d texts" % (
+        cc.coverage_line(route, cover, nb, across, n_main), n_sec, rows_sec, n_two)
+
+
 def mp_batch_expected(r, pats, seqs, caches):
     """The oracle (lev, subs) or the class model (cls) per (pattern, sequence) -> per pattern (raw rows, reduced rows) as
     (sequence, start, end, dist[, block]).  `caches`: one dict per pattern, by sequence bytes."""
@@ -840,6 +974,17 @@ def main(argv):
         eng.close()
         print(line)
         print("OK %d %d" % (n_search, n_rows))
+        return
+    if what == "shardcut":
+        # one route of tests/shard_cut_case.py under the process-wide switch it needs: argv = route name
+        from tests import shard_cut_case as cc
+        route = next(r for r in cc.ROUTES if r.name == argv[1])
+        eng2, eng = _native.Engine([0, 0]), _native.Engine([0])
+        line = run_shardcut_route(eng2, eng, route)
+        eng2.close()
+        eng.close()
+        print(line)
+        print("OK %s" % route.name)
         return
     if what == "batch-seams":
         # one route of tests/batch_seam_case.py under the process-wide switch it needs (FZ_NO_BITS, FZ_NO_WF_FUSE,
