@@ -14,7 +14,8 @@ sequence and ``find_near_matches_batch`` one subsequence in many sequences (``re
 in one pass; ``find_near_matches_multi_batch`` searches many subsequences in many sequences, a pass per group of up to 64;
 ``resident_records`` makes such a batch from a FASTQ file or a file of lines and ``resident_fasta`` from the contigs of a
 FASTA file, split on the device; ``derive_batch`` (``batch.derive(...)``) makes a batch of cuts of a resident batch — selected,
-trimmed, reversed, complemented — without leaving the device.  The multi-pattern
+trimmed, reversed, complemented — without leaving the device; ``format_records`` / ``write_records`` assemble batches into the
+text of a FASTQ, FASTA or line file on the device, one copy back.  The multi-pattern
 calls take ``classes=IUPAC_DNA`` (or any mapping of pattern byte -> accepted sequence bytes) for degenerate patterns.
 """
 import io
@@ -35,6 +36,7 @@ from .records import resident_records, RecordBatch
 from .fasta import resident_fasta, FastaBatch
 from .classes import IUPAC_DNA
 from .derive import derive_batch, DerivedBatch, DNA_COMPLEMENT
+from .egress import format_records, write_records
 
 __version__ = '0.1.0'
 
@@ -57,6 +59,8 @@ __all__ = [
     'derive_batch',
     'DerivedBatch',
     'DNA_COMPLEMENT',
+    'format_records',
+    'write_records',
     'cache_info',
     'cache_clear',
     'UnsupportedSearch',

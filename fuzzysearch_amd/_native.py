@@ -30,6 +30,11 @@ class FzDeriveInfo(ctypes.Structure):
                 ("bad_item", ctypes.c_uint64), ("bad_reason", ctypes.c_uint32)]
 
 
+class FzFormatInfo(ctypes.Structure):
+    _fields_ = [("n_records", ctypes.c_uint64), ("text_bytes", ctypes.c_uint64), ("longest_record", ctypes.c_uint64),
+                ("bad_record", ctypes.c_uint64), ("bad_reason", ctypes.c_uint32)]
+
+
 class FzStats(ctypes.Structure):
     _fields_ = [("bytes_scanned", ctypes.c_uint64), ("ngram_hits", ctypes.c_uint64),
                 ("raw_matches", ctypes.c_uint64), ("filter_ms", ctypes.c_double),
@@ -57,6 +62,7 @@ vpp, cip, f64p = ctypes.POINTER(vp), ctypes.POINTER(ci), ctypes.POINTER(f64)
 u32p, u64p, mp = ctypes.POINTER(u32), ctypes.POINTER(u64), ctypes.POINTER(FzMatch)
 u32pp, u64pp, mpp = ctypes.POINTER(u32p), ctypes.POINTER(u64p), ctypes.POINTER(mp)
 rip, dip, stp = ctypes.POINTER(FzRecordsInfo), ctypes.POINTER(FzDeriveInfo), ctypes.POINTER(FzStats)
+fip = ctypes.POINTER(FzFormatInfo)
 
 _SEARCH = (ci, (vp, vp, bp, u32, u32, mpp, u64p))                          # (ctx, seq, p, m, k, &rows, &n)
 _GENERIC = (ci, (vp, vp, bp, u32, u32, u32, u32, u32, mpp, u64p))          # (ctx, seq, p, m, subs, ins, dels, l, &rows, &n)
@@ -124,6 +130,10 @@ PROTOTYPES = {
     "fz_batch_derive": (ci, (vp, vp, vp, vp, vp, u64, u32, bp, vpp, dip)),
     "fz_debug_derive_plan": (ci, (vp, u64, vp, vp, vp, u64, vp, vp, dip)),
     "fz_debug_derive_ms": (ci, (vp, f64p)),
+    "fz_batch_upload_records_lines": (ci, (vp, bp, u64, u32, vp, u32, u32, vpp, rip)),
+    "fz_batch_format": (ci, (vp, vp, u32, bp, vp, u32, u32, vp, u64, fip)),
+    "fz_debug_format_plan": (ci, (vp, u32, u64, vp, u32, u32, vp, fip)),
+    "fz_debug_format_ms": (ci, (vp, f64p)),
     "fz_subs_ngrams_any": _ANY,
     "fz_subs_lp_any": _ANY,
     "fz_generic_ngrams_any": (ci, (vp, vp, bp, u32, u32, u32, u32, u32, cip)),
@@ -180,6 +190,7 @@ OPTIONAL = frozenset((
     "fz_debug_records_ms",
     "fz_batch_upload_fasta", "fz_batch_fasta_index", "fz_debug_fasta_split", "fz_debug_fasta_upper4", "fz_debug_fasta_src",
     "fz_batch_derive", "fz_debug_derive_plan", "fz_debug_derive_ms",
+    "fz_batch_upload_records_lines", "fz_batch_format", "fz_debug_format_plan", "fz_debug_format_ms",
     "fz_debug_scan_plan", "fz_mem_info",
 ))
 
@@ -577,6 +588,57 @@ def derive_plan(offs, index, starts, ends, n_out):
     return src, at, d
 
 
+FORMAT_MAX_COLUMNS, FORMAT_MAX_LITERAL, FORMAT_NO_CHECK = 8, 255, 0xffffffff     # FZ_FORMAT_*
+# preset -> (the C + 1 literals, the pair of columns whose sequences must be of one length in every record or None)
+FORMAT_PRESETS = {'lines': ((b'', b'\n'), None),
+                  'fastq': ((b'', b'\n', b'\n+\n', b'\n'), (1, 2)),
+                  'fasta': ((b'>', b'\n', b'\n'), None)}
+
+
+def _raise_format(rc, info):
+    try:
+        _raise(rc)
+    except ValueError as e:
+        e.info = info
+        raise
+
+
+def _format_literals(literals, equal):
+    """-> (the literals back to back, their uint32 lengths, equal_a, equal_b) as fz_batch_format takes them."""
+    import numpy as np
+    lens = np.array([len(l) for l in literals], dtype=np.uint32)
+    a, b = (FORMAT_NO_CHECK, FORMAT_NO_CHECK) if equal is None else equal
+    return b''.join(literals) or b'\0', lens, a, b
+
+
+def format_plan(offs, literal_lens, equal=None):
+    """fz_debug_format_plan (no device): the measure step and the scan of fz_batch_format on the host, through the function
+    its kernel runs.  offs: per column its len + 1 offsets (the same array twice: a column twice) -> (at, info dict); a bad
+    record raises ValueError as format_batch does."""
+    import numpy as np
+    cols, seen = [], {}
+    for o in offs:
+        if id(o) not in seen:
+            seen[id(o)] = np.ascontiguousarray(o, dtype=np.uint64)
+        cols.append(seen[id(o)])
+    n = len(cols[0]) - 1 if cols else 0
+    for c in cols:
+        if len(c) != n + 1:
+            raise ValueError('the columns have different numbers of sequences')
+    ptrs = (ctypes.c_void_p * max(1, len(cols)))(*[c.ctypes.data for c in cols])
+    lens = np.ascontiguousarray(literal_lens, dtype=np.uint32)
+    if len(lens) != len(cols) + 1:
+        raise ValueError('%d literals for %d columns' % (len(lens), len(cols)))
+    a, b = (FORMAT_NO_CHECK, FORMAT_NO_CHECK) if equal is None else equal
+    at = np.zeros(n + 1, dtype=np.uint64)
+    info = FzFormatInfo()
+    rc = _entry(load_library(), 'fz_debug_format_plan')(ptrs, len(cols), n, lens.ctypes.data, a, b, at.ctypes.data, ctypes.byref(info))
+    d = _struct_dict(info)
+    if rc != FZ_OK:
+        _raise_format(rc, d)
+    return at, d
+
+
 def assign_dtype():
     """The numpy dtype of an fz_assign row (include/fzhip.h): pattern (-1: nothing matched), dist, tied, start, end."""
     global _ASSIGN_DTYPE
@@ -856,6 +918,66 @@ class Engine(object):
         seq.n_seqs = d['n_out']
         seq.info = d
         return seq
+
+    def upload_records_lines(self, text, lines_per_record, lines, flags):
+        """fz_batch_upload_records_lines: upload_records for several lines of every record from one copy of the text and one
+        line table -> a list of batch handles, one per entry of `lines`, each with `.n_seqs` and `.info` (the call's info;
+        packed_bytes: the handle's own).  A malformed text raises as upload_records does; no handle is left."""
+        import numpy as np
+        entry = _entry(self._lib, 'fz_batch_upload_records_lines')
+        kept = np.ascontiguousarray(lines, dtype=np.uint32)
+        addr, n, keep = _buffer_address(text)
+        hs = (ctypes.c_void_p * max(1, len(kept)))()
+        info = FzRecordsInfo()
+        with self._lock:
+            rc = entry(self._h, addr, n, lines_per_record, kept.ctypes.data, len(kept), flags, hs, ctypes.byref(info))
+        del keep
+        d = _struct_dict(info)
+        if rc != FZ_OK:
+            _raise_records(rc, d)
+        out = []
+        for i in range(len(kept)):
+            h = ctypes.c_void_p(hs[i])
+            seq = ResidentSequence(self, h, int(self._lib.fz_seq_len(h)))
+            seq.n_seqs = d['n_seqs']
+            seq.info = dict(d, packed_bytes=seq.nbytes)
+            out.append(seq)
+        return out
+
+    def format_batch(self, columns, literals, equal=None, out=None):
+        """fz_batch_format: the text  join_j(lit[0] + col[0][j] + lit[1] + ... + col[C-1][j] + lit[C])  of C batch handles of
+        this engine, assembled on the device -> a numpy uint8 array of exactly the text (a view of `out`, a writable
+        C-contiguous numpy uint8 array of at least the text's size, when one is given).  equal = (a, b): columns whose
+        sequences must be of one length in every record.  A bad record raises ValueError naming it (`.info`: bad_record,
+        bad_reason) and leaves `out` as it was."""
+        import numpy as np
+        entry = _entry(self._lib, 'fz_batch_format')
+        columns = list(columns)
+        for c in columns:
+            if getattr(c, '_h', None) is None or getattr(c, 'n_seqs', None) is None:
+                raise ValueError('format_batch takes batch handles that have not been released')
+        if len(literals) != len(columns) + 1:
+            raise ValueError('%d literals for %d columns' % (len(literals), len(columns)))
+        blob, lens, a, b = _format_literals(literals, equal)
+        size = sum(c.nbytes for c in columns) + (columns[0].n_seqs if columns else 0) * int(lens.sum())
+        if out is None:
+            out = np.empty(size, dtype=np.uint8)
+        hs = (ctypes.c_void_p * max(1, len(columns)))(*[c._h.value for c in columns])
+        info = FzFormatInfo()
+        with self._lock:
+            rc = entry(self._h, hs, len(columns), blob, lens.ctypes.data, a, b, out.ctypes.data if out.size else None, out.size,
+                       ctypes.byref(info))
+        d = _struct_dict(info)
+        if rc != FZ_OK:
+            _raise_format(rc, d)
+        return out[:d['text_bytes']]
+
+    def format_ms(self):
+        """fz_debug_format_ms: {desc_h2d, measure_scan, gather, text_d2h, call} milliseconds of this engine's last format_batch."""
+        ms = (ctypes.c_double * 5)()
+        with self._lock:
+            _check(_entry(self._lib, 'fz_debug_format_ms')(self._h, ms))
+        return {'desc_h2d': ms[0], 'measure_scan': ms[1], 'gather': ms[2], 'text_d2h': ms[3], 'call': ms[4]}
 
     def derive_ms(self):
         """fz_debug_derive_ms: {tables_h2d, measure_scan, gather, ends_d2h, call} milliseconds of this engine's last derive_batch."""

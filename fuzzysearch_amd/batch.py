@@ -123,6 +123,15 @@ class BatchSequences(object):
         return derive_batch(self, index, starts, ends, reverse, translate)
 
 
+    def format(self, format=None, literals=None, out=None):
+        """format_records(self, ...): the text of this one column, assembled on the device (egress.py); no format and no
+        literals: 'lines'.  (A RecordBatch keeps the name of its record format in ``.format``: format_records(batch, 'lines').)"""
+        from .egress import format_records
+        if format is None and literals is None:
+            format = 'lines'
+        return format_records(self, format, literals, out)
+
+
 def resident_batch(sequences, engine=None):
     """Pack ``sequences`` and upload them to HBM once -> a handle usable as ``sequences`` of find_near_matches_batch."""
     return BatchSequences(sequences, engine)

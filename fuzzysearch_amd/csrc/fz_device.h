@@ -1736,3 +1736,77 @@ FZ_HD uint32_t fz_derive_xlat4(const uint8_t *table, uint32_t v) {
     return (uint32_t)table[v & 0xffu] | ((uint32_t)table[(v >> 8) & 0xffu] << 8) | ((uint32_t)table[(v >> 16) & 0xffu] << 16) |
            ((uint32_t)table[v >> 24] << 24);
 }
+
+// ---------------------------------------------------------------------------------------------
+// Formatted text (fz_batch_format; fz_kernels.h: fz_format_*_kernel): C batches of n sequences each become one text,
+//     text = join over j < n of  lit[0] + col[0][j] + lit[1] + col[1][j] + ... + col[C - 1][j] + lit[C]
+// A record is 2C + 1 segments: segment 2c is literal c, segment 2c + 1 is sequence j of column c.  The descriptor holds, per
+// column, its packed bytes and its scanned length table (n + 1 entries, the first 0; not read when n == 0), and the
+// literals back to back with their offsets.  It is the same struct on the device (device pointers, a copy in LDS per
+// workgroup) and in the host twins (host pointers).  A record is bad when the two columns named for the check differ in
+// length in it (1); the smallest error key (j << 8 | reason, fz_rec_err_key) is the one reported.
+#define FZ_FMT_MAX_COLS 8u             // = FZ_FORMAT_MAX_COLUMNS (include/fzhip.h)
+#define FZ_FMT_MAX_LIT 255u            // = FZ_FORMAT_MAX_LITERAL
+#define FZ_FMT_NO_CHECK 0xffffffffu    // = FZ_FORMAT_NO_CHECK
+#define FZ_FMT_E_EQUAL 1u
+#define FZ_FMT_LIT_BYTES 2304u         // (FZ_FMT_MAX_COLS + 1) * FZ_FMT_MAX_LIT, rounded up to whole dwords
+
+struct FzFmtCol { const uint8_t *bytes; const uint64_t *offs; };
+struct FzFmtDesc {
+    FzFmtCol col[FZ_FMT_MAX_COLS];
+    uint32_t lit_off[FZ_FMT_MAX_COLS + 2u];               // literal c = lits[lit_off[c] .. lit_off[c + 1]); lit_off[C + 1] = their total
+    uint32_t n_cols, equal_a, equal_b, pad_;
+    uint8_t lits[FZ_FMT_LIT_BYTES];
+};
+
+FZ_HD uint64_t fz_format_col_len(const FzFmtDesc &d, uint32_t c, uint64_t j) { return d.col[c].offs[j + 1u] - d.col[c].offs[j]; }
+
+// record -> (its length in the text, verdict)
+struct FzFmtRec { uint64_t len; uint32_t reason; };
+FZ_HD FzFmtRec fz_format_record(const FzFmtDesc &d, uint64_t j) {
+    FzFmtRec o;
+    o.len = d.lit_off[d.n_cols + 1u];
+    for (uint32_t c = 0; c < d.n_cols; ++c) o.len += fz_format_col_len(d, c, j);
+    o.reason = FZ_REC_OK;
+    if (d.equal_a != FZ_FMT_NO_CHECK && d.equal_b != FZ_FMT_NO_CHECK && fz_format_col_len(d, d.equal_a, j) != fz_format_col_len(d, d.equal_b, j))
+        o.reason = FZ_FMT_E_EQUAL;
+    return o;
+}
+
+// The gather's address rule.  A cursor names one byte of record j: segment seg (0 .. 2C), byte off of its len.
+struct FzFmtCur { uint32_t seg; uint64_t off, len; };
+FZ_HD uint64_t fz_format_seg_len(const FzFmtDesc &d, uint64_t j, uint32_t seg) {
+    return (seg & 1u) ? fz_format_col_len(d, seg >> 1, j) : (uint64_t)(d.lit_off[(seg >> 1) + 1u] - d.lit_off[seg >> 1]);
+}
+
+// Byte o of record j (o < the record's length) -> its cursor: at most 2C + 1 segments are walked.
+FZ_HD FzFmtCur fz_format_seek(const FzFmtDesc &d, uint64_t j, uint64_t o) {
+    FzFmtCur g;
+    g.seg = 0; g.off = o; g.len = fz_format_seg_len(d, j, 0);
+    while (g.off >= g.len && g.seg < 2u * d.n_cols) {
+        g.off -= g.len;
+        ++g.seg;
+        g.len = fz_format_seg_len(d, j, g.seg);
+    }
+    return g;
+}
+
+// A cursor that may stand behind its segment's last byte -> the next byte of the text: empty segments and empty records
+// are passed (the caller knows that a byte follows: its position lies in front of the text's end).
+FZ_HD void fz_format_settle(const FzFmtDesc &d, uint64_t &j, FzFmtCur &g) {
+    while (g.off >= g.len) {
+        g.off = 0;
+        if (g.seg == 2u * d.n_cols) { g.seg = 0; ++j; } else ++g.seg;
+        g.len = fz_format_seg_len(d, j, g.seg);
+    }
+}
+
+// Whether the cnt bytes from the cursor on are one run of column bytes, and where that run starts in the column's packed
+// bytes: every one of them lies inside sequence j of the column.
+FZ_HD bool fz_format_run(const FzFmtCur &g, uint32_t cnt) { return (g.seg & 1u) && g.off + cnt <= g.len; }
+FZ_HD uint64_t fz_format_run_lo(const FzFmtDesc &d, uint64_t j, const FzFmtCur &g) { return d.col[g.seg >> 1].offs[j] + g.off; }
+
+// The source of the one byte under the cursor: in a column's packed bytes, or in the descriptor's literals.
+FZ_HD const uint8_t *fz_format_byte_src(const FzFmtDesc &d, uint64_t j, const FzFmtCur &g) {
+    return (g.seg & 1u) ? d.col[g.seg >> 1].bytes + fz_format_run_lo(d, j, g) : d.lits + d.lit_off[g.seg >> 1] + g.off;
+}

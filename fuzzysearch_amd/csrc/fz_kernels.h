@@ -2793,3 +2793,93 @@ __global__ __launch_bounds__(FZ_REC_THREADS) void fz_derive_gather_kernel(const 
         __syncthreads();
     }
 }
+
+// ---------------------------------------------------------------------------------------------
+// Formatted text (fz_batch_format; fz_device.h: fz_format_*): C batches become one text of records, without leaving the device.
+//   fz_format_measure_kernel   one lane per record: the lengths of its sequences from the columns' scanned length tables,
+//                              the literals' total, the pair of columns checked for equal length; the record lengths for
+//                              the records path's scan, the longest record, the smallest bad (record, reason)
+//   fz_format_gather_kernel    text[] by 16-byte pieces of the DESTINATION, as fz_derive_gather_kernel
+// info as fz_rec_measure_kernel's.  desc lies in device memory.
+__global__ __launch_bounds__(FZ_REC_THREADS) void fz_format_measure_kernel(const FzFmtDesc *__restrict__ desc, uint64_t n,
+                                                                           uint64_t *__restrict__ lens,
+                                                                           unsigned long long *__restrict__ info) {
+    const uint64_t stride = (uint64_t)gridDim.x * FZ_REC_THREADS;
+    unsigned long long longest = 0;
+    for (uint64_t j = (uint64_t)blockIdx.x * FZ_REC_THREADS + threadIdx.x; j < n; j += stride) {
+        const FzFmtRec o = fz_format_record(*desc, j);
+        lens[j] = o.len;
+        longest = o.len > longest ? o.len : longest;
+        if (o.reason != FZ_REC_OK) (void)atomicMin(&info[0], (unsigned long long)fz_rec_err_key(j, o.reason));
+    }
+#pragma unroll
+    for (uint32_t d = 32; d; d >>= 1) {
+        const unsigned long long o = __shfl_xor(longest, d, 64);
+        longest = o > longest ? o : longest;
+    }
+    if ((threadIdx.x & 63u) == 0 && longest > __hip_atomic_load(&info[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+        (void)atomicMax(&info[1], longest);
+    if (blockIdx.x == 0 && threadIdx.x == 0) lens[n] = 0;
+}
+
+// at[j] = where record j starts in text[] (n + 1 entries, at[n] = total > 0).  The descriptor, its literals included, is
+// copied into LDS once per workgroup.  Every piece finds its record by the search over at[] and its segment by the walk
+// (fz_format_seek).  A piece inside one column segment is one unaligned 16-byte load from that column's packed bytes and
+// one aligned 16-byte store; every other piece — across a segment or record seam, in a literal, the text's last partial one
+// — goes byte by byte under a cursor that moves on from segment to segment (fz_format_settle, fz_format_byte_src).
+// The over-read guard is the address rule's: a 16-byte load covers exactly the source bytes of the piece's own output
+// bytes, which lie inside sequence j of the column (fz_format_run), never a neighbouring sequence or padding.  text is
+// allocated in whole tiles; the aligned stores end at or in front of `total` besides.
+__global__ __launch_bounds__(FZ_REC_THREADS) void fz_format_gather_kernel(const FzFmtDesc *__restrict__ desc,
+                                                                          const uint64_t *__restrict__ at, uint64_t n, uint64_t total,
+                                                                          uint8_t *__restrict__ text) {
+    __shared__ uint64_t bound[2];
+    __shared__ FzFmtDesc sd;
+    static_assert(sizeof(FzFmtDesc) % 4u == 0, "the descriptor is copied by dwords");
+    {
+        const uint32_t *g = reinterpret_cast<const uint32_t *>(desc);
+        uint32_t *s = reinterpret_cast<uint32_t *>(&sd);
+        for (uint32_t i = threadIdx.x; i < sizeof(FzFmtDesc) / 4u; i += FZ_REC_THREADS) s[i] = g[i];   // (the first tile's barrier orders it)
+    }
+    const uint64_t *ends = at + 1;
+    const uint64_t ntiles = (total + FZ_TILE_BYTES - 1u) / FZ_TILE_BYTES;
+    for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const uint64_t p0 = t * (uint64_t)FZ_TILE_BYTES;
+        const uint64_t p1 = p0 + FZ_TILE_BYTES < total ? p0 + FZ_TILE_BYTES : total;
+        if (threadIdx.x < 2u) {                            // the records of the tile's first and last byte
+            const uint64_t target = threadIdx.x ? p1 - 1u : p0;
+            uint64_t lo = 0, hi = n - 1u;
+            while (lo < hi) {                              // first j with ends[j] > target (target < total = ends[n - 1])
+                const uint64_t mid = lo + ((hi - lo) >> 1);
+                if (ends[mid] > target) hi = mid; else lo = mid + 1u;
+            }
+            bound[threadIdx.x] = lo;
+        }
+        __syncthreads();
+        const uint64_t jlo = bound[0], jhi = bound[1];
+        for (uint32_t q = 0; q < FZ_TILE_BYTES / 16u / FZ_REC_THREADS; ++q) {
+            uint64_t p = p0 + (uint64_t)(q * FZ_REC_THREADS + threadIdx.x) * 16u;
+            if (p >= p1) continue;
+            uint64_t lo = jlo, hi = jhi;
+            while (lo < hi) {
+                const uint64_t mid = lo + ((hi - lo) >> 1);
+                if (ends[mid] > p) hi = mid; else lo = mid + 1u;
+            }
+            uint64_t j = lo;
+            FzFmtCur g = fz_format_seek(sd, j, p - at[j]);
+            if (fz_format_run(g, 16u)) {                   // the piece lies inside one sequence of one column
+                uint4 v;
+                __builtin_memcpy(&v, sd.col[g.seg >> 1].bytes + fz_format_run_lo(sd, j, g), 16);
+                *reinterpret_cast<uint4 *>(text + p) = v;
+            } else {
+                const uint64_t pe = p + 16u < total ? p + 16u : total;
+                for (; p < pe; ++p) {
+                    fz_format_settle(sd, j, g);            // (p < total: a byte follows)
+                    text[p] = *fz_format_byte_src(sd, j, g);
+                    ++g.off;
+                }
+            }
+        }
+        __syncthreads();
+    }
+}

@@ -425,6 +425,7 @@ struct fz_ctx {
     bool any_found = false;                      // result of the last has_near_match_* (fz_*_any) search
     double rec_ms[4] = {0, 0, 0, 0};             // fz_debug_records_ms: the last fz_batch_upload_records
     double drv_ms[5] = {0, 0, 0, 0, 0};          // fz_debug_derive_ms: the last fz_batch_derive
+    double fmt_ms[5] = {0, 0, 0, 0, 0};          // fz_debug_format_ms: the last fz_batch_format
     bool batch_call = false;                     // inside fz_batch_search: the one caller a batch handle is valid for (validate)
     // sharded searches: where every shard's (rank's) records end in the collected vector, and the shards in ascending
     // order of the index range they own (emit_matches orders shard by shard)
@@ -3405,6 +3406,324 @@ int fz_debug_derive_plan(const uint64_t *offs, uint64_t n_src, const uint32_t *i
     if (key != FZ_REC_NO_ERROR) return drv_report(key, info);
     if (total >= (1ull << FZ_IDX_BITS)) return fail(FZ_EUNSUPPORTED, "sequence too long");
     info->packed_bytes = total; info->longest = longest;
+    return FZ_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Several lines of every record (fz_batch_upload_records_lines): the text and its line table once (Ingest::line_table),
+// then the records path's measure, scan and gather once per kept line.  Every line's measure and scan are enqueued before
+// the one readback of all verdicts; with the FASTQ checks the verdict is line 1's, measured even when it is not kept.
+
+namespace {
+// One measured line: its tables on the device until a handle takes them.
+struct RecPass {
+    uint32_t line = 0, flags = 0;
+    int out = -1;                                         // the handle it becomes (-1: measured for the verdict only)
+    uint64_t n_seqs = 0;                                  // the records it measures
+    uint64_t *starts = nullptr, *at = nullptr;
+    uint64_t total = 0, longest = 0;
+};
+struct RecPasses {
+    std::vector<RecPass> v;
+    ~RecPasses() {
+        for (RecPass &p : v)
+            for (void *q : {(void *)p.starts, (void *)p.at})
+                if (q) (void)hipFree(q);
+    }
+};
+
+int rec_lines_check_args(const uint8_t *text, uint64_t n, uint32_t period, const uint32_t *lines, uint32_t n_kept, uint32_t flags) {
+    if ((!text && n) || !lines) return fail(FZ_EINVAL, "null argument");
+    if (flags & ~FZ_REC_FASTQ_CHECKS) return fail(FZ_EINVAL, "unknown record flags");
+    if (period == 0 || n_kept == 0 || n_kept > period) return fail(FZ_EINVAL, "between 1 and lines_per_record lines are kept");
+    for (uint32_t i = 0; i < n_kept; ++i) {
+        if (lines[i] >= period) return fail(FZ_EINVAL, "a kept line must be smaller than lines_per_record");
+        for (uint32_t k = 0; k < i; ++k)
+            if (lines[k] == lines[i]) return fail(FZ_EINVAL, "line %u is kept twice", lines[i]);
+    }
+    if ((flags & FZ_REC_FASTQ_CHECKS) && period != 4) return fail(FZ_EINVAL, "the FASTQ checks take 4 lines per record");
+    if (n >= (1ull << FZ_IDX_BITS)) return fail(FZ_EUNSUPPORTED, "sequence too long");
+    return FZ_OK;
+}
+}  // namespace
+
+int fz_batch_upload_records_lines(fz_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t lines_per_record, const uint32_t *lines,
+                                  uint32_t n_kept, uint32_t flags, fz_seq **outs, fz_records_info *info) {
+    if (!ctx || !outs) return fail(FZ_EINVAL, "null argument");
+    if (info) *info = fz_records_info{};
+    int rc = rec_lines_check_args(text, n, lines_per_record, lines, n_kept, flags);
+    if (rc) return rc;                                    // (n_kept is not known to be the length of outs[] before this)
+    for (uint32_t i = 0; i < n_kept; ++i) outs[i] = nullptr;
+    if ((rc = batch_upload_admit(ctx))) return rc;
+    Ingest in(ctx, "records");
+    DevState &d = in.d;
+    const bool checks = (flags & FZ_REC_FASTQ_CHECKS) != 0;
+    if (checks) n = rec_trim(text, n);
+    // 1. the line table, once
+    uint64_t n_nl = 0, n_lines = 0;
+    if ((rc = in.line_table(text, n, &n_nl, &n_lines))) return rc;
+    uint64_t n_seqs = ~0ull;                              // the records in which every kept line exists
+    for (uint32_t i = 0; i < n_kept; ++i) n_seqs = std::min(n_seqs, fz_rec_n_seqs(n_lines, lines_per_record, lines[i]));
+    if (info) { info->n_lines = n_lines; info->n_seqs = n_seqs; }
+    if (n_seqs >= (1ull << 32)) return fail(FZ_EUNSUPPORTED, "more than 2^32 - 1 sequences in a batch");
+    // 2. one lane per record and the scan of the lengths, per line; line 1 carries the FASTQ verdict
+    RecPasses ps;
+    bool has_verdict_line = false;
+    for (uint32_t i = 0; i < n_kept; ++i) has_verdict_line |= lines[i] == 1u;
+    if (checks && !has_verdict_line) {                    // (over the records whose line 1 exists, as the single-line call)
+        ps.v.emplace_back();
+        ps.v.back().line = 1u; ps.v.back().flags = flags; ps.v.back().n_seqs = fz_rec_n_seqs(n_lines, lines_per_record, 1u);
+    }
+    for (uint32_t i = 0; i < n_kept; ++i) {
+        ps.v.emplace_back();
+        ps.v.back().line = lines[i]; ps.v.back().out = (int)i; ps.v.back().n_seqs = n_seqs;
+        ps.v.back().flags = (checks && lines[i] == 1u) ? flags : 0u;
+    }
+    const size_t np = ps.v.size();
+    uint64_t key = fz_rec_count_key(n_lines, lines_per_record, flags);
+    bool measured = false;
+    if ((rc = rec_malloc(&in.info, 2 * np))) return rc;
+    for (size_t i = 0; i < np; ++i) {
+        RecPass &p = ps.v[i];
+        if (!p.n_seqs) continue;
+        measured = true;
+        if ((rc = rec_malloc(&p.starts, p.n_seqs))) return rc;
+        if ((rc = rec_malloc(&p.at, p.n_seqs + 1))) return rc;
+        HIP_TRY(hipMemsetAsync(in.info + 2 * i, 0xff, sizeof(uint64_t), d.stream));
+        HIP_TRY(hipMemsetAsync(in.info + 2 * i + 1, 0, sizeof(uint64_t), d.stream));
+        hipLaunchKernelGGL(fz_rec_measure_kernel, dim3(rec_grid(d, (p.n_seqs + FZ_REC_THREADS - 1) / FZ_REC_THREADS)), dim3(FZ_REC_THREADS), 0, d.stream,
+                           in.raw, n, in.nl, n_nl, n_lines, lines_per_record, p.line, p.flags, p.n_seqs, p.starts, p.at, in.info + 2 * i);
+        if ((rc = in.scan(p.at, p.n_seqs + 1))) return rc;
+    }
+    in.mark();
+    if (measured) {
+        std::vector<unsigned long long> got(2 * np, 0ull);
+        HIP_TRY(hipMemcpyAsync(got.data(), in.info, got.size() * sizeof(got[0]), hipMemcpyDeviceToHost, d.stream));
+        for (RecPass &p : ps.v)
+            if (p.n_seqs) HIP_TRY(hipMemcpyAsync(&p.total, p.at + p.n_seqs, sizeof(uint64_t), hipMemcpyDeviceToHost, d.stream));
+        HIP_TRY(hipStreamSynchronize(d.stream));
+        for (size_t i = 0; i < np; ++i) {
+            if (!ps.v[i].n_seqs) continue;
+            key = std::min<uint64_t>(key, got[2 * i]);
+            ps.v[i].longest = got[2 * i + 1];
+        }
+        if (key == FZ_REC_NO_ERROR)
+            for (const RecPass &p : ps.v)
+                if (p.total > n || p.longest > p.total) return fail(FZ_EDEVICE, "records: the packed length is outside the text");
+    }
+    if (key != FZ_REC_NO_ERROR) return rec_report(checks ? "fastq" : "lines", key, info);
+    // 3. the handles, their bytes gathered on the device
+    double kernels_ms = 0, d2h_ms = 0;
+    std::vector<fz_seq *> made;
+    for (RecPass &p : ps.v) {
+        if (p.out < 0) continue;
+        fz_seq *seq = nullptr;
+        double one_d2h = 0;
+        const uint64_t *at = p.at;                        // (batch_make_handle takes p.at over: the gather is enqueued before that)
+        rc = batch_make_handle(ctx, n_seqs, p.total, p.longest, nullptr, p.at, &one_d2h, &seq, [&](uint8_t *d_buf) {
+            if (in.timed) (void)hipEventRecord(d.rec_ev[5], d.stream);
+            if (p.total)
+                hipLaunchKernelGGL(fz_rec_gather_kernel, dim3(rec_grid(d, (p.total + FZ_TILE_BYTES - 1) / FZ_TILE_BYTES)), dim3(FZ_REC_THREADS), 0,
+                                   d.stream, in.raw, p.starts, at, n_seqs, p.total, d_buf);
+            if (in.timed) (void)hipEventRecord(d.rec_ev[6], d.stream);
+            return FZ_OK;
+        });
+        if (rc) break;
+        if (n_seqs) { seq->d_src_starts = p.starts; p.starts = nullptr; }
+        if (in.timed) kernels_ms += span_ms(d.rec_ev[5], d.rec_ev[6]);      // (the handle's builder has waited for the stream)
+        d2h_ms += one_d2h;
+        made.push_back(seq);
+        if (p.out == 0 && info) info->packed_bytes = p.total;
+    }
+    if (rc) {
+        for (fz_seq *s : made) fz_seq_release(s);
+        if (info) info->packed_bytes = 0;
+        return rc;
+    }
+    if (in.timed) {
+        ctx->rec_ms[0] = span_ms(d.rec_ev[0], d.rec_ev[1]);
+        ctx->rec_ms[1] = span_ms(d.rec_ev[1], d.rec_ev[2]) + span_ms(d.rec_ev[3], d.rec_ev[4]) + kernels_ms;
+        ctx->rec_ms[2] = d2h_ms;
+    }
+    ctx->rec_ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - in.t_call).count();
+    size_t k = 0;
+    for (const RecPass &p : ps.v)
+        if (p.out >= 0) { ctx->live.push_back(made[k]); outs[p.out] = made[k]; ++k; }
+    return FZ_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Formatted text (fz_batch_format): the egress end.  The descriptor goes up, one lane per record measures and checks it
+// (fz_kernels.h: fz_format_measure_kernel), the records path's scan places the records, the gather writes the text into a
+// transient buffer of whole tiles, and one copy brings it to the caller's buffer.
+
+namespace {
+static_assert(sizeof(fz_format_info) == 40, "fz_format_info");
+static_assert(FZ_FMT_MAX_COLS == FZ_FORMAT_MAX_COLUMNS && FZ_FMT_MAX_LIT == FZ_FORMAT_MAX_LITERAL && FZ_FMT_NO_CHECK == FZ_FORMAT_NO_CHECK,
+              "fz_device.h and fzhip.h state the same limits");
+
+const char *fmt_reason_text(uint32_t reason) {
+    if (reason == FZ_FMT_E_EQUAL) return "the two columns checked for equal length differ in length";
+    return "bad record";
+}
+
+int fmt_report(uint64_t key, fz_format_info *info) {
+    if (info) { info->bad_record = fz_rec_err_record(key); info->bad_reason = fz_rec_err_reason(key); }
+    return fail(FZ_EINVAL, "format: record %llu: %s", (unsigned long long)fz_rec_err_record(key), fmt_reason_text(fz_rec_err_reason(key)));
+}
+
+// The descriptor's host half: the literals and the pair to check.  -> the literals' total per record.
+int fmt_describe(uint32_t n_columns, const uint8_t *literals, const uint32_t *literal_lens, uint32_t equal_a, uint32_t equal_b,
+                 FzFmtDesc &desc, uint64_t *lit_total) {
+    if (n_columns == 0 || n_columns > FZ_FMT_MAX_COLS) return fail(FZ_EINVAL, "between 1 and %u columns are formatted", FZ_FMT_MAX_COLS);
+    if (!literal_lens) return fail(FZ_EINVAL, "null argument");
+    memset(&desc, 0, sizeof desc);
+    desc.n_cols = n_columns;
+    uint32_t at = 0;
+    for (uint32_t c = 0; c <= n_columns; ++c) {
+        if (literal_lens[c] > FZ_FMT_MAX_LIT) return fail(FZ_EINVAL, "literal %u is longer than %u bytes", c, FZ_FMT_MAX_LIT);
+        desc.lit_off[c] = at;
+        at += literal_lens[c];
+    }
+    desc.lit_off[n_columns + 1u] = at;
+    if (at && !literals) return fail(FZ_EINVAL, "null argument");
+    if (at && literals) memcpy(desc.lits, literals, at);
+    const bool check = equal_a != FZ_FMT_NO_CHECK && equal_b != FZ_FMT_NO_CHECK;
+    if (check && (equal_a >= n_columns || equal_b >= n_columns)) return fail(FZ_EINVAL, "the columns checked for equal length are columns of the call");
+    desc.equal_a = check ? equal_a : FZ_FMT_NO_CHECK;
+    desc.equal_b = check ? equal_b : FZ_FMT_NO_CHECK;
+    *lit_total = at;
+    return FZ_OK;
+}
+
+// sum + n * lit_total, or ~0 when it does not fit.
+uint64_t fmt_text_bytes(uint64_t sum, uint64_t n, uint64_t lit_total) {
+    if (lit_total && n > (~0ull - sum) / lit_total) return ~0ull;
+    return sum + n * lit_total;
+}
+
+struct FmtTables {
+    FzFmtDesc *desc = nullptr;
+    ~FmtTables() { if (desc) (void)hipFree(desc); }
+};
+}  // namespace
+
+int fz_batch_format(fz_ctx *ctx, fz_seq *const *columns, uint32_t n_columns, const uint8_t *literals, const uint32_t *literal_lens,
+                    uint32_t equal_a, uint32_t equal_b, uint8_t *out, uint64_t cap, fz_format_info *info) {
+    if (!ctx || !columns) return fail(FZ_EINVAL, "null argument");
+    if (info) *info = fz_format_info{};
+    int rc = batch_upload_admit(ctx);
+    if (rc) return rc;
+    FzFmtDesc desc;
+    uint64_t lit_total = 0, sum = 0;
+    if ((rc = fmt_describe(n_columns, literals, literal_lens, equal_a, equal_b, desc, &lit_total))) return rc;
+    for (uint32_t c = 0; c < n_columns; ++c) {
+        fz_seq *col = columns[c];
+        if (!col || std::find(ctx->live.begin(), ctx->live.end(), col) == ctx->live.end())
+            return fail(FZ_EINVAL, "fz_batch_format: column %u is no live batch handle of this context", c);
+        if (!col->is_batch) return fail(FZ_EINVAL, "fz_batch_format: column %u is no batch handle", c);
+        if (col->shards.size() != 1) return fail(FZ_EUNSUPPORTED, "batches are formatted on one device");
+        if (col->n_seqs != columns[0]->n_seqs)
+            return fail(FZ_EINVAL, "fz_batch_format: column %u has %llu sequences, column 0 has %llu", c, (unsigned long long)col->n_seqs,
+                        (unsigned long long)columns[0]->n_seqs);
+        sum += col->n;                                    // (each below 2^48, at most 8 of them)
+        desc.col[c].bytes = col->shards[0].d_buf;
+        desc.col[c].offs = col->d_ends_base;
+    }
+    const uint64_t n = columns[0]->n_seqs;
+    const uint64_t text_bytes = fmt_text_bytes(sum, n, lit_total);
+    if (text_bytes >= (1ull << FZ_IDX_BITS)) return fail(FZ_EUNSUPPORTED, "the text is too long");
+    if (info) { info->n_records = n; info->text_bytes = text_bytes; }
+    if (cap < text_bytes) return fail(FZ_EINVAL, "the buffer is smaller than the text");
+    if (!out && text_bytes) return fail(FZ_EINVAL, "null argument");
+    Ingest in(ctx, "format");
+    DevState &d = in.d;
+    FmtTables tb;
+    HIP_TRY(hipSetDevice(d.device));
+    if (in.timed) for (auto &ev : d.rec_ev) if (!ev) HIP_TRY(hipEventCreate(&ev));
+    // 1. the descriptor
+    in.mark();
+    if (n) {
+        if ((rc = rec_malloc_bytes(reinterpret_cast<void **>(&tb.desc), sizeof desc))) return rc;
+        HIP_TRY(hipMemcpyAsync(tb.desc, &desc, sizeof desc, hipMemcpyHostToDevice, d.stream));
+    }
+    in.mark();
+    // 2. one lane per record; the scan of the lengths
+    uint64_t key = FZ_REC_NO_ERROR, total = 0, longest = 0;
+    in.n = text_bytes;
+    if (n) {
+        if ((rc = rec_malloc(&in.at, n + 1))) return rc;
+        if ((rc = in.arm_verdict())) return rc;
+        hipLaunchKernelGGL(fz_format_measure_kernel, dim3(rec_grid(d, (n + FZ_REC_THREADS - 1) / FZ_REC_THREADS)), dim3(FZ_REC_THREADS), 0, d.stream,
+                           tb.desc, n, in.at, in.info);
+        if ((rc = in.scan(in.at, n + 1))) return rc;
+    }
+    in.mark();
+    if (n && (rc = in.read_verdict(n, &key, &total, &longest))) return rc;
+    if (key != FZ_REC_NO_ERROR) return fmt_report(key, info);
+    if (total != text_bytes) return fail(FZ_EDEVICE, "format: the measured length is not the text's");
+    if (info) info->longest_record = longest;
+    // 3. the text, gathered into whole tiles, and its copy to the caller
+    double d2h_ms = 0;
+    in.mark();
+    if (total) {
+        const uint64_t ntiles = (total + FZ_TILE_BYTES - 1) / FZ_TILE_BYTES;
+        if ((rc = rec_malloc_bytes(reinterpret_cast<void **>(&in.raw), ntiles * FZ_TILE_BYTES))) return rc;
+        hipLaunchKernelGGL(fz_format_gather_kernel, dim3(rec_grid(d, ntiles)), dim3(FZ_REC_THREADS), 0, d.stream, tb.desc, in.at, n, total, in.raw);
+    }
+    in.mark();
+    if (total) {
+        // a timed call waits for the gather here, so that the host clock around the copy holds the copy alone
+        if (in.timed) HIP_TRY(hipStreamSynchronize(d.stream));
+        const auto t0 = std::chrono::steady_clock::now();
+        HIP_TRY(hipMemcpyAsync(out, in.raw, total, hipMemcpyDeviceToHost, d.stream));
+        HIP_TRY(hipStreamSynchronize(d.stream));
+        d2h_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    for (int i = 0; i < 4; ++i) ctx->fmt_ms[i] = 0;       // (an untimed call leaves no spans of an earlier one behind)
+    if (in.timed) {
+        ctx->fmt_ms[0] = span_ms(d.rec_ev[0], d.rec_ev[1]);
+        ctx->fmt_ms[1] = span_ms(d.rec_ev[1], d.rec_ev[2]);
+        ctx->fmt_ms[2] = span_ms(d.rec_ev[3], d.rec_ev[4]);
+        ctx->fmt_ms[3] = d2h_ms;
+    }
+    ctx->fmt_ms[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - in.t_call).count();
+    return FZ_OK;
+}
+
+int fz_debug_format_ms(fz_ctx *ctx, double *ms5) {
+    if (!ctx || !ms5) return fail(FZ_EINVAL, "null argument");
+    for (int i = 0; i < 5; ++i) ms5[i] = ctx->fmt_ms[i];
+    return FZ_OK;
+}
+
+int fz_debug_format_plan(const uint64_t *const *offs, uint32_t n_columns, uint64_t n, const uint32_t *literal_lens,
+                         uint32_t equal_a, uint32_t equal_b, uint64_t *at, fz_format_info *info) {
+    if (!offs || !at || !info) return fail(FZ_EINVAL, "null argument");
+    *info = fz_format_info{};
+    FzFmtDesc desc;
+    uint64_t lit_total = 0, sum = 0;
+    static const uint8_t no_bytes[(FZ_FMT_MAX_COLS + 1u) * FZ_FMT_MAX_LIT] = {};
+    if (int rc = fmt_describe(n_columns, no_bytes, literal_lens, equal_a, equal_b, desc, &lit_total)) return rc;
+    for (uint32_t c = 0; c < n_columns; ++c) {
+        if (!offs[c]) return fail(FZ_EINVAL, "null argument");
+        desc.col[c].offs = offs[c];
+        sum += offs[c][n] - offs[c][0];
+    }
+    const uint64_t text_bytes = fmt_text_bytes(sum, n, lit_total);
+    if (text_bytes >= (1ull << FZ_IDX_BITS)) return fail(FZ_EUNSUPPORTED, "the text is too long");
+    info->n_records = n; info->text_bytes = text_bytes;
+    uint64_t key = FZ_REC_NO_ERROR, total = 0, longest = 0;
+    for (uint64_t j = 0; j < n; ++j) {
+        const FzFmtRec o = fz_format_record(desc, j);
+        if (o.reason != FZ_REC_OK) key = std::min(key, fz_rec_err_key(j, o.reason));
+        at[j] = total;
+        total += o.len;
+        longest = std::max(longest, o.len);
+    }
+    at[n] = total;
+    if (key != FZ_REC_NO_ERROR) return fmt_report(key, info);
+    info->longest_record = longest;
     return FZ_OK;
 }
 

@@ -12,6 +12,10 @@ What a line is: it ends at ``\\n`` or, the last one, at the end of the text; one
                      line count is a multiple of 4, the first line starts with ``@``, the third with ``+``, the fourth is as
                      long as the second.  The first malformed record raises ``ValueError`` naming it.
 
+``lines=(0, 1, 3)`` keeps several lines of every record — a FASTQ file's headers, bases and qualities — as one RecordBatch each,
+from ONE upload of the text and one line table (fz_batch_upload_records_lines): what ``format_records`` (egress.py) takes to
+write the file back.  The FASTQ checks are the same whichever lines are kept.
+
 Not understood: FASTQ records whose sequence spans several lines and compressed files — decompress and pass the bytes.
 FASTA (newlines inside a sequence have to be removed, which is another gather) is ``resident_fasta``'s (fasta.py).
 """
@@ -64,12 +68,14 @@ class RecordSequences(object):
 
 class RecordBatch(BatchSequences):
     """A BatchSequences made from a text of records.  ``starts[j]`` = offset of sequence j's first byte in the source,
-    ``lengths[j]`` its length (numpy uint64); ``sequences`` cuts ``bytes`` from the source, which is kept alive, on demand."""
+    ``lengths[j]`` its length (numpy uint64); ``sequences`` cuts ``bytes`` from the source, which is kept alive, on demand.
+    ``line``: the line of every record that the sequences are."""
 
     def __init__(self, source, format='fastq', engine=None):
         if format not in _native.RECORD_FORMATS:
             raise ValueError('unknown record format %r (known: %s)' % (format, ', '.join(sorted(_native.RECORD_FORMATS))))
         self.format = format
+        self.line = _native.RECORD_FORMATS[format][1]
         self.source = _open_source(source)
         self.engine = engine or _native.default_engine()
         self.handle = None
@@ -87,11 +93,55 @@ class RecordBatch(BatchSequences):
             view = RecordSequences(self.source, self.starts, self.lengths)
             self.sequences = list(view)
 
+    @classmethod
+    def _of_line(cls, source, format, engine, line, handle):
+        """The batch of one kept line of a several-line upload (handle: its batch handle; None: split on the host)."""
+        self = cls.__new__(cls)
+        self.format, self.line, self.source, self.engine, self.handle, self.kind = format, line, source, engine, handle, None
+        if handle is not None:
+            self.kind = 'bytes'
+            self.starts, ends = engine.batch_tables(handle)
+            self.lengths = ends.copy()
+            if len(ends) > 1:
+                self.lengths[1:] -= ends[:-1]
+            self.sequences = RecordSequences(source, self.starts, self.lengths)
+        else:
+            self.starts, self.lengths = split_records(source, format, line)
+            self.sequences = list(RecordSequences(source, self.starts, self.lengths))
+        return self
 
-def resident_records(source, format='fastq', engine=None):
+
+def _kept_lines(format, lines):
+    period = _native.RECORD_FORMATS[format][0]
+    kept = [l.__index__() for l in lines]
+    if not 1 <= len(kept) <= period:
+        raise ValueError('between 1 and %d lines of a %s record are kept, not %d' % (period, format, len(kept)))
+    for l in kept:
+        if not 0 <= l < period:
+            raise ValueError('a %s record has the lines 0 .. %d, not %d' % (format, period - 1, l))
+    if len(set(kept)) != len(kept):
+        raise ValueError('a line is kept twice')
+    return kept
+
+
+def resident_records(source, format='fastq', engine=None, lines=None):
     """``source`` (bytes-like, or the path of a file, which is mapped read-only) -> a RecordBatch: its sequences resident in
-    device memory, usable as ``sequences`` of the batch searches.  ``format``: 'fastq' or 'lines' (module docstring)."""
-    return RecordBatch(source, format, engine)
+    device memory, usable as ``sequences`` of the batch searches.  ``format``: 'fastq' or 'lines' (module docstring).
+    ``lines``: several lines of every record, e.g. ``(0, 1, 3)`` of a FASTQ file -> a tuple of RecordBatch, one per entry in
+    that order, from one upload; they share the one source object."""
+    if lines is None:
+        return RecordBatch(source, format, engine)
+    if format not in _native.RECORD_FORMATS:
+        raise ValueError('unknown record format %r (known: %s)' % (format, ', '.join(sorted(_native.RECORD_FORMATS))))
+    kept = _kept_lines(format, lines)
+    source = _open_source(source)
+    engine = engine or _native.default_engine()
+    if _single_device(engine):
+        period, _line, flags = _native.RECORD_FORMATS[format]
+        handles = engine.upload_records_lines(source, period, kept, flags)
+    else:                                           # the batched call does not serve this engine: split in plain Python
+        handles = [None] * len(kept)
+    return tuple(RecordBatch._of_line(source, format, engine, l, h) for l, h in zip(kept, handles))
 
 
 def _open_source(source):
@@ -130,9 +180,12 @@ def _refuse(format, bad):
         raise ValueError('%s: record %d: %s' % (format, r, _REASONS[why]))
 
 
-def split_records(source, format):
-    """The split on the host, in plain Python (engines the batched call does not serve) -> (starts, lengths)."""
+def split_records(source, format, line=None):
+    """The split on the host, in plain Python (engines the batched call does not serve) -> (starts, lengths) of line ``line``
+    of every record (None: the format's sequence line)."""
     period, phase, flags = _native.RECORD_FORMATS[format]
+    if line is not None:
+        phase = line
     data = bytes(source)
     spans = [(s, n) for s, n, _w in _line_spans(data, trim=bool(flags & _native.REC_FASTQ_CHECKS))]
     if flags & _native.REC_FASTQ_CHECKS:

@@ -454,6 +454,53 @@ int fz_debug_derive_plan(const uint64_t *offs, uint64_t n_src, const uint32_t *i
                          uint64_t n_out, uint64_t *src, uint64_t *at, fz_derive_info *info);
 int fz_debug_derive_ms(fz_ctx *ctx, double *ms5);
 
+/* Several lines of every record: fz_batch_upload_records for n_kept lines of each record from ONE copy of the text and ONE
+ * line table.  lines[i] < lines_per_record names the line of handle outs[i]; 1 <= n_kept <= lines_per_record, a repeated
+ * entry is FZ_EINVAL.  Measure, scan and gather run once per kept line with the kernels of fz_batch_upload_records; every
+ * kept line gets a batch handle of its own, all with the same number of sequences: the records in which every kept line
+ * exists.  With FZ_REC_FASTQ_CHECKS (lines_per_record = 4; any lines) trailing empty lines are dropped first and the FASTQ
+ * verdict is computed once, by the measure at line 1 whether or not line 1 is kept, and reported exactly as
+ * fz_batch_upload_records reports it; the other lines are measured without checks over the trimmed text.  On any error
+ * every handle already made is released and all outs[] are NULL.  *info is filled for line lines[0].  Refusals as
+ * fz_batch_upload_records.  fz_debug_records_ms afterwards: {H2D copy, the kernels of all lines, the D2H of all ends[], whole call}. */
+int fz_batch_upload_records_lines(fz_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t lines_per_record, const uint32_t *lines,
+                                  uint32_t n_kept, uint32_t flags, fz_seq **outs, fz_records_info *info);
+
+/* Formatted text: batches become the text of a file, assembled in device memory.  The rule:
+ *     text = join over j < n of  lit[0] + col[0][j] + lit[1] + col[1][j] + ... + col[C - 1][j] + lit[C]
+ *   columns: C live batch handles of this context (1 <= C <= FZ_FORMAT_MAX_COLUMNS) with n sequences each; a column may
+ *   appear twice; they stay as they are.  literals: the C + 1 byte strings back to back, literal_lens: their lengths, each
+ *   at most FZ_FORMAT_MAX_LITERAL.  equal_a / equal_b: two columns whose sequences must be of one length in every record
+ *   (FASTQ: bases and qualities), or FZ_FORMAT_NO_CHECK for either.  A record in which they differ is bad (reason 1); the
+ *   smallest bad record is an error: FZ_EINVAL, info->bad_record / bad_reason filled in, nothing written to `out`, nothing
+ *   left allocated.  The text's length, sum(fz_seq_len(col)) + n * sum(literal_lens), is known before anything runs: `out`
+ *   is the caller's buffer of `cap` bytes, and a cap smaller than the text is FZ_EINVAL.
+ * On the device (fz_kernels.h: fz_format_*_kernel): one lane per record measures and checks it, the lengths are scanned as
+ * fz_batch_upload_records scans them, the text is gathered by 16-byte pieces of the destination from the columns' packed
+ * bytes and the literals, then one copy of the text to `out`.  All device memory of the call is transient.
+ * Refusals as fz_batch_derive's: a column that is no live batch handle of this context, columns with different numbers of
+ * sequences (the column is named), several devices or a communicator, a search in flight, a text of 2^48 bytes or more. */
+#define FZ_FORMAT_MAX_COLUMNS 8u
+#define FZ_FORMAT_MAX_LITERAL 255u
+#define FZ_FORMAT_NO_CHECK 0xffffffffu
+typedef struct {
+    uint64_t n_records, text_bytes, longest_record, bad_record;
+    uint32_t bad_reason;
+} fz_format_info;
+
+int fz_batch_format(fz_ctx *ctx, fz_seq *const *columns, uint32_t n_columns, const uint8_t *literals, const uint32_t *literal_lens,
+                    uint32_t equal_a, uint32_t equal_b, uint8_t *out, uint64_t cap, fz_format_info *info);
+/* Test hooks.  fz_debug_format_plan: no device; the measure step and the scan on the host through the function the kernel
+ * runs (fz_device.h: fz_format_record).  offs[c] = column c's n + 1 offsets (the same pointer twice: a column twice); at[]
+ * (n + 1 entries: the records' starts in the text, its length last) is the caller's; the verdict as above, in *info.
+ * fz_debug_format_ms: device and host spans of the context's last fz_batch_format, milliseconds: {the descriptor's H2D copy,
+ * measure + scan, the gather (hipEvents on the stream), the D2H of the text (host clock, started once the gather has
+ * finished), whole call}.  With timing off (fz_set_timing) the first four are 0 and the call does not wait for the gather
+ * on its own. */
+int fz_debug_format_plan(const uint64_t *const *offs, uint32_t n_columns, uint64_t n, const uint32_t *literal_lens,
+                         uint32_t equal_a, uint32_t equal_b, uint64_t *at, fz_format_info *info);
+int fz_debug_format_ms(fz_ctx *ctx, double *ms5);
+
 /* has_near_match_* (substitutions_only.py:139-145, :218-233; generic_search.py:240-253): *found = 1 iff the
  * corresponding search would return at least one record.  Nothing is ordered or copied, and device work that starts
  * after the first record has been counted is skipped (workgroups of the scan, hits of the automaton kernel). */
