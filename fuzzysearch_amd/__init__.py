@@ -32,6 +32,7 @@ from .multi import find_near_matches_multi
 from .batch import find_near_matches_batch, resident_batch
 from .multi_batch import find_near_matches_multi_batch
 from .assign import find_best_matches_batch, BestMatches
+from .overlap import find_end_overlaps_batch, EndOverlaps
 from .records import resident_records, RecordBatch
 from .fasta import resident_fasta, FastaBatch
 from .classes import IUPAC_DNA
@@ -48,6 +49,8 @@ __all__ = [
     'find_near_matches_multi_batch',
     'find_best_matches_batch',
     'BestMatches',
+    'find_end_overlaps_batch',
+    'EndOverlaps',
     'IUPAC_DNA',
     'Match',
     'resident',

@@ -110,6 +110,9 @@ PROTOTYPES = {
     "fz_batch_search_multi": (ci, (vp, vp, u32, bp, u64p, u32, u32, ci, mpp, u32pp, u64pp)),
     "fz_batch_assign": (ci, (vp, vp, u32, bp, u64p, u32, u32, vpp)),
     "fz_debug_assign_fold": (ci, (vp, u64, vp, u64, u32, vp, u32, vp, u32, u32, vp)),
+    "fz_batch_end_overlaps": (ci, (vp, vp, u32, bp, u64p, u32, u32, u32, vpp)),
+    "fz_debug_end_overlaps": (ci, (u32, bp, u64p, u32, u32, u32, bp, vp, u64, vp)),
+    "fz_debug_overlap_ms": (ci, (vp, f64p)),
     "fz_subs_ngrams_multi_cls": _MULTI_CLS,
     "fz_subs_ngrams_multi_best_cls": _MULTI_CLS,
     "fz_batch_search_multi_cls": (ci, (vp, vp, bp, u64p, u32, u32, bp, bp, ci, mpp, u32pp, u64pp)),
@@ -184,6 +187,7 @@ EXPORTED_SYMBOLS = tuple(PROTOTYPES)
 # symbol is mandatory at load time.
 OPTIONAL = frozenset((
     "fz_batch_search_multi", "fz_batch_assign", "fz_debug_assign_fold",
+    "fz_batch_end_overlaps", "fz_debug_end_overlaps", "fz_debug_overlap_ms",
     "fz_subs_ngrams_multi_cls", "fz_subs_ngrams_multi_best_cls", "fz_batch_search_multi_cls", "fz_batch_assign_cls",
     "fz_debug_multi_plan_cls",
     "fz_batch_upload_records", "fz_batch_tables", "fz_debug_batch_bytes", "fz_debug_records_split", "fz_debug_scan_items",
@@ -671,6 +675,32 @@ def assign_fold(offs, recs, L, pat_table, pat_m, k):
     return out
 
 
+_OVERLAP_DTYPE = None
+
+
+def overlap_dtype():
+    """The numpy dtype of an fz_overlap row (include/fzhip.h): start, pattern (0xffff: none, then start = the length), overlap, dist."""
+    global _OVERLAP_DTYPE
+    if _OVERLAP_DTYPE is None:
+        import numpy as np
+        _OVERLAP_DTYPE = np.dtype([("start", "<u4"), ("pattern", "<u2"), ("overlap", "u1"), ("dist", "u1")])
+    return _OVERLAP_DTYPE
+
+
+def end_overlaps_twin(mode, patterns, k, min_overlap, blob, offs):
+    """fz_debug_end_overlaps (no device): fz_batch_end_overlaps on the host, through the functions its kernels' lanes run and
+    with its refusals.  blob: the packed sequences; offs: their n_seqs + 1 offsets -> fz_overlap structured array of n_seqs rows."""
+    import numpy as np
+    lib = load_library()
+    pats, poffs = pack_patterns(list(patterns))
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    blob = bytes(blob)
+    out = np.empty(len(offs) - 1, dtype=overlap_dtype())
+    _check(_entry(lib, 'fz_debug_end_overlaps')(mode, pats, poffs, len(patterns), k, min_overlap, blob, offs[1:].ctypes.data, len(offs) - 1,
+                                                out.ctypes.data))
+    return out
+
+
 class OwnedRows(object):
     """A C-ABI result buffer (fz_match rows) that has not been copied anywhere: address, n, and fz_free on release."""
     __slots__ = ('_lib', '_ptr', 'n')
@@ -1058,6 +1088,24 @@ class Engine(object):
         with self._lock:
             _check(fn(self._h, batch._h, *args, ctypes.byref(ptr)))
         return _take_assign_array(self._lib, ptr.value, batch.n_seqs)     # (a plain handle was refused above)
+
+    def batch_end_overlaps(self, batch, mode, patterns, k, min_overlap):
+        """fz_batch_end_overlaps: per sequence of the batch the pattern whose strictly partial prefix ends it -> a structured
+        array (overlap_dtype) of one row per sequence over the library's buffer: start, pattern (0xffff: none), overlap, dist."""
+        patterns = list(patterns)
+        blob, offs = pack_patterns(patterns)
+        fn = _entry(self._lib, "fz_batch_end_overlaps")
+        ptr = ctypes.c_void_p()
+        with self._lock:
+            _check(fn(self._h, batch._h, mode, blob, offs, len(patterns), k, min_overlap, ctypes.byref(ptr)))
+        return _take_rows(self._lib, ptr.value, batch.n_seqs, overlap_dtype())
+
+    def overlap_ms(self):
+        """fz_debug_overlap_ms: {tables_h2d, kernels, rows_d2h, call} milliseconds of this engine's last batch_end_overlaps."""
+        ms = (ctypes.c_double * 4)()
+        with self._lock:
+            _check(_entry(self._lib, 'fz_debug_overlap_ms')(self._h, ms))
+        return {'tables_h2d': ms[0], 'kernels': ms[1], 'rows_d2h': ms[2], 'call': ms[3]}
 
     # the class calls by their names of old: substitutions mode, tables = (pmask, tmask) of classes.class_tables
     def batch_multi_rows_call_classes(self, batch, patterns, k, tables, reduced=True):

@@ -1810,3 +1810,199 @@ FZ_HD uint64_t fz_format_run_lo(const FzFmtDesc &d, uint64_t j, const FzFmtCur &
 FZ_HD const uint8_t *fz_format_byte_src(const FzFmtDesc &d, uint64_t j, const FzFmtCur &g) {
     return (g.seg & 1u) ? d.col[g.seg >> 1].bytes + fz_format_run_lo(d, j, g) : d.lits + d.lit_off[g.seg >> 1] + g.off;
 }
+
+// ---------------------------------------------------------------------------------------------
+// End overlaps (fz_batch_end_overlaps; fz_kernels.h: fz_overlap_kernel): a PREFIX of a pattern at the END of a read, the
+// adapter that a read runs into and breaks off in.  Per read r (n bytes), pattern p (m bytes), budget k and smallest
+// overlap o, over the strictly partial prefix lengths o <= i <= m - 1 with the scaled budget k_i = k * i / m:
+//   Levenshtein     E(i) = min over a of ed(p[:i], r[a:]),  j(i) = the longest suffix of r at that distance
+//   substitutions   E(i) = Hamming(p[:i], r[n - i:]) for i <= n,  j(i) = i
+// i qualifies when E(i) <= k_i; the pattern answers with the i of the most matched characters i - E(i), then the smaller
+// E(i); the read answers with the pattern of the largest i - d, then the smaller d, then the lower list position.  That order
+// is the order of ONE unsigned key, so a read's answer is a maximum (0: none):
+//   key = (i - d) << 40 | (255 - d) << 32 | (65535 - pattern) << 16 | j
+#define FZ_OVL_MAX_M 64u               // one 64-bit column vector
+#define FZ_OVL_MAX_K 16u
+#define FZ_OVL_MAX_PATS 65534u         // 0xffff in a row's pattern field = none
+#define FZ_OVL_ROW_BYTES 64u           // a pattern's row in the call's table: its bytes, zeros behind them
+#define FZ_OVL_CHUNK_LEV 8u            // patterns per launch: two Peq tables of 2 KiB each per pattern in LDS
+#define FZ_OVL_CHUNK_SUBS 64u          // ... the rows alone
+
+struct FzOverlapRow { uint32_t start; uint16_t pattern; uint8_t overlap, dist; };   // = fz_overlap
+
+FZ_HD uint32_t fz_overlap_chunk(uint32_t mode) { return mode == FZ_MODE_LEV ? FZ_OVL_CHUNK_LEV : FZ_OVL_CHUNK_SUBS; }
+// The bytes at a read's end that a pattern can reach: its longest partial prefix and what that prefix may insert.
+FZ_HD uint32_t fz_overlap_tail(uint32_t mode, uint32_t m, uint32_t k) {
+    return m ? (m - 1u) + (mode == FZ_MODE_LEV ? k * (m - 1u) / m : 0u) : 0u;
+}
+// Dwords of a staged tail of up to tmax bytes: up to 3 bytes in front of it, and one dword behind the last for the
+// two-dword steps of the substitutions form.
+FZ_HD uint32_t fz_overlap_win_dwords(uint32_t tmax) { return (tmax + 6u) / 4u + 1u; }
+
+FZ_HD uint64_t fz_overlap_key(uint32_t score, uint32_t d, uint32_t pattern, uint32_t j) {
+    return ((uint64_t)score << 40) | ((uint64_t)(255u - d) << 32) | ((uint64_t)(65535u - pattern) << 16) | j;
+}
+// (n = the read's length)
+FZ_HD FzOverlapRow fz_overlap_row(uint64_t key, uint32_t n) {
+    FzOverlapRow r;
+    r.start = n; r.pattern = 0xffffu; r.overlap = 0; r.dist = 0;
+    if (key) {
+        const uint32_t d = 255u - ((uint32_t)(key >> 32) & 0xffu);
+        r.start = n - ((uint32_t)key & 0xffffu);
+        r.pattern = (uint16_t)(65535u - ((uint32_t)(key >> 16) & 0xffffu));
+        r.overlap = (uint8_t)((uint32_t)(key >> 40) + d);
+        r.dist = (uint8_t)d;
+    }
+    return r;
+}
+
+// Word c of a pattern's Peq table in the top-aligned layout of fz_bits_column: position q at bit q + 64 - m of the forward
+// table (side 0), at bit 63 - q of the reversed one (side 1).
+FZ_HD uint64_t fz_overlap_peq_word(const uint8_t *p, uint32_t m, uint32_t c, uint32_t side) {
+    uint64_t w = 0;
+    for (uint32_t q = 0; q < m; ++q)
+        if (p[q] == c) w |= 1ull << (side ? 63u - q : q + 64u - m);
+    return w;
+}
+
+// fz_bits_column in the SEARCH form, D[0][j] = 0: the occurrence may start at any column.  The piece is the rows under `hm`
+// (any run of bits of the top-aligned layout; eq is masked to it).  Nothing enters its first row: the horizontal vectors are
+// masked to the piece before the shift and 0 is shifted in.  Rows above the piece are further rows that never match, rows
+// below it keep hp = hn = 0 and add nothing to the sum's carry; neither feeds into the piece.
+FZ_HD void fz_bits_column_search(FzBitsCol<1> &c, uint64_t eq, uint64_t hm) {
+    const uint64_t d0 = (((eq & c.vp) + c.vp) ^ c.vp) | eq | c.vn;
+    const uint64_t hp = (fz_or_not<uint64_t>(c.vn, d0 | c.vp) & hm) << 1;
+    const uint64_t hn = ((c.vp & d0) & hm) << 1;
+    c.vp = fz_or_not<uint64_t>(hn, d0 | hp);
+    c.vn = hp & d0;
+}
+
+// Where a read's tail lies once it is staged a dword at a time: the last ts = min(n, tmax) bytes of [sa, se) start `sh`
+// bytes into dword 0 of the window, which is dword wbase / 4 of the buffer; nd dwords hold them.  Every dword loaded starts
+// in front of buf_len, so a load ends inside the padding behind the data at the latest.  The up to 3 bytes in front of the
+// tail and behind the read's end belong to a neighbour or to the padding: the accessors below never hand them out.
+struct FzOvlStage { uint64_t wbase; uint32_t sh, ts, nd; };
+FZ_HD FzOvlStage fz_overlap_stage(uint64_t sa, uint64_t se, uint32_t tmax, uint64_t buf_len) {
+    FzOvlStage s;
+    const uint64_t n = se - sa;
+    s.ts = n < tmax ? (uint32_t)n : tmax;
+    const uint64_t wlo = se - s.ts;
+    s.wbase = wlo & ~(uint64_t)3;
+    s.sh = (uint32_t)(wlo - s.wbase);
+    s.nd = s.ts ? (uint32_t)((se - s.wbase + 3u) >> 2) : 0u;
+    const uint64_t resident = buf_len > s.wbase ? (buf_len - s.wbase + 3u) >> 2 : 0u;
+    if (s.nd > resident) s.nd = (uint32_t)resident;
+    return s;
+}
+FZ_HD uint32_t fz_overlap_load_dword(const uint8_t *buf, uint64_t off) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return *reinterpret_cast<const uint32_t *>(buf + off);
+#else
+    uint32_t v;
+    __builtin_memcpy(&v, buf + off, 4);
+    return v;
+#endif
+}
+// The window of one lane: dword d at win[d * stride] (the lane-transposed layout of the verification kernels: stride 64).
+FZ_HD void fz_overlap_stage_copy(const uint8_t *buf, const FzOvlStage &s, uint32_t win_dwords, uint32_t *win, uint32_t stride) {
+    for (uint32_t d0 = 0; d0 < win_dwords; d0 += 4u) {     // (four loads in flight, then their stores)
+        uint32_t x[4];
+        for (uint32_t j = 0; j < 4u; ++j) x[j] = d0 + j < s.nd ? fz_overlap_load_dword(buf, s.wbase + 4u * (d0 + j)) : 0u;
+        for (uint32_t j = 0; j < 4u; ++j)
+            if (d0 + j < win_dwords) win[(d0 + j) * stride] = x[j];
+    }
+}
+struct FzOvlWindow {
+    const uint32_t *win;
+    uint32_t stride;
+    uint32_t off;                                          // window byte offset of tail byte 0
+    FZ_HD uint32_t dword(uint32_t j) const { return win[j * stride]; }
+    FZ_HD uint32_t at(uint32_t t) const { return (win[((off + t) >> 2) * stride] >> (8u * ((off + t) & 3u))) & 0xffu; }
+};
+
+// The call's tables for the patterns of one launch (LDS on the device): lengths, rows, and (Levenshtein) the Peq tables,
+// word c of side s of pattern i at peq[(2 i + s) * 256 + c].
+struct FzOvlTabs { const uint32_t *pm; const uint32_t *rows; const uint64_t *peq; };
+FZ_HD void fz_overlap_budget_step(uint32_t &acc, uint32_t &ki, uint32_t k, uint32_t m) {   // ki = k * i / m, from i - 1 to i (k < m)
+    acc += k;
+    if (acc >= m) { acc -= m; ++ki; }
+}
+
+// One pattern against one read's tail, Levenshtein: T = min(n, fz_overlap_tail) bytes behind w.  A forward search-form pass
+// over rows p[:m-1] leaves D[i] = E(i) (exact wherever E(i) <= k_i: a longer suffix costs more than k_i) in the running sum
+// of the vertical deltas; the best (i, d) then takes fz_expand_bits over the reversed tail with the reversed table, whose top
+// i bits are p[:i] reversed: its last arg-min is j(i).  No lane of the wave qualifies: the second pass is skipped.
+FZ_HD uint64_t fz_overlap_lev(const uint64_t *fwd, const uint64_t *rev, const FzOvlWindow &w, uint32_t T, uint32_t m, uint32_t k,
+                              uint32_t o, uint32_t pattern) {
+    const uint32_t rows = m - 1u;
+    if (!rows || o > rows) return 0ull;                    // (wave-uniform; rows = 0 would shift by 64 below)
+    const uint64_t hm = (~0ull << (64u - m)) & ~(1ull << 63);
+    FzBitsCol<1> c;
+    c.vp = hm; c.vn = 0;                                   // column 0: the empty suffix, D[i] = i
+    for (uint32_t t = 0; t < T; ++t) fz_bits_column_search(c, fwd[w.at(t)] & hm, hm);
+    uint32_t D = 0, acc = 0, ki = 0, best = 0;
+    for (uint32_t i = 1; i <= rows; ++i) {
+        const uint32_t bit = 63u - m + i;
+        D += (uint32_t)(c.vp >> bit) & 1u;
+        D -= (uint32_t)(c.vn >> bit) & 1u;
+        fz_overlap_budget_step(acc, ki, k, m);
+        const uint32_t key = ((i - D) << 8) | (255u - D);  // (wraps where D > i: impossible, D <= i)
+        if (i >= o && D <= ki && key > best) best = key;
+    }
+    if (!FZ_WAVE_BALLOT(best != 0u)) return 0ull;
+    if (!best) return 0ull;
+    const uint32_t d = 255u - (best & 0xffu), i = (best >> 8) + d;
+    const uint32_t winlen = T < i + d ? T : i + d;          // (j(i) <= i + d)
+    uint32_t dist = 0, consumed = 0;
+    const bool ok = fz_expand_bits<1>([&](uint32_t ch) { return rev[ch]; }, i, [&](uint32_t j) { return w.at(T - 1u - j); }, winlen, d,
+                                      dist, consumed);
+    return ok && dist == d ? fz_overlap_key(i - d, d, pattern, consumed) : 0ull;
+}
+
+// ... substitutions only: per i the window r[n - i:] against the row's dwords, two window dwords brought to the row's
+// alignment per step (fz_dword_diff), the bytes of p[:i] kept (fz_dword_bytes_in), left once over k_i.  `end` = window byte
+// offset of the read's end; every byte compared lies in [end - i, end) with i <= n: inside the read.
+FZ_HD uint64_t fz_overlap_subs(const uint32_t *p4, const FzOvlWindow &w, uint32_t end, uint32_t n, uint32_t m, uint32_t k, uint32_t o,
+                               uint32_t pattern) {
+    const uint32_t imax = n < m - 1u ? n : m - 1u;
+    uint32_t acc = 0, ki = 0, best = 0;
+    for (uint32_t i = 1; i <= imax; ++i) {
+        fz_overlap_budget_step(acc, ki, k, m);
+        if (i < o) continue;
+        const uint32_t ws = end - i, d0 = ws >> 2, sh = ws & 3u;
+        uint32_t prev = w.dword(d0), nd = 0;
+        for (uint32_t q = 0; q < i && nd <= ki; q += 4u) {
+            const uint32_t next = w.dword(d0 + (q >> 2) + 1u);
+            nd += (uint32_t)__builtin_popcount(fz_dword_diff(prev, next, sh, p4[q >> 2]) & fz_dword_bytes_in(q, 0u, i));
+            prev = next;
+        }
+        const uint32_t key = ((i - nd) << 8) | (255u - nd);
+        if (nd <= ki && key > best) best = key;
+    }
+    if (!best) return 0ull;
+    const uint32_t d = 255u - (best & 0xffu), i = (best >> 8) + d;
+    return fz_overlap_key(i - d, d, pattern, i);
+}
+
+// One read against the npat patterns p0 .. of a launch: the lane's part of fz_overlap_kernel behind the staging.  The loop
+// over the patterns is wave-uniform; the best key stays in registers.
+template <uint32_t MODE>
+FZ_HD uint64_t fz_overlap_lane(const FzOvlTabs &tb, const uint32_t *win, uint32_t stride, const FzOvlStage &s, uint32_t n, uint32_t p0,
+                               uint32_t npat, uint32_t k, uint32_t o) {
+    uint64_t best = 0;
+    for (uint32_t pi = 0; pi < npat; ++pi) {
+        const uint32_t m = tb.pm[pi];
+        uint32_t T = fz_overlap_tail(MODE, m, k);
+        if (T > s.ts) T = s.ts;                            // = min(n, the pattern's tail): ts = min(n, the launch's longest)
+        uint64_t key;
+        if (MODE == FZ_MODE_LEV) {
+            const FzOvlWindow w{win, stride, s.sh + (s.ts - T)};
+            key = fz_overlap_lev(tb.peq + (2u * pi) * 256u, tb.peq + (2u * pi + 1u) * 256u, w, T, m, k, o, p0 + pi);
+        } else {
+            const FzOvlWindow w{win, stride, s.sh};
+            key = fz_overlap_subs(tb.rows + pi * (FZ_OVL_ROW_BYTES / 4u), w, s.sh + s.ts, n, m, k, o, p0 + pi);
+        }
+        if (key > best) best = key;
+    }
+    return best;
+}

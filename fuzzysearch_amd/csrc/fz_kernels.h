@@ -2883,3 +2883,75 @@ __global__ __launch_bounds__(FZ_REC_THREADS) void fz_format_gather_kernel(const 
         __syncthreads();
     }
 }
+
+// ---------------------------------------------------------------------------------------------
+// End overlaps (fz_batch_end_overlaps; fz_device.h: fz_overlap_*): a prefix of a pattern at the end of every read of a batch.
+// Nothing is filtered and nothing is streamed: a launch looks at the last fz_overlap_tail bytes of every read only.
+//
+//   fz_overlap_kernel<MODE>  one lane per read, a workgroup per 256 reads, grid-strided so that a workgroup's tables serve
+//       many reads.  LDS: the launch's patterns — lengths, 64-byte rows, and for Levenshtein the forward and the reversed Peq
+//       table of every pattern (2 x 256 x 8 B, built here from the row: thread t owns word t of both tables) — then per wave
+//       the window, win_dwords x 256 B in the lane-transposed layout of the verification kernels (dword d of lane l at
+//       win[d * 64 + l]: 32 banks per half wave, no conflicts at any alignment).  The read's extent comes from ends[]; its
+//       tail is staged a dword at a time (fz_overlap_stage: every dword starts in front of buf_len), the patterns of the
+//       launch are walked in a wave-uniform loop with the best key in registers (fz_overlap_lane), and a lane with an answer
+//       does ONE device-scope atomic maximum without return value on table[read].  table is zeroed by a memset in front of the
+//       first launch (0: none); later chunks of the list are further launches over the same table.
+//   fz_overlap_finish_kernel  one lane per read: the key decoded into the 8-byte output row.
+struct FzOvlArgs {
+    FzRagged rag;
+    uint64_t buf_len;
+    const uint32_t *rows;                                  // the call's patterns: FZ_OVL_ROW_BYTES each, zeros behind a pattern
+    const uint32_t *pm;                                    // ... and their lengths
+    uint32_t p0, npat;                                     // the patterns of this launch
+    uint32_t k, o;
+    uint32_t tmax, win_dwords;                             // the longest tail of the launch's patterns, and the window for it
+};
+
+__host__ __device__ inline uint32_t fz_overlap_tables_lds(uint32_t mode, uint32_t npat) {
+    return fz_overlap_chunk(mode) * (4u + FZ_OVL_ROW_BYTES) + (mode == FZ_MODE_LEV ? npat * 4096u : 0u);
+}
+__host__ __device__ inline uint32_t fz_overlap_lds(uint32_t mode, uint32_t npat, uint32_t win_dwords) {
+    return fz_overlap_tables_lds(mode, npat) + FZ_WAVES_PER_BLOCK * win_dwords * 256u;
+}
+
+template <uint32_t MODE>
+__global__ __launch_bounds__(FZ_FILTER_THREADS) void fz_overlap_kernel(const uint8_t *__restrict__ buf, const FzOvlArgs a,
+                                                                       unsigned long long *__restrict__ table) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    constexpr uint32_t CH = MODE == FZ_MODE_LEV ? FZ_OVL_CHUNK_LEV : FZ_OVL_CHUNK_SUBS, RD = FZ_OVL_ROW_BYTES / 4u;
+    uint32_t *pm = reinterpret_cast<uint32_t *>(smem);
+    uint32_t *rows = pm + CH;
+    uint64_t *peq = reinterpret_cast<uint64_t *>(rows + CH * RD);
+    for (uint32_t i = threadIdx.x; i < a.npat; i += FZ_FILTER_THREADS) pm[i] = a.pm[a.p0 + i];
+    for (uint32_t i = threadIdx.x; i < a.npat * RD; i += FZ_FILTER_THREADS) rows[i] = a.rows[a.p0 * RD + i];
+    __syncthreads();
+    if constexpr (MODE == FZ_MODE_LEV) {
+        for (uint32_t i = threadIdx.x; i < a.npat * 512u; i += FZ_FILTER_THREADS)
+            peq[i] = fz_overlap_peq_word(reinterpret_cast<const uint8_t *>(rows + (i >> 9) * RD), pm[i >> 9], i & 255u, (i >> 8) & 1u);
+        __syncthreads();
+    }
+    const uint32_t lane = fz_lane();
+    uint32_t *win = reinterpret_cast<uint32_t *>(smem + fz_overlap_tables_lds(MODE, a.npat)) + (threadIdx.x >> 6) * a.win_dwords * 64u + lane;
+    const FzOvlTabs tb{pm, rows, peq};
+    const uint64_t n_seqs = a.rag.n_seqs, groups = (n_seqs + FZ_FILTER_THREADS - 1u) / FZ_FILTER_THREADS;
+    for (uint64_t g = blockIdx.x; g < groups; g += gridDim.x) {
+        const uint64_t j = g * FZ_FILTER_THREADS + threadIdx.x;
+        const bool have = j < n_seqs;
+        const uint64_t sa = have && j ? a.rag.ends[j - 1u] : 0ull, se = have ? a.rag.ends[j] : 0ull;   // (no read: an empty one)
+        const FzOvlStage st = fz_overlap_stage(sa, se, a.tmax, a.buf_len);
+        fz_overlap_stage_copy(buf, st, a.win_dwords, win, 64u);
+        fz_wave_lds_sync();
+        const uint64_t key = fz_overlap_lane<MODE>(tb, win, 64u, st, (uint32_t)(se - sa), a.p0, a.npat, a.k, a.o);
+        if (key) (void)__hip_atomic_fetch_max(&table[j], (unsigned long long)key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        fz_wave_lds_sync();
+    }
+}
+
+__global__ __launch_bounds__(FZ_ASSIGN_THREADS) void fz_overlap_finish_kernel(const unsigned long long *__restrict__ table,
+                                                                              const uint64_t *__restrict__ ends, uint64_t n_seqs,
+                                                                              FzOverlapRow *__restrict__ out) {
+    const uint64_t stride = (uint64_t)gridDim.x * FZ_ASSIGN_THREADS;
+    for (uint64_t j = (uint64_t)blockIdx.x * FZ_ASSIGN_THREADS + threadIdx.x; j < n_seqs; j += stride)
+        out[j] = fz_overlap_row(table[j], (uint32_t)(ends[j] - (j ? ends[j - 1u] : 0ull)));
+}

@@ -426,6 +426,7 @@ struct fz_ctx {
     double rec_ms[4] = {0, 0, 0, 0};             // fz_debug_records_ms: the last fz_batch_upload_records
     double drv_ms[5] = {0, 0, 0, 0, 0};          // fz_debug_derive_ms: the last fz_batch_derive
     double fmt_ms[5] = {0, 0, 0, 0, 0};          // fz_debug_format_ms: the last fz_batch_format
+    double ovl_ms[4] = {0, 0, 0, 0};             // fz_debug_overlap_ms: the last fz_batch_end_overlaps
     bool batch_call = false;                     // inside fz_batch_search: the one caller a batch handle is valid for (validate)
     // sharded searches: where every shard's (rank's) records end in the collected vector, and the shards in ascending
     // order of the index range they own (emit_matches orders shard by shard)
@@ -5024,6 +5025,175 @@ int fz_debug_assign_fold(const uint64_t *offs, uint64_t n_seqs, const void *recs
     }
     for (uint64_t j = 0; j < n_seqs; ++j) {                   // the finish kernel's lane
         const FzAssignRow r = fz_assign_row(lo[j], hi[j], pat_m, k);
+        memcpy(&out[j], &r, sizeof r);
+    }
+    return FZ_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// End overlaps (fz_batch_end_overlaps): per read the pattern whose strictly partial prefix ends it.  No filter, no plan: the
+// list is cut into launches of fz_overlap_chunk patterns over ONE table of a key per read (fz_kernels.h: fz_overlap_kernel),
+// the finish kernel decodes it and one copy brings the 8-byte rows back.
+
+// What the call and its host twin refuse, in this order; then pm = the lengths and rows = the 64-byte rows of the patterns.
+static int ovl_check(uint32_t mode, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k, uint32_t min_overlap,
+                     std::vector<uint32_t> &pm, std::vector<uint32_t> &rows) {
+    if (mode != FZ_MODE_LEV && mode != FZ_MODE_SUBS) return fail(FZ_EUNSUPPORTED, "end overlaps: the mode must be Levenshtein or substitutions-only");
+    if (int rc = mp_check_lists(pats, offs, n_pats)) return rc;
+    if (min_overlap == 0) return fail(FZ_EINVAL, "end overlaps: min_overlap must be at least 1");
+    if (n_pats > FZ_OVL_MAX_PATS) return fail(FZ_EUNSUPPORTED, "end overlaps take at most %u patterns", FZ_OVL_MAX_PATS);
+    if (k > FZ_OVL_MAX_K) return fail(FZ_EUNSUPPORTED, "end overlaps take budgets up to %u", FZ_OVL_MAX_K);
+    pm.assign(n_pats, 0u);
+    rows.assign((size_t)n_pats * (FZ_OVL_ROW_BYTES / 4u), 0u);
+    for (uint32_t i = 0; i < n_pats; ++i) {
+        const uint64_t m = offs[i + 1] - offs[i];
+        if (m == 0) return fail(FZ_EINVAL, "end overlaps: pattern %u is empty", i);
+        if (m > FZ_OVL_MAX_M) return fail(FZ_EUNSUPPORTED, "end overlaps: pattern %u is longer than %u bytes", i, FZ_OVL_MAX_M);
+        if (k >= m) return fail(FZ_EUNSUPPORTED, "end overlaps: pattern %u is not longer than the budget %u", i, k);
+        pm[i] = (uint32_t)m;
+        memcpy(reinterpret_cast<uint8_t *>(rows.data()) + (size_t)i * FZ_OVL_ROW_BYTES, pats + offs[i], (size_t)m);
+    }
+    return FZ_OK;
+}
+
+// The longest tail of the patterns [p0, p0 + npat).
+static uint32_t ovl_tmax(uint32_t mode, const std::vector<uint32_t> &pm, uint32_t p0, uint32_t npat, uint32_t k) {
+    uint32_t tmax = 0;
+    for (uint32_t i = 0; i < npat; ++i) tmax = std::max(tmax, fz_overlap_tail(mode, pm[p0 + i], k));
+    return tmax;
+}
+
+int fz_batch_end_overlaps(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k,
+                          uint32_t min_overlap, fz_overlap **out) {
+    static_assert(sizeof(fz_overlap) == sizeof(FzOverlapRow) && sizeof(fz_overlap) == 8, "the kernel writes the C-ABI's rows");
+    const auto t_call = std::chrono::steady_clock::now();
+    auto since = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
+    if (!out) return fail(FZ_EINVAL, "null argument");
+    *out = nullptr;
+    if (!ctx || !batch || batch->ctx != ctx) return fail(FZ_EINVAL, "bad ctx/seq handle");
+    std::vector<uint32_t> pm, prow;
+    int rc = ovl_check(mode, pats, offs, n_pats, k, min_overlap, pm, prow);
+    if (rc) return rc;
+    if ((rc = batch_single_device(ctx, batch))) return rc;
+    if (!batch->is_batch) return fail(FZ_EUNSUPPORTED, "fz_batch_end_overlaps takes a batch handle (fz_batch_upload)");
+    if (ctx->npend || ctx->stream_inflight) return fail(FZ_EINVAL, "a search of this context is in flight");
+    if (batch->max_seq_len >= (1ull << 32)) return fail(FZ_EUNSUPPORTED, "end overlaps take sequences shorter than 2^32 bytes");
+    const uint64_t n_seqs = batch->n_seqs;
+    void *mem = nullptr;
+    if ((rc = alloc_out(n_seqs, sizeof(fz_overlap), &mem))) return rc;
+    struct Guard { void *p; ~Guard() { if (p) release_out(p); } } guard{mem};
+    fz_overlap *res = static_cast<fz_overlap *>(mem);
+    ctx->view = nullptr; ctx->view_n = 0; ctx->rows_ready = false;
+    mp_publish(ctx, MpTotals(), 0, FZ_FORM_NONE);
+    for (double &ms : ctx->ovl_ms) ms = 0;
+    if (n_pats == 0 || n_seqs == 0 || batch->n == 0) {         // nothing can overlap: nothing is launched
+        for (uint64_t j = 0; j < n_seqs; ++j) {
+            const FzOverlapRow r = fz_overlap_row(0ull, (uint32_t)(batch->ends[j] - (j ? batch->ends[j - 1] : 0ull)));
+            memcpy(&res[j], &r, sizeof r);
+        }
+        guard.p = nullptr;
+        *out = res;
+        ctx->ovl_ms[3] = since(t_call);
+        return FZ_OK;
+    }
+    const Shard &sh = batch->shards[0];
+    DevState &d = ctx->devs[sh.dev];
+    HIP_TRY(hipSetDevice(d.device));
+    // table | rows | pattern lengths | pattern rows (8-, 8-, 4-, 4-byte alignment)
+    const uint64_t o_rows = n_seqs * 8, o_pm = o_rows + n_seqs * sizeof(FzOverlapRow), o_pat = o_pm + (uint64_t)n_pats * 4;
+    const uint64_t need = o_pat + (uint64_t)n_pats * FZ_OVL_ROW_BYTES;
+    if ((rc = grow_device(d, d.d_assign, d.assign_cap, need, need))) return rc;
+    unsigned long long *d_table = reinterpret_cast<unsigned long long *>(d.d_assign);
+    FzOverlapRow *d_rows = reinterpret_cast<FzOverlapRow *>(d.d_assign + o_rows);
+    const auto t_h2d = std::chrono::steady_clock::now();
+    HIP_TRY(hipMemsetAsync(d_table, 0, (size_t)o_rows, d.stream));
+    HIP_TRY(hipMemcpyAsync(d.d_assign + o_pm, pm.data(), (size_t)n_pats * 4, hipMemcpyHostToDevice, d.stream));
+    HIP_TRY(hipMemcpyAsync(d.d_assign + o_pat, prow.data(), (size_t)n_pats * FZ_OVL_ROW_BYTES, hipMemcpyHostToDevice, d.stream));
+    HIP_TRY(hipStreamSynchronize(d.stream));               // (pm and prow are the call's own: the copies are done before they go)
+    ctx->ovl_ms[0] = since(t_h2d);
+    FzOvlArgs a;
+    a.rag = fz_ragged(sh.geom);
+    a.buf_len = sh.geom.buf_len;
+    a.rows = reinterpret_cast<const uint32_t *>(d.d_assign + o_pat);
+    a.pm = reinterpret_cast<const uint32_t *>(d.d_assign + o_pm);
+    a.k = k; a.o = min_overlap;
+    MpTotals tot;
+    const uint32_t chunk = fz_overlap_chunk(mode);
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((n_seqs + FZ_FILTER_THREADS - 1) / FZ_FILTER_THREADS, (uint64_t)d.n_cus * 8);
+    if (ctx->timing) HIP_TRY(hipEventRecord(d.ev[2], d.stream));
+    for (uint32_t p0 = 0; p0 < n_pats; p0 += chunk) {
+        a.p0 = p0;
+        a.npat = std::min(chunk, n_pats - p0);
+        a.tmax = ovl_tmax(mode, pm, p0, a.npat, k);
+        a.win_dwords = fz_overlap_win_dwords(a.tmax);
+        const uint32_t lds = fz_overlap_lds(mode, a.npat, a.win_dwords);
+        if (mode == FZ_MODE_LEV)
+            hipLaunchKernelGGL(fz_overlap_kernel<FZ_MODE_LEV>, dim3(grid), dim3(FZ_FILTER_THREADS), lds, d.stream, sh.d_buf, a, d_table);
+        else
+            hipLaunchKernelGGL(fz_overlap_kernel<FZ_MODE_SUBS>, dim3(grid), dim3(FZ_FILTER_THREADS), lds, d.stream, sh.d_buf, a, d_table);
+        HIP_TRY(hipGetLastError());
+        ++tot.launches;
+    }
+    hipLaunchKernelGGL(fz_overlap_finish_kernel, dim3(assign_grid(d, n_seqs)), dim3(FZ_ASSIGN_THREADS), 0, d.stream, d_table, a.rag.ends, n_seqs, d_rows);
+    HIP_TRY(hipGetLastError());
+    if (ctx->timing) HIP_TRY(hipEventRecord(d.ev[3], d.stream));
+    HIP_TRY(hipStreamSynchronize(d.stream));
+    const auto t_d2h = std::chrono::steady_clock::now();
+    HIP_TRY(hipMemcpyAsync(res, d_rows, (size_t)n_seqs * sizeof(fz_overlap), hipMemcpyDeviceToHost, d.stream));
+    HIP_TRY(hipStreamSynchronize(d.stream));
+    ctx->ovl_ms[2] = since(t_d2h);
+    if (ctx->timing) ctx->ovl_ms[1] = span_ms(d.ev[2], d.ev[3]);
+    tot.bytes = sh.geom.buf_len;
+    guard.p = nullptr;
+    *out = res;
+    mp_publish(ctx, tot, 0, FZ_FORM_NONE, ctx->ovl_ms[1]);
+    ctx->ovl_ms[3] = since(t_call);
+    return FZ_OK;
+}
+
+int fz_debug_overlap_ms(fz_ctx *ctx, double *ms4) {
+    if (!ctx || !ms4) return fail(FZ_EINVAL, "null argument");
+    for (int i = 0; i < 4; ++i) ms4[i] = ctx->ovl_ms[i];
+    return FZ_OK;
+}
+
+int fz_debug_end_overlaps(uint32_t mode, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k, uint32_t min_overlap,
+                          const uint8_t *bytes, const uint64_t *ends, uint64_t n_seqs, fz_overlap *out) {
+    if ((n_seqs && (!ends || !out)) || (n_seqs && ends[n_seqs - 1] && !bytes)) return fail(FZ_EINVAL, "null argument");
+    std::vector<uint32_t> pm, prow;
+    if (int rc = ovl_check(mode, pats, offs, n_pats, k, min_overlap, pm, prow)) return rc;
+    if (n_seqs >= (1ull << 32)) return fail(FZ_EUNSUPPORTED, "more than 2^32 - 1 sequences in a batch");
+    for (uint64_t j = 0; j < n_seqs; ++j) {
+        const uint64_t sa = j ? ends[j - 1] : 0ull;
+        if (ends[j] < sa) return fail(FZ_EINVAL, "sequence offsets must not decrease");
+        if (ends[j] - sa >= (1ull << 32)) return fail(FZ_EUNSUPPORTED, "end overlaps take sequences shorter than 2^32 bytes");
+    }
+    const uint64_t total = n_seqs ? ends[n_seqs - 1] : 0ull;
+    std::vector<uint8_t> buf((total + 3u) & ~(uint64_t)3, 0);  // the device's buffer: zeros behind the data
+    if (total) memcpy(buf.data(), bytes, (size_t)total);
+    std::vector<uint64_t> table(n_seqs, 0ull);
+    const uint32_t chunk = fz_overlap_chunk(mode);
+    std::vector<uint64_t> peq;
+    std::vector<uint32_t> win;
+    for (uint32_t p0 = 0; p0 < n_pats; p0 += chunk) {         // one launch
+        const uint32_t npat = std::min(chunk, n_pats - p0), tmax = ovl_tmax(mode, pm, p0, npat, k), win_dwords = fz_overlap_win_dwords(tmax);
+        const uint32_t *rows = prow.data() + (size_t)p0 * (FZ_OVL_ROW_BYTES / 4u);
+        peq.assign(mode == FZ_MODE_LEV ? (size_t)npat * 512u : 0u, 0ull);
+        for (size_t i = 0; i < peq.size(); ++i)
+            peq[i] = fz_overlap_peq_word(reinterpret_cast<const uint8_t *>(rows + (i >> 9) * (FZ_OVL_ROW_BYTES / 4u)), pm[p0 + (i >> 9)], i & 255u, (i >> 8) & 1u);
+        const FzOvlTabs tb{pm.data() + p0, rows, peq.data()};
+        win.assign(win_dwords, 0u);
+        for (uint64_t j = 0; j < n_seqs; ++j) {               // one lane
+            const uint64_t sa = j ? ends[j - 1] : 0ull, se = ends[j];
+            const FzOvlStage st = fz_overlap_stage(sa, se, tmax, total);
+            fz_overlap_stage_copy(buf.data(), st, win_dwords, win.data(), 1u);
+            const uint64_t key = mode == FZ_MODE_LEV ? fz_overlap_lane<FZ_MODE_LEV>(tb, win.data(), 1u, st, (uint32_t)(se - sa), p0, npat, k, min_overlap)
+                                                     : fz_overlap_lane<FZ_MODE_SUBS>(tb, win.data(), 1u, st, (uint32_t)(se - sa), p0, npat, k, min_overlap);
+            table[j] = std::max(table[j], key);
+        }
+    }
+    for (uint64_t j = 0; j < n_seqs; ++j) {                   // the finish kernel's lane
+        const FzOverlapRow r = fz_overlap_row(table[j], (uint32_t)(ends[j] - (j ? ends[j - 1] : 0ull)));
         memcpy(&out[j], &r, sizeof r);
     }
     return FZ_OK;

@@ -307,6 +307,43 @@ int fz_debug_assign_fold(const uint64_t *offs, uint64_t n_seqs, const void *recs
                          const uint32_t *pat_table, uint32_t n_table, const uint32_t *pat_m, uint32_t n_pats, uint32_t k,
                          fz_assign *out);
 
+/* End overlaps: the strictly partial PREFIX of a pattern at the END of every sequence of a batch (a read that runs into its
+ * adapter and breaks off: "3' adapter, partial occurrences allowed").  Per sequence r of n bytes, pattern p of m bytes,
+ * budget k and min_overlap o, over the prefix lengths o <= i <= m - 1, each with the scaled budget k_i = k * i / m:
+ *   FZ_MODE_LEV   E(i) = min over a in [0, n] of ed(p[:i], r[a:]), j(i) = the largest j with ed(p[:i], r[n-j:]) == E(i)
+ *                 (i may exceed n: a short sequence can hold a prefix with deletions)
+ *   FZ_MODE_SUBS  E(i) = Hamming(p[:i], r[n-i:]) for i <= n, j(i) = i
+ * A length qualifies when E(i) <= k_i.  A pattern answers with the i of the most matched bytes i - E(i), then the smaller
+ * E(i); the sequence answers with the pattern of the largest i - d, then the smaller d, then the lower list position (a
+ * pattern listed twice answers with its first).  Row j of *out (n_seqs rows, released with fz_free):
+ *   pattern, overlap = i, dist = d, start = n - j(i);  none: pattern = 0xffff, overlap = dist = 0, start = n
+ * so `start` is a cut position as it stands.  Whole occurrences, also those that end at the sequence's end, are
+ * fz_batch_search's to find.
+ * On the device (fz_kernels.h: fz_overlap_kernel): one lane per sequence reads its last m - 1 + k_(m-1) bytes only; the list
+ * is cut into launches of 8 (FZ_MODE_LEV) or 64 (FZ_MODE_SUBS) patterns that fold into one table of a 64-bit key per
+ * sequence by atomic maximum; a finish kernel decodes it and ONE copy of n_seqs * 8 bytes brings the rows back.
+ * Domain: 1 <= m <= 64, k <= 16, k < m, at most 65 534 patterns, sequences shorter than 2^32 bytes.  Refusals, before anything
+ * is launched: FZ_EUNSUPPORTED for anything outside the domain (the pattern is named), another mode, a plain sequence
+ * handle, a context of several devices or in a communicator; FZ_EINVAL for min_overlap == 0, an empty pattern, a search
+ * of the context still in flight.  No patterns or an empty batch: rows of none, or no rows.
+ * fz_stats afterwards: filter_launches = the launches of the list, verify_ms = device_ms = their span with the finish kernel. */
+typedef struct {
+    uint32_t start;
+    uint16_t pattern;
+    uint8_t  overlap, dist;
+} fz_overlap;
+
+int fz_batch_end_overlaps(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats,
+                          uint32_t k, uint32_t min_overlap, fz_overlap **out);
+/* Test hook, no device needed: the same call on the host, through the very functions the kernels' lanes run (fz_device.h:
+ * fz_overlap_stage, fz_overlap_lane, fz_overlap_row) and with the same refusals.  bytes = the packed sequences, ends = their
+ * n_seqs cumulative end offsets; out = n_seqs rows. */
+int fz_debug_end_overlaps(uint32_t mode, const uint8_t *pats, const uint64_t *offs, uint32_t n_pats, uint32_t k,
+                          uint32_t min_overlap, const uint8_t *bytes, const uint64_t *ends, uint64_t n_seqs, fz_overlap *out);
+/* ms4 = {tables to the device, kernels (0 for a context that does not time them), rows to the host, the whole call} of
+ * the context's last fz_batch_end_overlaps, in milliseconds. */
+int fz_debug_overlap_ms(fz_ctx *ctx, double *ms4);
+
 /* Symbol classes (IUPAC patterns) on the substitutions-only multi-pattern pass.  Two tables of 256 bytes define them:
  *   tmask[t]  the one-hot bit of text byte t among the base symbols (at most 8), 0 when t is no base symbol
  *   pmask[c]  the set of pattern byte c as a mask over those bits, 0 for a plain byte
