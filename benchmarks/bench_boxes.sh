@@ -20,7 +20,7 @@ tag = sys.argv[1]
 out = os.path.join("gpurun_out", "boxes")
 line = json.loads(open(os.path.join(out, "bench_%s.json" % tag)).read().strip().splitlines()[-1])
 trace = max(glob.glob("/tmp/boxtrace/*/*_kernel_trace.csv"), key=os.path.getmtime)
-head = "fz_scan_kernel<2, 3, true, false, true, 0>"
+head = "fz_lean_scan_kernel<2, 3, true>"
 rows = []
 for r in csv.DictReader(open(trace)):
     rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"], int(r.get("Grid_Size_X", r.get("Grid_Size", "0")) or 0)))

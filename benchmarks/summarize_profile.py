@@ -6,8 +6,8 @@ tag = sys.argv[1]
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 base = os.path.join(root, "gpurun_out", "prof_" + tag)
 alg = int(sys.argv[2]) if len(sys.argv) > 2 else 2 ** 30
-# the headline instance: hash windows (NWIN = 2, DH = 3), fused, in-memory, low-bits slot
-HEAD_KERNEL = "fz_scan_kernel<2, 3, true, false, true, 0>"
+# the headline instance: the lean one (no equal-n-gram sets, bands for k <= 2), hash windows (NWIN = 2, DH = 3), low-bits slot
+HEAD_KERNEL = "fz_lean_scan_kernel<2, 3, true>"
 TILES_PER_WG = 12
 # threads of the headline launch: round 1-2 (and inputs of 10+ rounds): one workgroup per 12 tiles; round 3: a whole
 # number of rounds of the 6 x 256 resident workgroups, ~9.5 tiles each (fzhip.hip: enqueue_shard)

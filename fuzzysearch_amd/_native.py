@@ -172,6 +172,7 @@ PROTOTYPES = {
     "fz_debug_order_segments": (ci, (vp, vp, u32, u32, mpp, u64p)),
     "fz_debug_scan_regions": (ci, (u64, u64, u32, ci, f64, ci, u32p, vp)),
     "fz_debug_scan_plan": (ci, (cs, u32, u32, u64, u32, ci, u32p, u32p, cip, u32p, vp)),
+    "fz_debug_scan_instance": (ci, (u32, cs, u32, u32, u64, u32, u32p, u32p, u32p)),
     "fz_debug_gather_merge": (ci, (vp, u32, u64, vp, u32, mpp, u64p, u64p)),
     "fz_stats": (ci, (vp, stp)),
     "fz_mem_info": (ci, (vp, u64p, u64p)),
@@ -195,7 +196,7 @@ OPTIONAL = frozenset((
     "fz_batch_upload_fasta", "fz_batch_fasta_index", "fz_debug_fasta_split", "fz_debug_fasta_upper4", "fz_debug_fasta_src",
     "fz_batch_derive", "fz_debug_derive_plan", "fz_debug_derive_ms",
     "fz_batch_upload_records_lines", "fz_batch_format", "fz_debug_format_plan", "fz_debug_format_ms",
-    "fz_debug_scan_plan", "fz_mem_info",
+    "fz_debug_scan_plan", "fz_mem_info", "fz_debug_scan_instance",
 ))
 
 _lib = None

@@ -389,14 +389,19 @@ struct FzBytes {
 
 // Budget-dispatched expansion: register band for k <= MAXK (<= FZ_REG_BAND_MAX), LDS ring otherwise.
 // MAXK is a compile-time cap so that a kernel only pays (in VGPRs) for the band widths it may run:
-// the fused scan kernel uses 4 (keeps it at <= 64 VGPRs), the stand-alone verify kernel 8.
+// the fused scan kernel uses 4 (keeps it at <= 64 VGPRs), its lean instances 2 (fz_kernels.h: fz_lean_scan_kernel, only
+// routed to with k <= 2), the stand-alone verify kernel 8.
 template <int MAXK, class Sc, class SubF, class WinF>
 FZ_HD bool fz_expand_any(Sc &sc, uint32_t k, SubF sub, uint32_t sublen, WinF win, uint32_t winlen, uint32_t budget,
                          uint32_t &dist, uint32_t &consumed) {
     if (k == 1) return fz_expand_band<1>(sub, sublen, win, winlen, budget, dist, consumed);
     if (k == 2) return fz_expand_band<2>(sub, sublen, win, winlen, budget, dist, consumed);
-    if (k == 3) return fz_expand_band<3>(sub, sublen, win, winlen, budget, dist, consumed);
-    if (k == 4) return fz_expand_band<4>(sub, sublen, win, winlen, budget, dist, consumed);
+    if constexpr (MAXK >= 3) {
+        if (k == 3) return fz_expand_band<3>(sub, sublen, win, winlen, budget, dist, consumed);
+    }
+    if constexpr (MAXK >= 4) {
+        if (k == 4) return fz_expand_band<4>(sub, sublen, win, winlen, budget, dist, consumed);
+    }
     if constexpr (MAXK >= 8) {
         if (k == 5) return fz_expand_band<5>(sub, sublen, win, winlen, budget, dist, consumed);
         if (k == 6) return fz_expand_band<6>(sub, sublen, win, winlen, budget, dist, consumed);

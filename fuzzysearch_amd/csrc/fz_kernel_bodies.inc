@@ -3,7 +3,8 @@
 // and for ragged segments, a batch of sequences packed back to back (fz_batch_*_kernel, fz_mp_batch_*_kernel; fz_device.h).  Included by fz_kernels.h inside each kernel, with
 // FZ_KERNEL_BODY naming the section and `constexpr bool RAG` (and the kernel's template parameters) in scope: one text,
 // two kernels — a shared inline function instead moved the register allocation of the existing instances.
-#if FZ_KERNEL_BODY == 1      // ---- fz_scan_kernel / fz_batch_scan_kernel
+#if FZ_KERNEL_BODY == 1      // ---- fz_scan_kernel / fz_lean_scan_kernel / fz_batch_scan_kernel
+    // (also in scope: `constexpr bool DUPH` — the equal-n-gram slot sets exist — and `constexpr int MAXK`, the widest register band)
     constexpr bool WF = WFG == 16 || WFG == 32;       // lane-per-cell verification inside the scan, WFG lanes per candidate
     constexpr int BITS = (WFG == 1 || WFG == 2 || WFG == 4) ? WFG : 0;   // bit-vector verification inside the scan, one candidate per lane:
                                                                          // one / two 64-bit words per column, 4 = one 32-bit word
@@ -47,9 +48,12 @@
         for (uint32_t g = a.nblk; g-- > 0;)
             if (((a.H[g] >> a.lut_shift) & (FZ_LUT_SLOTS - 1u)) == threadIdx.x) { t = a.H[g]; who = g; set |= 0x10000u << g; }
         lut[threadIdx.x] = t;
-        lut[FZ_LUT_SLOTS + threadIdx.x] = (a.flags & FZ_FLAG_DUP_HASHES) ? (who | set) : who;
+        if constexpr (DUPH) lut[FZ_LUT_SLOTS + threadIdx.x] = (a.flags & FZ_FLAG_DUP_HASHES) ? (who | set) : who;
+        else lut[FZ_LUT_SLOTS + threadIdx.x] = who;
     }
-    const bool dup_hashes = (a.flags & FZ_FLAG_DUP_HASHES) != 0;
+    // DUPH = false (the lean instances): no launch with equal block hashes gets here, the slot-set branch below does not exist
+    bool dup_hashes = false;
+    if constexpr (DUPH) dup_hashes = (a.flags & FZ_FLAG_DUP_HASHES) != 0;
     // this workgroup's walk over the tiles: first_tile, first_tile + stride, .. below limit (scalar values); the flushes
     // decode queue entries with the copy in LDS (fz_code_local)
     uint32_t wg0 = 0, stride = gridDim.x;
@@ -144,7 +148,7 @@
                         // saves three ops per firing but is the register that spills (measured: 0.218 -> 0.221 ms)
                         uint32_t pos = threadIdx.x;
                         asm volatile("v_lshlrev_b32 %0, 4, %0" : "+v"(pos));
-                        if (__builtin_expect(dup_hashes, 0)) {
+                        if (DUPH && __builtin_expect(dup_hashes, 0)) {
                             // equal n-grams (equal hashes) share a slot: the dword behind the hash table then carries, from
                             // bit 16 up, the SET of the launch's blocks that live in the slot, and a firing lane queues one
                             // entry per member (rounds 1 - 5 compared the window's hash with every block of the launch, offset
@@ -290,7 +294,7 @@
                 qf = qn;                              // what stays queued has its window
                 continue;
             } else {
-                confirmed += fz_queue_flush<FUSED, SEG, RAG>(buf, a, pat_lds, w, qn, hits, recs, counters);
+                confirmed += fz_queue_flush<FUSED, SEG, RAG, MAXK>(buf, a, pat_lds, w, qn, hits, recs, counters);
             }
         }
         qn = 0;
@@ -299,7 +303,7 @@
     }
     if constexpr (PREF) {
         if (qn > qf) fz_prefetch_windows(buf, a, w, qf, qn);
-        confirmed += fz_pooled_flush<4, VF, RAG>(buf, a, pat_lds, smem + FZ_TABLE_BYTES + mpad + peq_bytes, fz_wave_lds_pref_bytes(qcap, a.win_pieces),
+        confirmed += fz_pooled_flush<MAXK, VF, RAG>(buf, a, pat_lds, smem + FZ_TABLE_BYTES + mpad + peq_bytes, fz_wave_lds_pref_bytes(qcap, a.win_pieces),
                                               reinterpret_cast<volatile uint32_t *>(smem + 2u * FZ_LUT_BYTES), wave, qn, recs, counters,
                                               smem + FZ_TABLE_BYTES + mpad);
     }

@@ -578,7 +578,8 @@ __device__ __forceinline__ uint32_t fz_flush_wf(const uint8_t *__restrict__ buf,
                                                 volatile uint32_t *fills, uint32_t wave, uint32_t qn, bool pooled,
                                                 FzRec *__restrict__ recs, unsigned long long *__restrict__ counters);
 
-template <bool FUSED, bool SEG, bool RAG>
+// MAXK: the widest register band the verification carries (fz_expand_any); the lean instances pass 2.
+template <bool FUSED, bool SEG, bool RAG, int MAXK = 4>
 __device__ __forceinline__ uint32_t fz_queue_flush(const uint8_t *__restrict__ buf, const FzScanArgs &a,
                                                    const uint8_t *pat_lds, const FzWaveLds &w, uint32_t qn,
                                                    uint64_t *__restrict__ hits, FzRec *__restrict__ recs,
@@ -617,7 +618,7 @@ __device__ __forceinline__ uint32_t fz_queue_flush(const uint8_t *__restrict__ b
             }
             if (FUSED) {
                 if (SEG && c && !__ballot(valid)) continue;
-                confirmed += fz_wave_verify<4, PREF, 0, RAG>(buf, a, pat_lds, w, lane, hit, sg, valid, recs, counters,
+                confirmed += fz_wave_verify<MAXK, PREF, 0, RAG>(buf, a, pat_lds, w, lane, hit, sg, valid, recs, counters,
                                                      PREF ? reinterpret_cast<const uint8_t *>(w.win) + e * 16u : nullptr);
             } else {
                 if (valid) valid = fz_confirm(buf, a, blk, local);
@@ -772,7 +773,29 @@ __global__ __launch_bounds__(FZ_FILTER_THREADS)
 __attribute__((amdgpu_waves_per_eu(FZ_SCAN_WAVES(WFG, FUSED, SEG), FZ_SCAN_WAVES(WFG, FUSED, SEG)))) void fz_scan_kernel(
     const uint8_t *__restrict__ buf, const FzScanArgs a, uint64_t ntiles,
     uint64_t *__restrict__ hits, FzRec *__restrict__ recs, unsigned long long *__restrict__ counters) {
-    constexpr bool RAG = false;
+    constexpr bool RAG = false, DUPH = true;
+    constexpr int MAXK = 4;
+#define FZ_KERNEL_BODY 1
+#include "fz_kernel_bodies.inc"
+#undef FZ_KERNEL_BODY
+}
+
+// The lean instances of the in-memory register-band / Hamming-count form (FUSED, !SEG, WFG = 0: the headline workload, the
+// substitutions-only searches, Levenshtein budgets 1 and 2) — kernels of their own from the same text, like the ragged ones,
+// so that every fz_scan_kernel instance stays what it was.  Compiled out of them (DUPH = false, MAXK = 2):
+//   * the equal-n-gram slot sets of the rare path: the run-time test, the `while (__ballot(set))` loop in each of its 64
+//     unrolled copies and the set bits of the table word.  The host only launches a lean instance when no two blocks of the
+//     launch hash alike (fzhip.hip: scan_is_lean);
+//   * the register bands for k = 3 and 4 (right and left expansion, mid-scan and pooled flush: eight DP loops) — k >= 3 is
+//     never routed here.
+// What that leaves the headline instance: profiles/r23_headline_lean.txt.
+template <int NWIN, int DH, bool SA>
+__global__ __launch_bounds__(FZ_FILTER_THREADS)
+__attribute__((amdgpu_waves_per_eu(FZ_SCAN_WAVES(0, true, false), FZ_SCAN_WAVES(0, true, false)))) void fz_lean_scan_kernel(
+    const uint8_t *__restrict__ buf, const FzScanArgs a, uint64_t ntiles,
+    uint64_t *__restrict__ hits, FzRec *__restrict__ recs, unsigned long long *__restrict__ counters) {
+    constexpr bool FUSED = true, SEG = false, RAG = false, DUPH = false;
+    constexpr int WFG = 0, MAXK = 2;
 #define FZ_KERNEL_BODY 1
 #include "fz_kernel_bodies.inc"
 #undef FZ_KERNEL_BODY
@@ -784,7 +807,8 @@ __global__ __launch_bounds__(FZ_FILTER_THREADS)
 __attribute__((amdgpu_waves_per_eu(FZ_SCAN_WAVES(WFG, true, true), FZ_SCAN_WAVES(WFG, true, true)))) void fz_batch_scan_kernel(
     const uint8_t *__restrict__ buf, const FzScanArgs a, uint64_t ntiles,
     uint64_t *__restrict__ hits, FzRec *__restrict__ recs, unsigned long long *__restrict__ counters) {
-    constexpr bool SEG = false, RAG = true;
+    constexpr bool SEG = false, RAG = true, DUPH = true;
+    constexpr int MAXK = 4;
 #define FZ_KERNEL_BODY 1
 #include "fz_kernel_bodies.inc"
 #undef FZ_KERNEL_BODY

@@ -671,6 +671,35 @@ ScanKernel scan_kernel(int nwin, int dh, bool fused, bool seg, bool sa, int wf_g
 #endif
 }
 
+// The lean instances (fz_kernels.h: fz_lean_scan_kernel): the in-memory register-band / Hamming-count form without the
+// equal-n-gram slot sets and without the bands for k = 3, 4.
+template <bool SA>
+ScanKernel lean_scan_kernel_f(int nwin, int dh) {
+#ifdef FZ_LAB_ONLY
+    return nwin == 2 && dh == 3 ? fz_lean_scan_kernel<2, 3, SA> : nullptr;
+#else
+    if (nwin == 1) return fz_lean_scan_kernel<1, 0, SA>;
+    switch (dh) {
+        case 2: return fz_lean_scan_kernel<2, 2, SA>;
+        case 3: return fz_lean_scan_kernel<2, 3, SA>;
+        case 4: return fz_lean_scan_kernel<2, 4, SA>;
+        default: return fz_lean_scan_kernel<2, 5, SA>;
+    }
+#endif
+}
+
+ScanKernel lean_scan_kernel(int nwin, int dh, bool sa) { return sa ? lean_scan_kernel_f<true>(nwin, dh) : lean_scan_kernel_f<false>(nwin, dh); }
+
+// Lean or full, for one launch of a scan: lean where nothing the full instance carries on top can run — the register-band /
+// Hamming-count form (wf_gw = 0) of a fused in-memory search over one sequence, no two blocks of the launch with the same
+// hash, and Levenshtein with a budget of at most 2 or substitutions only.  Everything else — equal n-grams, k = 3 and 4 on
+// the band when the switches keep the bit-vector forms away — takes the full instance.  A function of the search's
+// arguments and the switches, as plan_scan and choose_launch_blocks are.
+bool scan_is_lean(uint32_t mode, uint32_t k, const FzScanArgs &fa, int wf_gw, bool seg, bool ragged) {
+    if (!fa.fused || seg || ragged || wf_gw != 0 || (fa.flags & FZ_FLAG_DUP_HASHES)) return false;
+    return mode == FZ_MODE_SUBS || (mode == FZ_MODE_LEV && k <= 2);
+}
+
 // The ragged instances (fz_batch_search: a batch of sequences packed back to back): every form of the in-memory search.
 // The register-band / Hamming-count / hit-emitting forms come with and without the one-v_and slot address (sa); the
 // bit-vector and lane-per-cell forms only in the general form, which serves every slot shift.
@@ -1100,6 +1129,32 @@ ScanPlan plan_scan(const Search &q, const FzGeom &geom, uint32_t n_cus, bool wit
     return sp;
 }
 
+// The block fields of one scan launch that starts at block g0 of the search (fa.mask1 and fa.d2 set): the longest run of
+// blocks (at most 8) whose distinct hashes land in distinct table slots under some multiplier.  One block always fits; equal
+// n-grams (equal hashes) share a slot and raise FZ_FLAG_DUP_HASHES.  -> the number of blocks of the launch.
+uint32_t fill_launch_blocks(FzScanArgs &fa, const Search &q, uint32_t g0, const HashGeom &hgeom) {
+    const uint32_t L = q.plan.L, G = (uint32_t)q.plan.s.size();
+    uint32_t hash_k = 0, lut_shift = 0;
+    const uint32_t nblk = choose_launch_blocks(q.p, q.plan.s.data(), g0, G, L, hash_k, lut_shift);
+    fa.hash_k = hash_k;
+    fa.lut_shift = lut_shift;
+    fa.nblk = nblk;
+    fa.g0 = g0;
+    for (uint32_t b = 0; b < nblk; ++b) {
+        const uint8_t *ng = q.p + q.plan.s[g0 + b];
+        fa.A[b] = load_le32(ng, L) & fa.mask1;
+        fa.B[b] = hgeom.nwin == 2 ? load_le32(ng + fa.d2, 4) : 0;
+        fa.H[b] = hgeom.nwin == 2 ? fz_hash_windows(fa.A[b], load_le32(ng + hgeom.dh, 3), fa.hash_k) : fz_hash_short(fa.A[b], fa.hash_k);
+        fa.s[b] = q.plan.s[g0 + b];
+        fz_block_range(q.mode, q.m, q.k, L, fa.s[b], fa.lo_rel[b], fa.hi_sub[b]);
+    }
+    fa.flags = q.any ? FZ_FLAG_ANY : 0u;
+    for (uint32_t b = 1; b < nblk; ++b)
+        for (uint32_t c = 0; c < b; ++c)
+            if (fa.H[b] == fa.H[c]) fa.flags |= FZ_FLAG_DUP_HASHES;
+    return nblk;
+}
+
 // Enqueue scan (+ separate verify when it cannot be fused) for one shard on its device stream, as plan_scan decided.
 // No host synchronisation.  `behind`: another search of the context is in flight (fz_*_begin with one search pending).
 int enqueue_shard(fz_ctx *ctx, const Shard &sh, const Search &q, bool with_verify, bool copy_back = true, bool behind = false) {
@@ -1175,34 +1230,16 @@ int enqueue_shard(fz_ctx *ctx, const Shard &sh, const Search &q, bool with_verif
     if (ctx->timing && !attach) HIP_TRY(hipEventRecord(d.ev[0], st));
     uint32_t launches = 0;
     for (uint32_t g0 = 0; g0 < G && ntiles > 0;) {
-        // Blocks [g0, g0 + nblk) of this launch and the hash multiplier: the longest run of blocks (at
-        // most 8) whose distinct hashes land in distinct table slots under some multiplier.  One block
-        // always fits; equal n-grams (equal hashes) share a slot.
-        uint32_t hash_k = 0, lut_shift = 0;
-        const uint32_t nblk = choose_launch_blocks(q.p, q.plan.s.data(), g0, G, L, hash_k, lut_shift);
-        fa.hash_k = hash_k;
-        fa.lut_shift = lut_shift;
-        fa.nblk = nblk;
-        fa.g0 = g0;
-        for (uint32_t b = 0; b < nblk; ++b) {
-            const uint8_t *ng = q.p + q.plan.s[g0 + b];
-            fa.A[b] = load_le32(ng, L) & fa.mask1;
-            fa.B[b] = nwin == 2 ? load_le32(ng + fa.d2, 4) : 0;
-            fa.H[b] = nwin == 2 ? fz_hash_windows(fa.A[b], load_le32(ng + dh, 3), fa.hash_k) : fz_hash_short(fa.A[b], fa.hash_k);
-            fa.s[b] = q.plan.s[g0 + b];
-            fz_block_range(q.mode, q.m, q.k, L, fa.s[b], fa.lo_rel[b], fa.hi_sub[b]);
-        }
+        // Blocks [g0, g0 + nblk) of this launch, the hash multiplier and whether two of the blocks hash alike
+        const uint32_t nblk = fill_launch_blocks(fa, q, g0, hgeom);
         // the final kernel of the search publishes the counters to the host (direct mode)
         const bool verify_follows = with_verify && !fa.fused;
         fa.host_hdr = (direct && !verify_follows && g0 + nblk >= G) ? reinterpret_cast<uint64_t>(d.h_stage_dev) : 0;
-        // equal n-grams (equal hashes) share a table slot: the rare path then compares with every block
-        fa.flags = q.any ? FZ_FLAG_ANY : 0u;
-        for (uint32_t b = 1; b < nblk; ++b)
-            for (uint32_t c = 0; c < b; ++c)
-                if (fa.H[b] == fa.H[c]) fa.flags |= FZ_FLAG_DUP_HASHES;
         const bool ragged = geom_is_ragged(sh.geom);
+        const bool seg = sh.geom.seg_stride != 0;
         ScanKernel kern = ragged ? batch_scan_kernel(nwin, dh, fa.fused != 0, fa.lut_shift == 2, sp.wfg)
-                                 : scan_kernel(nwin, dh, fa.fused != 0, sh.geom.seg_stride != 0, fa.lut_shift == 2, sp.wfg);
+                          : scan_is_lean(q.mode, q.k, fa, sp.wfg, seg, ragged) ? lean_scan_kernel(nwin, dh, fa.lut_shift == 2)
+                          : scan_kernel(nwin, dh, fa.fused != 0, seg, fa.lut_shift == 2, sp.wfg);
         if (!kern) return fail(FZ_EUNSUPPORTED, "this (lab) build carries no scan kernel for nwin=%d dh=%d", nwin, dh);
         hipEvent_t ev_start = (attach && ctx->timing && g0 == 0) ? d.ev[0] : nullptr;
         hipEvent_t ev_stop = g0 + nblk >= G ? (ext_events ? d.ev[3] : (attach && ctx->timing) ? d.ev[1] : nullptr) : nullptr;
@@ -5621,6 +5658,38 @@ int fz_debug_scan_plan(const uint8_t *p, uint32_t m, uint32_t k, uint64_t buf_le
     for (uint32_t r = 0; r < fa.nreg; ++r) {
         table[4 * r] = fa.reg_wg0[r]; table[4 * r + 1] = fa.reg_nwg[r]; table[4 * r + 2] = fa.reg_tile0[r]; table[4 * r + 3] = fa.reg_end[r];
     }
+    return FZ_OK;
+}
+
+int fz_debug_scan_instance(uint32_t mode, const uint8_t *p, uint32_t m, uint32_t k, uint64_t buf_len, uint32_t n_cus,
+                           uint32_t *n_launches, uint32_t *lean_mask, uint32_t *form) {
+    if (!p || !n_launches || !lean_mask || !form || m == 0 || m / (k + 1) == 0 || n_cus == 0 || (mode != FZ_MODE_LEV && mode != FZ_MODE_SUBS))
+        return fail(FZ_EINVAL, "bad argument");
+    Search q;                                               // what lev_plan / subs_plan make of the search, without a context
+    q.mode = mode; q.m = m; q.k = k; q.p = p;
+    q.plan.L = m / (k + 1);
+    for (uint32_t s = 0; s + q.plan.L <= m; s += q.plan.L) q.plan.s.push_back(s);
+    if (q.plan.s.size() > FZ_MAX_BLOCKS) return fail(FZ_EUNSUPPORTED, "more than %u n-gram blocks", FZ_MAX_BLOCKS);
+    FzGeom geom{};
+    geom.buf_len = buf_len;
+    static FzScanArgs fa;
+    static std::mutex mu;
+    std::lock_guard<std::mutex> lk(mu);
+    memset(&fa, 0, sizeof fa);
+    const ScanPlan sp = plan_scan(q, geom, n_cus, true, false, fa);
+    const HashGeom hgeom(q.plan.L);
+    fa.d2 = hgeom.nwin == 2 ? std::min<uint32_t>(q.plan.L, 8) - 4 : 0;
+    fa.mask1 = hgeom.mask1;
+    uint32_t nl = 0, mask = 0;
+    for (uint32_t g0 = 0; g0 < q.plan.s.size(); ++nl) {
+        const uint32_t nblk = fill_launch_blocks(fa, q, g0, hgeom);
+        if (nblk == 0) return fail(FZ_EDEVICE, "internal: a launch without blocks");
+        if (nl < 32 && scan_is_lean(q.mode, q.k, fa, sp.wfg, false, false)) mask |= 1u << nl;
+        g0 += nblk;
+    }
+    *n_launches = nl;
+    *lean_mask = mask;
+    *form = sp.form;
     return FZ_OK;
 }
 

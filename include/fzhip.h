@@ -688,6 +688,14 @@ int fz_debug_scan_regions(uint64_t ntiles, uint64_t grid, uint32_t n_cus, int st
 int fz_debug_scan_plan(const uint8_t *p, uint32_t m, uint32_t k, uint64_t buf_len, uint32_t n_cus, int shares_chip, uint32_t *grid,
                        uint32_t *form, int *overlapped, uint32_t *n_regions, uint64_t *table);
 
+/* Test hook, no device needed: which scan-kernel instance every launch of a fused in-memory search over one sequence
+ * would run (fzhip.hip: scan_is_lean).  mode = FZ_MODE_LEV (1) or FZ_MODE_SUBS (2), budget k, shard and GPU as in
+ * fz_debug_scan_plan.  *n_launches = scan launches of the search; bit i of *lean_mask = launch i (i < 32) runs the lean
+ * instance (no equal-n-gram slot sets, register bands for k <= 2 only), clear = the full one.  *form = FZ_FORM_* as in
+ * fz_debug_scan_plan: only FZ_FORM_FUSED_BAND has lean instances.  A function of the arguments and the FZ_* switches. */
+int fz_debug_scan_instance(uint32_t mode, const uint8_t *p, uint32_t m, uint32_t k, uint64_t buf_len, uint32_t n_cus,
+                           uint32_t *n_launches, uint32_t *lean_mask, uint32_t *form);
+
 /* Test hook (no device needed): the host half of the exchange step of a collective search (what follows the
  * ncclAllGather).  `blocks` = `world` blocks of 1024 + cap * 24 bytes, block r = what rank r contributed: 128 64-bit
  * counters (word 1 = records the rank produced) followed by min(count, cap) device records (see fz_debug_order_records);
