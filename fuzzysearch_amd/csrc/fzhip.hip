@@ -146,21 +146,59 @@ constexpr uint64_t kFirstCopyRecs = 4096;        // records fetched together wit
 constexpr uint64_t kHostRecs = 16384;            // records the pinned staging buffer holds (direct mode)
 static_assert(kHeaderBytes == FZ_HDR_WORDS * 8, "header layout");
 
+// What one enqueue decided and the collection of that search needs to know, kept in the result slot the search was launched
+// into.  Writers: enqueue_shard (starts from a fresh record) and the launch half of run_generic.  Readers: collect_shard, the
+// collect half of run_generic, search_enqueue (form_used, launches_used) and emit_matches (fused_used).
+struct SearchRun {
+    bool last_direct = false;                    // mode of the search being collected
+    bool timed = true;                           // the search being collected recorded its start event
+    bool fused_used = false;
+    uint32_t form_used = 0;                      // FZ_FORM_* of the last enqueue
+    uint32_t launches_used = 0;                  // scan launches of the last enqueue on this device
+    bool verify_launched = false;                // the last enqueue ran fz_verify_kernel (ev[2] recorded)
+    int scan_end_event = 1;                      // which event marks the end of the last scan (1 or 3)
+    int verify_end_event = 2;                    // ... and of the verification kernel behind it (2, or 3 = the completion event)
+    bool on_alt = false;                         // the search of this result slot scans on stream_alt (DevState)
+    // what the search being collected ran with (an overflow is judged against these, not against buffers
+    // that a search collected in between may have grown)
+    uint64_t hit_cap_used = 0, rec_cap_used = 0;
+    // the generic search (run_generic; in flight it has a lane to itself, not a slot)
+    bool dedup_used = false;                     // the search being collected ran with the window table (row count = counters[FZ_HDR_GEN_ROWS])
+    bool gen_multi_used = false;                 // ... and its automaton as fz_gen_hit_kernel (counters[FZ_HDR_GEN_FAIL]: hits it gave up on)
+    bool fold_was_direct = false;                // mode of the folded search being collected
+    uint64_t fold_copied = 0;                    // folded generic search: pairs fetched with the counters
+    int lp_end_event = 2;                        // which event marks the end of the last automaton kernel (2, or 3 = the completion)
+};
+
+// One result slot of a device state: where a search's counters and records arrive, the events around its kernels, and
+// what it ran with.  A device state has two: fz_lev_ngrams_begin with one search already in flight launches into the
+// second, so that the host orders the records of search i while search i + 1 scans (two-deep pipeline).
+struct ResultSlot {
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    uint8_t *h_stage = nullptr;                  // pinned, kHeaderBytes + kHostRecs * sizeof(FzRec)
+    uint8_t *h_stage_dev = nullptr;              // the same memory as the device addresses it
+    uint8_t *d_send = nullptr;                   // RCCL (fz_comm_*): the snapshot of a collective search's counters + records (DevState::comm)
+    hipEvent_t ev_snap = nullptr;                // ... recorded behind the copy that takes it
+    bool snap_taken = false;                     // ... and a search has taken one into this slot (ev_snap was recorded)
+    SearchRun run;
+};
+
 struct DevState {
     int device = 0;
     hipStream_t stream = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    ResultSlot slots[2];
+    int slot_id = 0;                             // which of the two result slots is the current one
+    ResultSlot &cur() { return slots[slot_id]; }
+    const ResultSlot &cur() const { return slots[slot_id]; }
+    void swap_slot() { slot_id ^= 1; }
     uint64_t *d_hits = nullptr;
     uint64_t hit_cap = 0;
     uint8_t *d_out = nullptr;                    // [header kHeaderBytes][recs]
     uint64_t rec_cap = 0;
-    uint8_t *h_stage = nullptr;                  // pinned, kHeaderBytes + kHostRecs * sizeof(FzRec)
-    uint8_t *h_stage_dev = nullptr;              // the same memory as the device addresses it
-    // Direct mode: the kernels write records and (last workgroup) the counters straight into h_stage,
+    // Direct mode: the kernels write records and (last workgroup) the counters straight into the slot's h_stage,
     // no D2H copy command.  Left when a search produces more than kHostRecs records, re-entered when
     // the counts are small again.
     bool direct = true;
-    bool last_direct = false;                    // mode of the search being collected
     // Large record sets of the automaton kernels (10^5 .. 10^6 records): a pinned, device-mapped host
     // buffer that grows on demand; the kernel's stores cross PCIe while it runs instead of a D2H copy
     // into pageable memory afterwards.
@@ -172,8 +210,6 @@ struct DevState {
     uint8_t *d_gen_dedup = nullptr;               // window table of the generic search (FzGenDedup, fz_device.h)
     bool dedup_zeroed = false;                   // ... zeroed behind the last search that used it
     uint64_t gen_dedup_arg = 0;                  // ... its address for the kernels of the search being launched (0: no table)
-    bool dedup_used = false;                     // the search being collected ran with it (row count = counters[FZ_HDR_GEN_ROWS])
-    bool gen_multi_used = false;                 // ... and its automaton as fz_gen_hit_kernel (counters[FZ_HDR_GEN_FAIL]: hits it gave up on)
     uint64_t gen_rows_cap = 0;                   // rows
     uint8_t *h_big = nullptr;
     uint64_t big_cap = 0;                        // records
@@ -184,25 +220,14 @@ struct DevState {
     hipEvent_t rec_ev[10] = {};                  // fz_batch_upload_records, _fasta: the spans of its copy and kernels (created on first use)
     uint64_t first_copy = 512;                   // records fetched with the header (tracks the last count)
     bool header_zeroed = false;                  // the counters were already zeroed after the last D2H copy
-    bool verify_launched = false;                // the last enqueue ran fz_verify_kernel (ev[2] recorded)
-    int scan_end_event = 1;                      // which event marks the end of the last scan (1 or 3)
-    int verify_end_event = 2;                    // ... and of the verification kernel behind it (2, or 3 = the completion event)
     // staging of the last closed file stream, kept for the next one (pinning 2 x 65 MiB costs ~30 ms)
     uint8_t *stream_h[2] = {nullptr, nullptr};
     uint8_t *stream_d = nullptr;
     uint64_t stream_cap = 0, stream_d_bytes = 0;
     int n_cus = 256;
-    // what the search being collected ran with (an overflow is judged against these, not against buffers
-    // that a search collected in between may have grown)
-    uint64_t hit_cap_used = 0, rec_cap_used = 0;
-    bool fused_used = false;
-    uint32_t form_used = 0;                      // FZ_FORM_* of the last enqueue
-    bool timed = true;                           // the search being collected recorded its start event
     double last_filter_ms = 0;                   // scan span of the search collected last on this device (fz_device_ms)
-    uint64_t fold_guess = 8192, fold_copied = 0; // folded generic search: pairs fetched with the counters
+    uint64_t fold_guess = 8192;                  // folded generic search: pairs to fetch with the counters (tracks the last count)
     bool fold_direct = true;                     // ... or written straight into h_stage by the automaton kernel (while they fit)
-    bool fold_was_direct = false;                // mode of the folded search being collected
-    int lp_end_event = 2;                        // which event marks the end of the last automaton kernel (2, or 3 = the completion)
     uint8_t *d_pat = nullptr;                    // pattern in HBM (subsequences longer than FZ_MAX_M, fz_verify_big_kernel)
     uint64_t pat_cap = 0;
     // multi-pattern search (fz_lev_ngrams_multi): the group descriptor and the counters (fixed sizes, allocated on first use),
@@ -215,52 +240,32 @@ struct DevState {
     // records of a pattern searched on its own on their way to the fold; both grow and stay, like the buffers above
     uint8_t *d_assign = nullptr, *d_assign_recs = nullptr;
     uint64_t assign_cap = 0, assign_rec_cap = 0;
-    int slot_id = 0;                             // which of the two result slots is the current one
-    uint32_t launches_used = 0;                  // scan launches of the last enqueue on this device
     // Two fused searches in flight: the younger one's scan on the stream the older one does not use, so that it starts
     // while the older scan drains instead of behind it (fz_ctx::streams; enqueue_shard states why the two may share the
-    // device).  stream_alt has a counter block of its own; on_alt: the search of this result slot scans there.
+    // device).  stream_alt has a counter block of its own; SearchRun::on_alt says which search scans there.
     hipStream_t stream_alt = nullptr;
     uint8_t *d_hdr_alt = nullptr;
-    bool on_alt = false;
     // RCCL (fz_comm_*): this device state is rank comm_rank of a communicator.  A search of such a context leaves
-    // its counters + records in d_out; a device-to-device snapshot (d_send[slot], taken on the scan stream right
+    // its counters + records in d_out; a device-to-device snapshot (the slot's d_send, taken on the scan stream right
     // behind the kernels, so a younger search may reuse d_out) is what the all-gather sends.
     ncclComm_t comm = nullptr;
     int comm_rank = -1;
     hipStream_t comm_stream = nullptr;           // default priority: the collective runs next to the (low-priority) scan
-    uint8_t *d_send[2] = {nullptr, nullptr};
     uint64_t send_cap = 0;                       // records a snapshot holds
     uint8_t *d_recv = nullptr, *h_recv = nullptr;
     uint64_t recv_bytes = 0;
-    hipEvent_t ev_snap[2] = {nullptr, nullptr}, ev_done = nullptr;
-    bool snap_taken[2] = {false, false};
-    // The second result slot: fz_lev_ngrams_begin with one search already in flight launches into it, so
-    // that the host orders the records of search i while search i + 1 scans (two-deep pipeline).
-    struct Slot {
-        hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-        uint8_t *h_stage = nullptr, *h_stage_dev = nullptr;
-        bool last_direct = false, verify_launched = false, fused_used = false, timed = true, on_alt = false;
-        int scan_end_event = 1, verify_end_event = 2;
-        uint64_t hit_cap_used = 0, rec_cap_used = 0;
-        int slot_id = 1;
-    } other;
-    void swap_slot() {
-        std::swap(slot_id, other.slot_id);
-        for (int i = 0; i < 4; ++i) std::swap(ev[i], other.ev[i]);
-        std::swap(h_stage, other.h_stage);
-        std::swap(h_stage_dev, other.h_stage_dev);
-        std::swap(last_direct, other.last_direct);
-        std::swap(verify_launched, other.verify_launched);
-        std::swap(timed, other.timed);
-        std::swap(fused_used, other.fused_used);
-        std::swap(on_alt, other.on_alt);
-        std::swap(scan_end_event, other.scan_end_event);
-        std::swap(verify_end_event, other.verify_end_event);
-        std::swap(hit_cap_used, other.hit_cap_used);
-        std::swap(rec_cap_used, other.rec_cap_used);
-    }
+    hipEvent_t ev_done = nullptr;
 };
+
+// The events around a search's kernels: the scan (f), the kernel behind it (v), the whole (t); read on demand (fz_ctx::tref).
+struct TimingRef { DevState *d; hipEvent_t f0, f1, v0, v1, t0, t1; };
+// The timing reference of the search in the device's current slot.  `generic`: the kernel behind the scan is the
+// automaton of run_generic, else the stand-alone verification (none: no span).
+TimingRef timing_ref(DevState &d, bool generic) {
+    const ResultSlot &s = d.cur();
+    hipEvent_t v0 = generic || s.run.verify_launched ? s.ev[1] : nullptr;
+    return {&d, s.ev[0], s.ev[s.run.scan_end_event], v0, s.ev[generic ? s.run.lp_end_event : s.run.verify_end_event], s.ev[0], s.ev[3]};
+}
 
 // A batch of sequences (fz_batch_upload): unsegmented to the planner, the tables in the segment fields (fz_device.h).
 inline bool geom_is_ragged(const FzGeom &g) { return g.seg_stride == 0 && g.seg_j1 != 0; }
@@ -370,9 +375,7 @@ struct ShardOut {
     std::vector<fz_match> rows;                  // the shard's records in the reference's order (multi-shard searches)
     bool rerun = false;
     uint64_t nh = 0, nr = 0, bytes = 0;
-    bool has_tref = false;
-    DevState *td = nullptr;
-    hipEvent_t tev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    TimingRef tref{};                            // d == nullptr: the search was not timed
 };
 
 }  // namespace
@@ -438,7 +441,6 @@ struct fz_ctx {
     // The spans are read from the events only when somebody asks (fz_stats / fz_device_ms): a hipEventElapsedTime call
     // costs ~5 us of host time, two or three of them sat between the completion of every search and its result.  The
     // references die with the next launch of the context (whose enqueue re-records the events).
-    struct TimingRef { DevState *d; hipEvent_t f0, f1, v0, v1, t0, t1; };
     std::vector<TimingRef> tref;
     int comm_world = 0;
     bool snapshot = false;
@@ -486,7 +488,7 @@ inline DevState &lane_dev(fz_ctx *ctx, int dev) { return ctx->lane ? ctx->devs2[
 
 // fz_stats / fz_device_ms: the kernel spans of the search collected last, read from its events now.
 void resolve_timing(fz_ctx *ctx) {
-    for (const fz_ctx::TimingRef &r : ctx->tref) {
+    for (const TimingRef &r : ctx->tref) {
         float f = 0, v = 0, t = 0;
         if (hipSetDevice(r.d->device) != hipSuccess) continue;
         if (r.f0 && hipEventElapsedTime(&f, r.f0, r.f1) != hipSuccess) f = 0;
@@ -565,19 +567,19 @@ int ensure_gen_rows(DevState &d) {
 // Snapshot buffers of a communicator's device state: at least `cap` records each; contents are kept (a snapshot
 // that is waiting for its all-gather survives the growth).
 int ensure_send(DevState &d, uint64_t cap) {
-    if (d.send_cap >= cap && d.d_send[0]) return FZ_OK;
+    if (d.send_cap >= cap && d.slots[0].d_send) return FZ_OK;
     HIP_TRY(hipSetDevice(d.device));
-    for (int i = 0; i < 2; ++i) {
+    for (ResultSlot &s : d.slots) {
         uint8_t *nb = nullptr;
         HIP_TRY(hipMalloc(reinterpret_cast<void **>(&nb), kHeaderBytes + cap * sizeof(FzRec)));
-        if (d.d_send[i]) {
+        if (s.d_send) {
             HIP_TRY(hipDeviceSynchronize());
-            HIP_TRY(hipMemcpy(nb, d.d_send[i], kHeaderBytes + d.send_cap * sizeof(FzRec), hipMemcpyDeviceToDevice));
-            HIP_TRY(hipFree(d.d_send[i]));
+            HIP_TRY(hipMemcpy(nb, s.d_send, kHeaderBytes + d.send_cap * sizeof(FzRec), hipMemcpyDeviceToDevice));
+            HIP_TRY(hipFree(s.d_send));
         } else {
             HIP_TRY(hipMemset(nb, 0, kHeaderBytes));
         }
-        d.d_send[i] = nb;
+        s.d_send = nb;
     }
     d.send_cap = cap;
     return FZ_OK;
@@ -1166,9 +1168,10 @@ int enqueue_shard(fz_ctx *ctx, const Shard &sh, const Search &q, bool with_verif
     // direct mode needs a kernel to publish the counters: an empty buffer launches none
     const bool snapshot = copy_back && with_verify && q.collective;      // collective search: records stay on the device
     const bool direct = copy_back && d.direct && !no_direct && !snapshot && sh.geom.buf_len > 0 && !q.plan.s.empty();
-    if (direct && with_verify) recs = reinterpret_cast<FzRec *>(d.h_stage_dev + kHeaderBytes);
-    d.last_direct = direct;
-    d.timed = ctx->timing;
+    if (direct && with_verify) recs = reinterpret_cast<FzRec *>(d.cur().h_stage_dev + kHeaderBytes);
+    SearchRun &run = d.cur().run = SearchRun{};
+    run.last_direct = direct;
+    run.timed = ctx->timing;
 
     FzScanArgs fa;
     fill_common_args(fa, sh, q);
@@ -1199,8 +1202,8 @@ int enqueue_shard(fz_ctx *ctx, const Shard &sh, const Search &q, bool with_verif
     //  - d_out: an overlapped scan on d.stream uses its header as counters (zeroed in stream order by the memset below or
     //    by the publishing workgroup of the last search on d.stream) and writes no records there: direct mode puts them in
     //    the pinned slot.  The scan on stream_alt never touches d_out.
-    //  - the pinned slots: every search writes the records and the published counters of its own result slot (h_stage_dev
-    //    of the slot enqueue runs in; pending_begin swaps the slots around the launch).
+    //  - the pinned slots: every search writes the records and the published counters of its own result slot (the current
+    //    one while enqueue runs; pending_begin swaps the slots around the launch).
     //  - d_hdr_alt: one search at a time on stream_alt (the two in flight are on different streams); its publishing
     //    workgroup zeroes it for the next one, which is ordered behind it on that stream.
     //  - pattern staging (d_pat): an overlapped scan reads the pattern from its argument block; a predecessor staged on
@@ -1210,8 +1213,8 @@ int enqueue_shard(fz_ctx *ctx, const Shard &sh, const Search &q, bool with_verif
     //    launched before the first is collected (pending_begin), so nothing overlaps until direct mode returns.
     // Synchronous calls, the first search of a pipeline and everything not overlapped stay on d.stream.
     if (sp.overlapped && fa.pat_g) return fail(FZ_EDEVICE, "internal: an overlapped scan with the pattern staged in HBM");
-    const bool alt = sp.overlapped && !d.other.on_alt;
-    d.on_alt = alt;
+    const bool alt = sp.overlapped && !d.slots[d.slot_id ^ 1].run.on_alt;
+    run.on_alt = alt;
     const hipStream_t st = alt ? d.stream_alt : d.stream;
     if (alt) counters = reinterpret_cast<unsigned long long *>(d.d_hdr_alt);
     else {
@@ -1227,22 +1230,22 @@ int enqueue_shard(fz_ctx *ctx, const Shard &sh, const Search &q, bool with_verif
     // ... and whenever the scan launches a kernel at all, its start / end events (ev[0], ev[1]: fz_stats' filter_ms) ride
     // on the first / last launch as well instead of two packets of their own in front of and behind the scan
     const bool attach = ntiles > 0 && G > 0;
-    if (ctx->timing && !attach) HIP_TRY(hipEventRecord(d.ev[0], st));
+    if (ctx->timing && !attach) HIP_TRY(hipEventRecord(d.cur().ev[0], st));
     uint32_t launches = 0;
     for (uint32_t g0 = 0; g0 < G && ntiles > 0;) {
         // Blocks [g0, g0 + nblk) of this launch, the hash multiplier and whether two of the blocks hash alike
         const uint32_t nblk = fill_launch_blocks(fa, q, g0, hgeom);
         // the final kernel of the search publishes the counters to the host (direct mode)
         const bool verify_follows = with_verify && !fa.fused;
-        fa.host_hdr = (direct && !verify_follows && g0 + nblk >= G) ? reinterpret_cast<uint64_t>(d.h_stage_dev) : 0;
+        fa.host_hdr = (direct && !verify_follows && g0 + nblk >= G) ? reinterpret_cast<uint64_t>(d.cur().h_stage_dev) : 0;
         const bool ragged = geom_is_ragged(sh.geom);
         const bool seg = sh.geom.seg_stride != 0;
         ScanKernel kern = ragged ? batch_scan_kernel(nwin, dh, fa.fused != 0, fa.lut_shift == 2, sp.wfg)
                           : scan_is_lean(q.mode, q.k, fa, sp.wfg, seg, ragged) ? lean_scan_kernel(nwin, dh, fa.lut_shift == 2)
                           : scan_kernel(nwin, dh, fa.fused != 0, seg, fa.lut_shift == 2, sp.wfg);
         if (!kern) return fail(FZ_EUNSUPPORTED, "this (lab) build carries no scan kernel for nwin=%d dh=%d", nwin, dh);
-        hipEvent_t ev_start = (attach && ctx->timing && g0 == 0) ? d.ev[0] : nullptr;
-        hipEvent_t ev_stop = g0 + nblk >= G ? (ext_events ? d.ev[3] : (attach && ctx->timing) ? d.ev[1] : nullptr) : nullptr;
+        hipEvent_t ev_start = (attach && ctx->timing && g0 == 0) ? d.cur().ev[0] : nullptr;
+        hipEvent_t ev_stop = g0 + nblk >= G ? (ext_events ? d.cur().ev[3] : (attach && ctx->timing) ? d.cur().ev[1] : nullptr) : nullptr;
         launch(kern, grid, dim3(FZ_FILTER_THREADS), sp.lds, st, ev_start, ev_stop, sh.d_buf, fa, ntiles, d.d_hits, recs, counters);
         HIP_TRY(hipGetLastError());
         ++launches;
@@ -1250,19 +1253,17 @@ int enqueue_shard(fz_ctx *ctx, const Shard &sh, const Search &q, bool with_verif
     }
     // ev[1] = end of the scan.  When the results need no copy and no verify kernel follows, ev[3] is
     // recorded at the same point of the stream: one event packet less on the critical path.
-    d.scan_end_event = (copy_back && direct && !(with_verify && !fa.fused)) ? 3 : 1;
-    if (d.scan_end_event == 1 && ctx->timing && !attach) HIP_TRY(hipEventRecord(d.ev[1], st));
-    d.verify_launched = false;
-    d.verify_end_event = 2;
+    run.scan_end_event = (copy_back && direct && !(with_verify && !fa.fused)) ? 3 : 1;
+    if (run.scan_end_event == 1 && ctx->timing && !attach) HIP_TRY(hipEventRecord(d.cur().ev[1], st));
     // the verification kernel is the search's last one when its records go straight to the host: then the completion
     // event rides on its launch (no ev[2] / ev[3] packets behind it; the verify span is ev[1] .. ev[3])
-    hipEvent_t v_stop = (copy_back && direct && !snapshot) ? d.ev[3] : nullptr;
+    hipEvent_t v_stop = (copy_back && direct && !snapshot) ? d.cur().ev[3] : nullptr;
     if (with_verify && !fa.fused && ntiles > 0 && G > 0) {
-        d.verify_launched = true;
-        if (v_stop) d.verify_end_event = 3;
+        run.verify_launched = true;
+        if (v_stop) run.verify_end_event = 3;
         fa.nblk = 0;
         fa.g0 = 0;
-        fa.host_hdr = direct ? reinterpret_cast<uint64_t>(d.h_stage_dev) : 0;
+        fa.host_hdr = direct ? reinterpret_cast<uint64_t>(d.cur().h_stage_dev) : 0;
         using VerifyKernel = void (*)(const uint8_t *, const FzScanArgs, const uint64_t *, FzRec *, unsigned long long *);
         VerifyKernel vk;
         dim3 vgrid, vblock;
@@ -1301,33 +1302,33 @@ int enqueue_shard(fz_ctx *ctx, const Shard &sh, const Search &q, bool with_verif
         launch(vk, vgrid, vblock, (uint32_t)vlds, d.stream, nullptr, v_stop, sh.d_buf, fa, d.d_hits, recs, counters);
         HIP_TRY(hipGetLastError());
     }
-    const bool completion_attached = ext_events || (d.verify_launched && v_stop);
+    const bool completion_attached = ext_events || (run.verify_launched && v_stop);
     if (copy_back) {
-        if (d.verify_launched && ctx->timing && d.verify_end_event == 2) HIP_TRY(hipEventRecord(d.ev[2], d.stream));
+        if (run.verify_launched && ctx->timing && run.verify_end_event == 2) HIP_TRY(hipEventRecord(d.cur().ev[2], d.stream));
         if (snapshot) {
             // counters to the host (overflow checks, statistics); counters + records to this slot's snapshot
-            HIP_TRY(hipMemcpyAsync(d.h_stage, d.d_out, kHeaderBytes, hipMemcpyDeviceToHost, d.stream));
+            HIP_TRY(hipMemcpyAsync(d.cur().h_stage, d.d_out, kHeaderBytes, hipMemcpyDeviceToHost, d.stream));
             int rc = ensure_send(d, d.rec_cap);
             if (rc) return rc;
-            HIP_TRY(hipMemcpyAsync(d.d_send[d.slot_id], d.d_out, kHeaderBytes + d.rec_cap * sizeof(FzRec), hipMemcpyDeviceToDevice, d.stream));
-            HIP_TRY(hipEventRecord(d.ev_snap[d.slot_id], d.stream));
-            d.snap_taken[d.slot_id] = true;
+            HIP_TRY(hipMemcpyAsync(d.cur().d_send, d.d_out, kHeaderBytes + d.rec_cap * sizeof(FzRec), hipMemcpyDeviceToDevice, d.stream));
+            HIP_TRY(hipEventRecord(d.cur().ev_snap, d.stream));
+            d.cur().snap_taken = true;
         } else if (!direct) {
             d.first_copy = std::min<uint64_t>(std::min<uint64_t>(d.first_copy, kFirstCopyRecs), d.rec_cap);
-            HIP_TRY(hipMemcpyAsync(d.h_stage, d.d_out, kHeaderBytes + d.first_copy * sizeof(FzRec), hipMemcpyDeviceToHost,
+            HIP_TRY(hipMemcpyAsync(d.cur().h_stage, d.d_out, kHeaderBytes + d.first_copy * sizeof(FzRec), hipMemcpyDeviceToHost,
                                    d.stream));
         }
-        if (!completion_attached) HIP_TRY(hipEventRecord(d.ev[3], st));
+        if (!completion_attached) HIP_TRY(hipEventRecord(d.cur().ev[3], st));
         // the counters are zeroed for the NEXT search now, off the critical path of that call: by the
         // publishing workgroup itself in direct mode, by a memset behind the copy otherwise
         if (!direct) HIP_TRY(hipMemsetAsync(d.d_out, 0, kHeaderBytes, d.stream));
         if (!alt) d.header_zeroed = true;
     }
-    d.launches_used = launches;                  // (summed by search_enqueue: this may run on the device's worker thread)
-    d.fused_used = fa.fused != 0;
-    d.form_used = sp.form;
-    d.hit_cap_used = d.hit_cap;
-    d.rec_cap_used = d.rec_cap;
+    run.launches_used = launches;                // (summed by search_enqueue: this may run on the device's worker thread)
+    run.fused_used = fa.fused != 0;
+    run.form_used = sp.form;
+    run.hit_cap_used = d.hit_cap;
+    run.rec_cap_used = d.rec_cap;
     return FZ_OK;
 }
 
@@ -1336,60 +1337,56 @@ int enqueue_shard(fz_ctx *ctx, const Shard &sh, const Search &q, bool with_verif
 // (view_ok), which never run on a worker — the context's record view.
 int collect_shard(fz_ctx *ctx, const Shard &sh, bool with_verify, bool view_ok, ShardOut &so, bool collective = false) {
     DevState &d = ctx->devs[sh.dev];
+    const SearchRun &run = d.cur().run;
     HIP_TRY(hipSetDevice(d.device));
     Trace tr;
     so.recs.clear();
     so.hits.clear();
     so.rerun = false;
-    so.has_tref = false;
+    so.tref = {};
     so.nh = so.nr = so.bytes = 0;
     // wait for the copy only: the memset that pre-zeroes the header for the next search runs behind it
-    HIP_TRY(hipEventSynchronize(d.ev[3]));
+    HIP_TRY(hipEventSynchronize(d.cur().ev[3]));
     tr.mark("  sync");
-    const unsigned long long *cnt = reinterpret_cast<const unsigned long long *>(d.h_stage);
+    const unsigned long long *cnt = reinterpret_cast<const unsigned long long *>(d.cur().h_stage);
     uint64_t nh = cnt[0];
     const uint64_t nr = cnt[1];
-    const bool fused = with_verify && d.fused_used;
+    const bool fused = with_verify && run.fused_used;
     if (fused) { nh = 0; for (int i = 0; i < 64; ++i) nh += cnt[8 + i]; }
     bool rerun = false;
-    if (nh > d.hit_cap_used && !fused) {
+    if (nh > run.hit_cap_used && !fused) {
         HIP_TRY(hipStreamSynchronize(d.stream));          // a second search in flight still uses the old buffers
         HIP_TRY(hipStreamSynchronize(d.stream_alt));
         int rc = ensure_hits(d, nh + nh / 8 + 1024);
         if (rc) return rc;
         rerun = true;
     }
-    if (d.last_direct && with_verify && nr > kHostRecs) d.direct = false;   // too many for the staging buffer
-    if (nr > (d.last_direct ? kHostRecs : d.rec_cap_used)) {
+    if (run.last_direct && with_verify && nr > kHostRecs) d.direct = false;   // too many for the staging buffer
+    if (nr > (run.last_direct ? kHostRecs : run.rec_cap_used)) {
         HIP_TRY(hipStreamSynchronize(d.stream));
         HIP_TRY(hipStreamSynchronize(d.stream_alt));
         int rc = ensure_recs(d, nr + nr / 8 + 1024);
         if (rc) return rc;
         rerun = true;
     }
-    if (!d.last_direct && nr * 4 < kHostRecs) d.direct = true;
+    if (!run.last_direct && nr * 4 < kHostRecs) d.direct = true;
     so.rerun = rerun;
     if (rerun) return FZ_OK;
     d.last_filter_ms = 0;
-    if (d.timed) {
-        so.has_tref = true;
-        so.td = &d;
-        so.tev[0] = d.ev[0]; so.tev[1] = d.ev[d.scan_end_event]; so.tev[2] = d.verify_launched ? d.ev[1] : nullptr;
-        so.tev[3] = d.ev[d.verify_end_event]; so.tev[4] = d.ev[0]; so.tev[5] = d.ev[3];
-    }
+    if (run.timed) so.tref = timing_ref(d, /*generic=*/false);
     so.bytes = sh.geom.buf_len;
     so.nh = nh;
     if (with_verify && collective) {
         // collective search: the records travel in the all-gather (gather_records), not through this host
-    } else if (with_verify && view_ok && d.last_direct) {
+    } else if (with_verify && view_ok && run.last_direct) {
         so.nr = nr;
-        ctx->view = reinterpret_cast<const FzRec *>(d.h_stage + kHeaderBytes);
+        ctx->view = reinterpret_cast<const FzRec *>(d.cur().h_stage + kHeaderBytes);
         ctx->view_n = nr;
     } else if (with_verify) {
         so.nr = nr;
         so.recs.resize(nr);
-        const uint64_t first = d.last_direct ? nr : std::min<uint64_t>(nr, d.first_copy);
-        if (first) memcpy(so.recs.data(), d.h_stage + kHeaderBytes, first * sizeof(FzRec));
+        const uint64_t first = run.last_direct ? nr : std::min<uint64_t>(nr, d.first_copy);
+        if (first) memcpy(so.recs.data(), d.cur().h_stage + kHeaderBytes, first * sizeof(FzRec));
         if (nr > first)
             HIP_TRY(hipMemcpy(so.recs.data() + first, d.d_out + kHeaderBytes + first * sizeof(FzRec),
                               (nr - first) * sizeof(FzRec), hipMemcpyDeviceToHost));
@@ -1588,12 +1585,12 @@ int gather_records(fz_ctx *ctx, fz_seq *seq, std::vector<FzRec> &recs) {
             }
             bool has_shard = false;
             for (const Shard &sh : seq->shards) has_shard |= &ctx->devs[sh.dev] == &d;
-            if (has_shard && d.snap_taken[d.slot_id]) HIP_TRY(hipStreamWaitEvent(d.comm_stream, d.ev_snap[d.slot_id], 0));
-            else HIP_TRY(hipMemsetAsync(d.d_send[d.slot_id], 0, kHeaderBytes, d.comm_stream));   // this rank holds nothing of the sequence
+            if (has_shard && d.cur().snap_taken) HIP_TRY(hipStreamWaitEvent(d.comm_stream, d.cur().ev_snap, 0));
+            else HIP_TRY(hipMemsetAsync(d.cur().d_send, 0, kHeaderBytes, d.comm_stream));   // this rank holds nothing of the sequence
         }
         NCCL_TRY(rccl_api()->GroupStart());
         for (DevState &d : ctx->devs)
-            NCCL_TRY(rccl_api()->AllGather(d.d_send[d.slot_id], d.d_recv, bytes, ncclChar, d.comm, d.comm_stream));
+            NCCL_TRY(rccl_api()->AllGather(d.cur().d_send, d.d_recv, bytes, ncclChar, d.comm, d.comm_stream));
         NCCL_TRY(rccl_api()->GroupEnd());
         DevState &d0 = ctx->devs[0];
         HIP_TRY(hipSetDevice(d0.device));
@@ -1637,9 +1634,9 @@ int search_enqueue(fz_ctx *ctx, fz_seq *seq, const Search &q, bool with_verify, 
     });
     if (rc) return rc;
     for (const Shard &sh : seq->shards) {
-        const DevState &d = lane_dev(ctx, sh.dev);
-        ctx->stats.filter_launches += d.launches_used;
-        ctx->stats.verify_form = d.form_used;
+        const SearchRun &run = lane_dev(ctx, sh.dev).cur().run;
+        ctx->stats.filter_launches += run.launches_used;
+        ctx->stats.verify_form = run.form_used;
     }
     return FZ_OK;
 }
@@ -1675,7 +1672,7 @@ int search_collect(fz_ctx *ctx, fz_seq *seq, const Search &q, bool with_verify, 
             ShardOut &so = ctx->souts[si];
             int r = collect_shard(ctx, seq->shards[si], with_verify, ns == 1, so, collective);
             if (r || so.rerun || !order_rows) return r;
-            const bool dense = ctx->devs[seq->shards[si].dev].fused_used;
+            const bool dense = ctx->devs[seq->shards[si].dev].cur().run.fused_used;
             return emit_matches(so.recs.data(), so.recs.size(), L, nullptr, nullptr, nglob, nblk, !dense, &so.rows);
         });
         if (rc) return rc;
@@ -1687,7 +1684,7 @@ int search_collect(fz_ctx *ctx, fz_seq *seq, const Search &q, bool with_verify, 
             ctx->stats.bytes_scanned += so.bytes;
             ctx->stats.ngram_hits += so.nh;
             ctx->stats.raw_matches += so.nr;
-            if (so.has_tref) ctx->tref.push_back({so.td, so.tev[0], so.tev[1], so.tev[2], so.tev[3], so.tev[4], so.tev[5]});
+            if (so.tref.d) ctx->tref.push_back(so.tref);
         }
         tr.mark(" collect");
         if (!any_rerun) {
@@ -1807,7 +1804,6 @@ int run_generic(fz_ctx *ctx, fz_seq *seq, const Search &q, std::vector<FzGenRec>
             // (emit_generic) serves searches with more than FZ_GEN_ORDER_MAX hits, several shards and the file API's segments.
             const bool dev_order = !q.any && !q.fold && seq->shards.size() == 1 && sh.geom.seg_stride == 0 && !comm_multi_process(ctx);
             const bool dedup = !sw().gen_no_dedup && sh.geom.seg_stride == 0 && (dev_order || q.fold || q.any);
-            d.dedup_used = dedup;
             d.gen_dedup_arg = 0;
             if (dedup) {
                 HIP_TRY(hipSetDevice(d.device));
@@ -1821,6 +1817,8 @@ int run_generic(fz_ctx *ctx, fz_seq *seq, const Search &q, std::vector<FzGenRec>
             }
             int rc = enqueue_shard(ctx, sh, q, /*with_verify=*/false, /*copy_back=*/false);
             if (rc) return rc;
+            SearchRun &run = d.cur().run;                     // (fresh from enqueue_shard)
+            run.dedup_used = dedup;
             size_t lds = 0;
             uint64_t scratch = 0;
             rc = cand_lists(d, cand_cap, mpad + wpad + FZ_GEN_MCAP * 8, lds, scratch);
@@ -1852,15 +1850,15 @@ int run_generic(fz_ctx *ctx, fz_seq *seq, const Search &q, std::vector<FzGenRec>
             // buffer and its last workgroup publishes the counters there, as the fused scan does for its records — no
             // copy command between the kernel and the host (FZ_NO_DIRECT=1, or more pairs than the buffer holds: the copy).
             const bool fold_direct = q.fold && !env_no_direct() && d.fold_direct && seq->shards.size() == 1;
-            d.fold_was_direct = fold_direct;
+            run.fold_was_direct = fold_direct;
             fa.rec_cap = fold_direct ? kHostRecs : d.rec_cap;
-            if (fold_direct) fa.host_hdr = reinterpret_cast<uint64_t>(d.h_stage_dev);
+            if (fold_direct) fa.host_hdr = reinterpret_cast<uint64_t>(d.cur().h_stage_dev);
             unsigned long long *counters = reinterpret_cast<unsigned long long *>(d.d_out);
-            FzGenRec *recs = reinterpret_cast<FzGenRec *>((fold_direct ? d.h_stage_dev : d.d_out) + kHeaderBytes);
+            FzGenRec *recs = reinterpret_cast<FzGenRec *>((fold_direct ? d.cur().h_stage_dev : d.d_out) + kHeaderBytes);
             static_assert(sizeof(FzGenRec) == sizeof(FzRec), "the generic records share the record buffer");
             const GenHitPlan gp = plan_gen_hit(q, cand_cap);
             const bool multi = ctx->gen_multi && !legacy_now && scratch == 0 && sh.geom.seg_stride == 0 && gp.lds <= 160 * 1024;
-            d.gen_multi_used = multi;
+            run.gen_multi_used = multi;
             if (multi) {
                 fa.cand_cap = gp.capw;
                 if (gp.lds > 64 * 1024)
@@ -1882,8 +1880,8 @@ int run_generic(fz_ctx *ctx, fz_seq *seq, const Search &q, std::vector<FzGenRec>
             // scan, which is what bounds the pair, starves.)
             // the automaton's end event rides on its own launch; for a folded search in direct mode that event is also
             // the search's completion (ev[3]): no event packet of its own anywhere in such a search
-            hipEvent_t lp_stop = fold_direct ? d.ev[3] : ctx->timing ? d.ev[2] : nullptr;
-            d.lp_end_event = fold_direct ? 3 : 2;
+            hipEvent_t lp_stop = fold_direct ? d.cur().ev[3] : ctx->timing ? d.cur().ev[2] : nullptr;
+            run.lp_end_event = fold_direct ? 3 : 2;
             if (multi)
                 launch(gp.kernel, dim3(d.n_cus * kGenHitGridPerCu), dim3(64 * gp.waves), (uint32_t)gp.lds, d.stream, nullptr, lp_stop,
                        sh.d_buf, fa, d.d_hits, recs, counters);
@@ -1891,7 +1889,7 @@ int run_generic(fz_ctx *ctx, fz_seq *seq, const Search &q, std::vector<FzGenRec>
                 launch(lp, dim3(scratch ? kCandScratchGrid : d.n_cus * kLpGridPerCu), dim3(64), (uint32_t)lds, d.stream, nullptr, lp_stop,
                        sh.d_buf, fa, d.d_hits, (uint64_t)0, recs, counters);
             HIP_TRY(hipGetLastError());
-            if (ctx->timing && !lp_stop && !fold_direct) HIP_TRY(hipEventRecord(d.ev[2], d.stream));
+            if (ctx->timing && !lp_stop && !fold_direct) HIP_TRY(hipEventRecord(d.cur().ev[2], d.stream));
             if (dev_order) {
                 hipLaunchKernelGGL(fz_gen_order_kernel, dim3(d.n_cus * 8), dim3(256), 0, d.stream, d.d_hits, fa, counters);
                 hipLaunchKernelGGL(fz_gen_scatter_kernel, dim3(d.n_cus * 8), dim3(256), 0, d.stream, d.d_hits, fa, recs,
@@ -1899,17 +1897,17 @@ int run_generic(fz_ctx *ctx, fz_seq *seq, const Search &q, std::vector<FzGenRec>
                 HIP_TRY(hipGetLastError());
             }
             // folded search: the (few) pairs come back with the counters in ONE copy — as many as the previous search had
-            d.fold_copied = fold_direct ? kHostRecs : q.fold ? std::min<uint64_t>(std::min<uint64_t>(d.fold_guess, kHostRecs), d.rec_cap) : 0;
+            run.fold_copied = fold_direct ? kHostRecs : q.fold ? std::min<uint64_t>(std::min<uint64_t>(d.fold_guess, kHostRecs), d.rec_cap) : 0;
             if (!fold_direct) {
-                HIP_TRY(hipMemcpyAsync(d.h_stage, d.d_out, kHeaderBytes + d.fold_copied * sizeof(FzGenRec), hipMemcpyDeviceToHost, d.stream));
-                HIP_TRY(hipEventRecord(d.ev[3], d.stream));
+                HIP_TRY(hipMemcpyAsync(d.cur().h_stage, d.d_out, kHeaderBytes + run.fold_copied * sizeof(FzGenRec), hipMemcpyDeviceToHost, d.stream));
+                HIP_TRY(hipEventRecord(d.cur().ev[3], d.stream));
                 // the counters are zeroed for the next search now, behind the copy (not in front of that search's scan)
                 HIP_TRY(hipMemsetAsync(d.d_out, 0, kHeaderBytes, d.stream));
             } else {
-                if (!lp_stop) HIP_TRY(hipEventRecord(d.ev[3], d.stream));
+                if (!lp_stop) HIP_TRY(hipEventRecord(d.cur().ev[3], d.stream));
             }
             d.header_zeroed = true;                           // (direct: by the publishing workgroup)
-            if (d.dedup_used) {                               // the window table is cleared for the next search, behind this one
+            if (dedup) {                                      // the window table is cleared for the next search, behind this one
                 HIP_TRY(hipMemsetAsync(d.d_gen_dedup, 0, FZ_GEN_DEDUP_ZERO_BYTES, d.stream));
                 d.dedup_zeroed = true;
             }
@@ -1920,21 +1918,22 @@ int run_generic(fz_ctx *ctx, fz_seq *seq, const Search &q, std::vector<FzGenRec>
         trg.mark(" generic enqueue");
         for (const Shard &sh : seq->shards) {
             DevState &d = lane_dev(ctx, sh.dev);
+            const SearchRun &run = d.cur().run;
             HIP_TRY(hipSetDevice(d.device));
-            HIP_TRY(hipEventSynchronize(d.ev[3]));            // (recorded behind the last command of the search, on whichever stream)
+            HIP_TRY(hipEventSynchronize(d.cur().ev[3]));      // (recorded behind the last command of the search, on whichever stream)
             trg.mark(" generic sync");
-            const unsigned long long *cnt = reinterpret_cast<const unsigned long long *>(d.h_stage);
+            const unsigned long long *cnt = reinterpret_cast<const unsigned long long *>(d.cur().h_stage);
             const uint64_t nh = cnt[0], nr = cnt[1];
             uint64_t novf = cnt[2];
-            if (d.gen_multi_used && cnt[FZ_HDR_GEN_FAIL]) {   // a hit outgrew a wave's share of the list / its match buffer: one wave per hit
+            if (run.gen_multi_used && cnt[FZ_HDR_GEN_FAIL]) { // a hit outgrew a wave's share of the list / its match buffer: one wave per hit
                 multi_failed = true;
                 if (q.any && nr > 0) { ctx->any_found = true; continue; }
                 rerun = true;
                 continue;
             }
-            if (d.gen_multi_used) multi_ok = true;
+            if (run.gen_multi_used) multi_ok = true;
             // rows of the ordered search: with the window table every hit takes its window's matches, computed once
-            const uint64_t nrows = d.dedup_used && !q.fold && !q.any && nh <= FZ_GEN_ORDER_MAX ? cnt[FZ_HDR_GEN_ROWS] : nr;
+            const uint64_t nrows = run.dedup_used && !q.fold && !q.any && nh <= FZ_GEN_ORDER_MAX ? cnt[FZ_HDR_GEN_ROWS] : nr;
             if (q.any) {                                      // has_near_match_generic_ngrams: a record anywhere settles it
                 ctx->any_found |= nr > 0;
                 if (nr > 0) continue;
@@ -1946,10 +1945,10 @@ int run_generic(fz_ctx *ctx, fz_seq *seq, const Search &q, std::vector<FzGenRec>
             }
             if (nh > d.hit_cap) { int rc = ensure_hits(d, nh + nh / 8 + 1024); if (rc) return rc; rerun = true; }
             if (nr > d.big_cap) { int rc = ensure_big(d, nr + nr / 8 + 1024); if (rc) return rc; }
-            if (d.fold_was_direct) {                          // pairs beyond the staging buffer were dropped: again, through d_out
+            if (run.fold_was_direct) {                        // pairs beyond the staging buffer were dropped: again, through d_out
                 if (nr > kHostRecs) { d.fold_direct = false; rerun = true; }
             } else if (q.fold && nr * 4 < kHostRecs) d.fold_direct = true;
-            if (!d.fold_was_direct && std::max(nr, nrows) > d.rec_cap) { int rc = ensure_recs(d, std::max(nr, nrows) + nrows / 8 + 1024); if (rc) return rc; rerun = true; }
+            if (!run.fold_was_direct && std::max(nr, nrows) > d.rec_cap) { int rc = ensure_recs(d, std::max(nr, nrows) + nrows / 8 + 1024); if (rc) return rc; rerun = true; }
             const bool rows_ready = !q.fold && seq->shards.size() == 1 && sh.geom.seg_stride == 0 &&
                                     nh <= FZ_GEN_ORDER_MAX && nrows <= d.gen_rows_cap && !comm_multi_process(ctx);
             // Window table + device ordering: only the windows' LEADERS left automaton records, the members' rows exist on the
@@ -1958,17 +1957,17 @@ int run_generic(fz_ctx *ctx, fz_seq *seq, const Search &q, std::vector<FzGenRec>
             // the host-ordered fallback below would silently miss the members' rows — run again, the launch sizes the row buffer
             // by the record capacity (ensure_gen_rows).  Not reachable with today's capacity bookkeeping (rows <= rec_cap is
             // checked above); kept as the invariant's enforcement.
-            if (d.dedup_used && !q.fold && !q.any && !rows_ready && !rerun && nh <= FZ_GEN_ORDER_MAX && nrows > d.gen_rows_cap) {
+            if (run.dedup_used && !q.fold && !q.any && !rows_ready && !rerun && nh <= FZ_GEN_ORDER_MAX && nrows > d.gen_rows_cap) {
                 if (d.rec_cap < nrows) { int rc = ensure_recs(d, nrows + nrows / 8 + 1024); if (rc) return rc; }
                 rerun = true;
             }
-            const bool in_stage = q.fold && nr <= d.fold_copied && seq->shards.size() == 1;   // the pairs are in h_stage already
+            const bool in_stage = q.fold && nr <= run.fold_copied && seq->shards.size() == 1;   // the pairs are in h_stage already
             if (q.fold) d.fold_guess = std::max<uint64_t>(4096, nr + nr / 4 + 256);
             if (!rerun && !novf && nr && !rows_ready && !in_stage)
                 HIP_TRY(hipMemcpy(d.h_big, d.d_out + kHeaderBytes, nr * sizeof(FzGenRec), hipMemcpyDeviceToHost));
             if (novf) { lists_overflowed = true; rerun = true; }
             if (rerun) continue;
-            if (d.timed) ctx->tref.push_back({&d, d.ev[0], d.ev[1], d.ev[1], d.ev[d.lp_end_event], d.ev[0], d.ev[3]});
+            if (run.timed) ctx->tref.push_back(timing_ref(d, /*generic=*/true));
             ctx->stats.bytes_scanned += sh.geom.buf_len;
             ctx->stats.ngram_hits += nh;
             if (rows_ready) {                                 // finished rows, fetched by emit_generic
@@ -1976,7 +1975,7 @@ int run_generic(fz_ctx *ctx, fz_seq *seq, const Search &q, std::vector<FzGenRec>
                 ctx->gen_rows_n = nrows;
                 ctx->gen_rows_device = d.device;
             } else if (seq->shards.size() == 1) {             // read in place (valid until the next search)
-                ctx->gen_view = reinterpret_cast<const FzGenRec *>(in_stage ? d.h_stage + kHeaderBytes : d.h_big);
+                ctx->gen_view = reinterpret_cast<const FzGenRec *>(in_stage ? d.cur().h_stage + kHeaderBytes : d.h_big);
                 ctx->gen_view_n = nr;
             } else {
                 const size_t base = recs_out.size();
@@ -2311,8 +2310,8 @@ int emit_matches(fz_ctx *ctx, const std::vector<FzRec> &recs, uint32_t L, fz_mat
         return merge_rows(ptrs, ctx->seg_order, out, n);
     }
     // (the fused scan appends real records only; the stand-alone verifications may leave empty slots)
-    bool dense = true;                                     // (of the search being collected: its slot is the current one)
-    for (const DevState &d : ctx->devs) dense = dense && d.fused_used;
+    bool dense = true;
+    for (const DevState &d : ctx->devs) dense = dense && d.cur().run.fused_used;
     if (!ctx->view && ctx->seg_ends.size() > 1 && ctx->seg_ends.back() == recs.size())
         return emit_matches_segments(ctx, recs.data(), ctx->seg_ends, ctx->seg_order, L, out, n, idx_bound, blk_bound, !dense);
     return ctx->view ? emit_matches(ctx->view, (size_t)ctx->view_n, L, out, n, idx_bound, blk_bound, !dense)
@@ -2352,12 +2351,11 @@ static int devstate_init(DevState &d) {
     HIP_TRY(hipStreamCreateWithPriority(&d.stream_alt, hipStreamNonBlocking, prio_least));
     HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d.d_hdr_alt), kHeaderBytes));
     HIP_TRY(hipMemset(d.d_hdr_alt, 0, kHeaderBytes));
-    for (auto &ev : d.ev) HIP_TRY(hipEventCreate(&ev));
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&d.h_stage), kHeaderBytes + kHostRecs * sizeof(FzRec), hipHostMallocMapped));
-    HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&d.h_stage_dev), d.h_stage, 0));
-    for (auto &ev : d.other.ev) HIP_TRY(hipEventCreate(&ev));
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&d.other.h_stage), kHeaderBytes + kHostRecs * sizeof(FzRec), hipHostMallocMapped));
-    HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&d.other.h_stage_dev), d.other.h_stage, 0));
+    for (ResultSlot &s : d.slots) {
+        for (auto &ev : s.ev) HIP_TRY(hipEventCreate(&ev));
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s.h_stage), kHeaderBytes + kHostRecs * sizeof(FzRec), hipHostMallocMapped));
+        HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&s.h_stage_dev), s.h_stage, 0));
+    }
     int rc = ensure_hits(d, 1u << 20);
     if (rc == FZ_OK) rc = ensure_recs(d, 1u << 16);
     return rc;
@@ -2372,9 +2370,10 @@ static void devstate_destroy(DevState &d) {
     if (d.d_out) (void)hipFree(d.d_out);
     if (d.spare_alloc) (void)hipFree(d.spare_alloc);
     for (auto &ev : d.rec_ev) if (ev) (void)hipEventDestroy(ev);
-    if (d.h_stage) (void)hipHostFree(d.h_stage);
-    if (d.other.h_stage) (void)hipHostFree(d.other.h_stage);
-    for (auto &ev : d.other.ev) if (ev) (void)hipEventDestroy(ev);
+    for (ResultSlot &s : d.slots) {
+        if (s.h_stage) (void)hipHostFree(s.h_stage);
+        for (auto &ev : s.ev) if (ev) (void)hipEventDestroy(ev);
+    }
     if (d.h_big) (void)hipHostFree(d.h_big);
     if (d.d_cand) (void)hipFree(d.d_cand);
     if (d.d_pat) (void)hipFree(d.d_pat);
@@ -2384,7 +2383,6 @@ static void devstate_destroy(DevState &d) {
     if (d.d_gen_dedup) (void)hipFree(d.d_gen_dedup);
     for (int i = 0; i < 2; ++i) if (d.stream_h[i]) (void)hipHostFree(d.stream_h[i]);
     if (d.stream_d) (void)hipFree(d.stream_d);
-    for (auto &ev : d.ev) if (ev) (void)hipEventDestroy(ev);
     if (d.stream) (void)hipStreamDestroy(d.stream);
 }
 
@@ -4093,11 +4091,11 @@ static int mp_launch_shard(fz_ctx *ctx, const Shard &sh, uint32_t mode, const ui
         unsigned long long *dctr = reinterpret_cast<unsigned long long *>(d.d_mp_ctr);
         HIP_TRY(hipMemcpyAsync(d.d_mp_desc, desc, (size_t)desc_words * 4u, hipMemcpyHostToDevice, d.stream));
         HIP_TRY(hipMemsetAsync(d.d_mp_ctr, 0, FZ_MP_CTR_WORDS * 8u, d.stream));
-        if (ctx->timing) HIP_TRY(hipEventRecord(d.ev[0], d.stream));
+        if (ctx->timing) HIP_TRY(hipEventRecord(d.cur().ev[0], d.stream));
         hipLaunchKernelGGL(fk, dim3(grid), dim3(FZ_FILTER_THREADS), FZ_MP_FILTER_LDS, d.stream, sh.d_buf, a, ntiles, ddesc,
                            reinterpret_cast<uint64_t *>(d.d_mp_hits), dctr);
         HIP_TRY(hipGetLastError());
-        if (ctx->timing) HIP_TRY(hipEventRecord(d.ev[1], d.stream));
+        if (ctx->timing) HIP_TRY(hipEventRecord(d.cur().ev[1], d.stream));
         // (rag: the shard is a batch — the ragged instances look every candidate's sequence up in the geometry's tables)
         if (cls)
             hipLaunchKernelGGL(rag ? fz_mp_batch_verify_cls_kernel : fz_mp_verify_cls_kernel, dim3((uint32_t)d.n_cus * 4), dim3(FZ_FILTER_THREADS),
@@ -4112,14 +4110,14 @@ static int mp_launch_shard(fz_ctx *ctx, const Shard &sh, uint32_t mode, const ui
                                fz_mp_verify_lds(a.win_dwords), d.stream,
                                sh.d_buf, a, ddesc, reinterpret_cast<const uint64_t *>(d.d_mp_hits), reinterpret_cast<FzRec *>(d.d_mp_recs), dctr);
         HIP_TRY(hipGetLastError());
-        if (ctx->timing) HIP_TRY(hipEventRecord(d.ev[2], d.stream));
+        if (ctx->timing) HIP_TRY(hipEventRecord(d.cur().ev[2], d.stream));
         unsigned long long ctr[FZ_MP_CTR_WORDS];
         HIP_TRY(hipMemcpyAsync(ctr, d.d_mp_ctr, sizeof ctr, hipMemcpyDeviceToHost, d.stream));
         HIP_TRY(hipStreamSynchronize(d.stream));
         ++tot.launches;
         if (ctx->timing) {
-            tot.filter_ms += span_ms(d.ev[0], d.ev[1]);
-            tot.verify_ms += span_ms(d.ev[1], d.ev[2]);
+            tot.filter_ms += span_ms(d.cur().ev[0], d.cur().ev[1]);
+            tot.verify_ms += span_ms(d.cur().ev[1], d.cur().ev[2]);
         }
         uint64_t need_hits = 0;
         for (uint32_t l = 0; l < FZ_MP_LISTS; ++l) need_hits = std::max<uint64_t>(need_hits, ctr[FZ_MP_CTR_LIST(l)]);
@@ -4745,10 +4743,10 @@ static uint32_t assign_grid(const DevState &d, uint64_t items) {
 
 // launch() between ev[2] and ev[3] of a context that times its kernels; once ev[3] is complete the span goes to fold_ms.
 static int assign_launch(fz_ctx *ctx, DevState &d, const std::function<void()> &launch) {
-    if (ctx->timing) HIP_TRY(hipEventRecord(d.ev[2], d.stream));
+    if (ctx->timing) HIP_TRY(hipEventRecord(d.cur().ev[2], d.stream));
     launch();
     HIP_TRY(hipGetLastError());
-    if (ctx->timing) HIP_TRY(hipEventRecord(d.ev[3], d.stream));
+    if (ctx->timing) HIP_TRY(hipEventRecord(d.cur().ev[3], d.stream));
     return FZ_OK;
 }
 
@@ -4762,8 +4760,8 @@ static int assign_fold_device(fz_ctx *ctx, AssignCall &ac, const FzRec *d_recs, 
     });
     if (rc) return rc;
     if (ctx->timing) {
-        HIP_TRY(hipEventSynchronize(d.ev[3]));
-        ac.fold_ms += span_ms(d.ev[2], d.ev[3]);
+        HIP_TRY(hipEventSynchronize(d.cur().ev[3]));
+        ac.fold_ms += span_ms(d.cur().ev[2], d.cur().ev[3]);
     }
     return FZ_OK;
 }
@@ -5011,7 +5009,7 @@ static int batch_assign_impl(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const ui
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(rows, ac.d_rows, (size_t)n_seqs * sizeof(fz_assign), hipMemcpyDeviceToHost, d.stream));
     HIP_TRY(hipStreamSynchronize(d.stream));
-    if (ctx->timing) ac.fold_ms += span_ms(d.ev[2], d.ev[3]);
+    if (ctx->timing) ac.fold_ms += span_ms(d.cur().ev[2], d.cur().ev[3]);
     guard.p = nullptr;
     *out = rows;
     mp_publish(ctx, tot, ac.folded, form, ac.fold_ms);
@@ -5157,7 +5155,7 @@ int fz_batch_end_overlaps(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8
     MpTotals tot;
     const uint32_t chunk = fz_overlap_chunk(mode);
     const uint32_t grid = (uint32_t)std::min<uint64_t>((n_seqs + FZ_FILTER_THREADS - 1) / FZ_FILTER_THREADS, (uint64_t)d.n_cus * 8);
-    if (ctx->timing) HIP_TRY(hipEventRecord(d.ev[2], d.stream));
+    if (ctx->timing) HIP_TRY(hipEventRecord(d.cur().ev[2], d.stream));
     for (uint32_t p0 = 0; p0 < n_pats; p0 += chunk) {
         a.p0 = p0;
         a.npat = std::min(chunk, n_pats - p0);
@@ -5173,13 +5171,13 @@ int fz_batch_end_overlaps(fz_ctx *ctx, fz_seq *batch, uint32_t mode, const uint8
     }
     hipLaunchKernelGGL(fz_overlap_finish_kernel, dim3(assign_grid(d, n_seqs)), dim3(FZ_ASSIGN_THREADS), 0, d.stream, d_table, a.rag.ends, n_seqs, d_rows);
     HIP_TRY(hipGetLastError());
-    if (ctx->timing) HIP_TRY(hipEventRecord(d.ev[3], d.stream));
+    if (ctx->timing) HIP_TRY(hipEventRecord(d.cur().ev[3], d.stream));
     HIP_TRY(hipStreamSynchronize(d.stream));
     const auto t_d2h = std::chrono::steady_clock::now();
     HIP_TRY(hipMemcpyAsync(res, d_rows, (size_t)n_seqs * sizeof(fz_overlap), hipMemcpyDeviceToHost, d.stream));
     HIP_TRY(hipStreamSynchronize(d.stream));
     ctx->ovl_ms[2] = since(t_d2h);
-    if (ctx->timing) ctx->ovl_ms[1] = span_ms(d.ev[2], d.ev[3]);
+    if (ctx->timing) ctx->ovl_ms[1] = span_ms(d.cur().ev[2], d.cur().ev[3]);
     tot.bytes = sh.geom.buf_len;
     guard.p = nullptr;
     *out = res;
@@ -5370,7 +5368,7 @@ namespace {
 int comm_setup_dev(DevState &d) {
     HIP_TRY(hipSetDevice(d.device));
     if (!d.comm_stream) HIP_TRY(hipStreamCreateWithFlags(&d.comm_stream, hipStreamNonBlocking));
-    for (auto &ev : d.ev_snap) if (!ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    for (ResultSlot &s : d.slots) if (!s.ev_snap) HIP_TRY(hipEventCreateWithFlags(&s.ev_snap, hipEventDisableTiming));
     if (!d.ev_done) HIP_TRY(hipEventCreateWithFlags(&d.ev_done, hipEventDisableTiming));
     return ensure_send(d, d.rec_cap);
 }
@@ -5381,9 +5379,8 @@ void comm_teardown(fz_ctx *ctx) {
         // the communicator, its streams and buffers are left behind (the process is about to report the failure)
         for (DevState &d : ctx->devs) {
             d.comm = nullptr; d.comm_stream = nullptr; d.d_recv = nullptr; d.h_recv = nullptr; d.recv_bytes = 0; d.send_cap = 0;
-            for (auto &b : d.d_send) b = nullptr;
-            for (auto &ev : d.ev_snap) ev = nullptr;
-            d.ev_done = nullptr; d.comm_rank = -1; d.snap_taken[0] = d.snap_taken[1] = false;
+            for (ResultSlot &s : d.slots) { s.d_send = nullptr; s.ev_snap = nullptr; s.snap_taken = false; }
+            d.ev_done = nullptr; d.comm_rank = -1;
         }
         ctx->comm_world = 0; ctx->snapshot = false; ctx->comm_broken = false;
         return;
@@ -5392,16 +5389,18 @@ void comm_teardown(fz_ctx *ctx) {
         (void)hipSetDevice(d.device);
         if (d.comm_stream) (void)hipStreamSynchronize(d.comm_stream);
         if (d.comm) { if (rccl_api()->ok) (void)rccl_api()->CommDestroy(d.comm); d.comm = nullptr; }
-        for (auto &b : d.d_send) if (b) { (void)hipFree(b); b = nullptr; }
+        for (ResultSlot &s : d.slots) {
+            if (s.d_send) { (void)hipFree(s.d_send); s.d_send = nullptr; }
+            if (s.ev_snap) { (void)hipEventDestroy(s.ev_snap); s.ev_snap = nullptr; }
+            s.snap_taken = false;
+        }
         d.send_cap = 0;
         if (d.d_recv) { (void)hipFree(d.d_recv); d.d_recv = nullptr; }
         if (d.h_recv) { (void)hipHostFree(d.h_recv); d.h_recv = nullptr; }
         d.recv_bytes = 0;
-        for (auto &ev : d.ev_snap) if (ev) { (void)hipEventDestroy(ev); ev = nullptr; }
         if (d.ev_done) { (void)hipEventDestroy(d.ev_done); d.ev_done = nullptr; }
         if (d.comm_stream) { (void)hipStreamDestroy(d.comm_stream); d.comm_stream = nullptr; }
         d.comm_rank = -1;
-        d.snap_taken[0] = d.snap_taken[1] = false;
     }
     ctx->comm_world = 0;
     ctx->snapshot = false;
@@ -5743,7 +5742,7 @@ int run_lp(fz_ctx *ctx, fz_seq *seq, const Search &q, uint32_t lp_kind, std::vec
             FzGenRec *recs = reinterpret_cast<FzGenRec *>(d.d_out + kHeaderBytes);
             HIP_TRY(hipMemsetAsync(d.d_out, 0, kHeaderBytes, d.stream));
             d.header_zeroed = false;
-            HIP_TRY(hipEventRecord(d.ev[0], d.stream));
+            HIP_TRY(hipEventRecord(d.cur().ev[0], d.stream));
             FzScanArgs fa;
             memset(&fa, 0, sizeof fa);
             fa.geom = sh.geom;
@@ -5767,29 +5766,29 @@ int run_lp(fz_ctx *ctx, fz_seq *seq, const Search &q, uint32_t lp_kind, std::vec
                                    nwin, recs, counters);
                 HIP_TRY(hipGetLastError());
             }
-            HIP_TRY(hipEventRecord(d.ev[1], d.stream));
-            HIP_TRY(hipMemcpyAsync(d.h_stage, d.d_out, kHeaderBytes + kFirstCopyRecs * sizeof(FzRec),
+            HIP_TRY(hipEventRecord(d.cur().ev[1], d.stream));
+            HIP_TRY(hipMemcpyAsync(d.cur().h_stage, d.d_out, kHeaderBytes + kFirstCopyRecs * sizeof(FzRec),
                                    hipMemcpyDeviceToHost, d.stream));
-            HIP_TRY(hipEventRecord(d.ev[3], d.stream));
+            HIP_TRY(hipEventRecord(d.cur().ev[3], d.stream));
         }
         for (const Shard &sh : seq->shards) {
             DevState &d = ctx->devs[sh.dev];
             HIP_TRY(hipSetDevice(d.device));
             HIP_TRY(hipStreamSynchronize(d.stream));
-            const unsigned long long *cnt = reinterpret_cast<const unsigned long long *>(d.h_stage);
+            const unsigned long long *cnt = reinterpret_cast<const unsigned long long *>(d.cur().h_stage);
             const uint64_t nr = cnt[1], novf = cnt[2];
             if (nr > d.rec_cap) { int rc = ensure_recs(d, nr + nr / 8 + 1024); if (rc) return rc; rerun = true; }
             if (novf) { cand_cap *= 4; rerun = true; }
             if (rerun) continue;
             float f = 0, t = 0;
-            HIP_TRY(hipEventElapsedTime(&f, d.ev[0], d.ev[1]));
-            HIP_TRY(hipEventElapsedTime(&t, d.ev[0], d.ev[3]));
+            HIP_TRY(hipEventElapsedTime(&f, d.cur().ev[0], d.cur().ev[1]));
+            HIP_TRY(hipEventElapsedTime(&t, d.cur().ev[0], d.cur().ev[3]));
             ctx->stats.verify_ms = std::max<double>(ctx->stats.verify_ms, f);
             ctx->stats.device_ms = std::max<double>(ctx->stats.device_ms, t);
             ctx->stats.bytes_scanned += sh.geom.buf_len;
             std::vector<FzGenRec> tmp(nr);
             const uint64_t first = std::min<uint64_t>(nr, kFirstCopyRecs);
-            if (first) memcpy(tmp.data(), d.h_stage + kHeaderBytes, first * sizeof(FzGenRec));
+            if (first) memcpy(tmp.data(), d.cur().h_stage + kHeaderBytes, first * sizeof(FzGenRec));
             if (nr > first)
                 HIP_TRY(hipMemcpy(tmp.data() + first, d.d_out + kHeaderBytes + first * sizeof(FzGenRec),
                                   (nr - first) * sizeof(FzGenRec), hipMemcpyDeviceToHost));
@@ -5934,21 +5933,21 @@ static int subs_lp_impl(fz_ctx *ctx, fz_seq *seq, const uint8_t *p, uint32_t m, 
             const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((own + 255) / 256, (uint64_t)d.n_cus * 16));
             hipLaunchKernelGGL(fz_hamming_kernel, dim3(grid), dim3(256), 0, d.stream, sh.d_buf, fa, drecs, counters);
             HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(d.h_stage, d.d_out, kHeaderBytes + kFirstCopyRecs * sizeof(FzRec),
+            HIP_TRY(hipMemcpyAsync(d.cur().h_stage, d.d_out, kHeaderBytes + kFirstCopyRecs * sizeof(FzRec),
                                    hipMemcpyDeviceToHost, d.stream));
         }
         for (const Shard &sh : seq->shards) {
             DevState &d = ctx->devs[sh.dev];
             HIP_TRY(hipSetDevice(d.device));
             HIP_TRY(hipStreamSynchronize(d.stream));
-            const unsigned long long *cnt = reinterpret_cast<const unsigned long long *>(d.h_stage);
+            const unsigned long long *cnt = reinterpret_cast<const unsigned long long *>(d.cur().h_stage);
             const uint64_t nr = cnt[1];
             if (found) { if (nr) *found = 1; continue; }
             if (nr > d.rec_cap) { rc = ensure_recs(d, nr + nr / 8 + 1024); if (rc) return rc; rerun = true; continue; }
             const size_t base = recs.size();
             recs.resize(base + nr);
             const uint64_t first = std::min<uint64_t>(nr, kFirstCopyRecs);
-            if (first) memcpy(recs.data() + base, d.h_stage + kHeaderBytes, first * sizeof(FzRec));
+            if (first) memcpy(recs.data() + base, d.cur().h_stage + kHeaderBytes, first * sizeof(FzRec));
             if (nr > first)
                 HIP_TRY(hipMemcpy(recs.data() + base + first, d.d_out + kHeaderBytes + first * sizeof(FzRec),
                                   (nr - first) * sizeof(FzRec), hipMemcpyDeviceToHost));

@@ -835,3 +835,51 @@ def test_two_searches_in_flight_for_every_kind(engine):
     assert np.array_equal(engine.search_end(as_array=True), want)
     h2.release()
     h.release()
+
+
+def test_fused_and_kernel_verified_searches_in_the_two_slots(engine):
+    """A fused search and one verified by a stand-alone kernel in flight together, in either order and in either result
+    slot: what a search ran with (fused or not: empty record slots; which events it recorded) is read from its own slot.
+    A: Levenshtein k = 2, the lean fused band.  C: substitutions-only, the fused Hamming count.  B: m = 160, k = 16 —
+    no fused form takes it (pattern beyond 128 characters, 33 band cells beyond the 32-lane group): scan, hit list,
+    fz_verify_wf_kernel<64>."""
+    from fuzzysearch_amd import _native
+    seq = workloads.dna(1 << 20, 41)
+    pa, pb = workloads.dna(20, 1), workloads.dna(160, 2)
+    workloads.plant_variants(seq, pa, 32, 7)
+    workloads.plant_variants(seq, pb, 32, 8)
+    t, a, b = seq.tobytes(), pa.tobytes(), pb.tobytes()
+    oracle_rows = {"A": oracle.lev_ngrams_raw(a, t, 2), "B": oracle.lev_ngrams_raw(b, t, 16), "C": oracle.subs_ngrams_raw(a, t, 2)}
+    assert all(len(rows) > 0 for rows in oracle_rows.values())
+
+    def drive(eng):
+        h = eng.upload(t)
+        begin = {"A": lambda: eng.lev_ngrams_begin(h, a, 2), "B": lambda: eng.lev_ngrams_begin(h, b, 16),
+                 "C": lambda: eng.subs_ngrams_begin(h, a, 2)}
+        assert eng.lev_ngrams(h, a, 2) == oracle_rows["A"]
+        assert eng.stats()["verify_form"] == _native.FORM_FUSED_BAND
+        assert eng.lev_ngrams(h, b, 16) == oracle_rows["B"]
+        assert eng.stats()["verify_form"] == _native.FORM_KERNEL
+        assert eng.subs_ngrams(h, a, 2) == oracle_rows["C"]
+        want = {"A": eng.lev_ngrams(h, a, 2, as_array=True), "B": eng.lev_ngrams(h, b, 16, as_array=True),
+                "C": eng.subs_ngrams(h, a, 2, as_array=True)}
+        for rep in range(2):                                   # (after an odd number of swaps the younger slot is the current one)
+            inflight = []
+            for step in ["A", "B", None, "C", None, "B", None, "A", None, None]:
+                if step:
+                    begin[step]()
+                    inflight.append(step)
+                else:
+                    which = inflight.pop(0)
+                    assert np.array_equal(eng.search_end(as_array=True), want[which]), (rep, which)
+            assert not inflight
+        assert np.array_equal(eng.lev_ngrams(h, b, 16, as_array=True), want["B"])
+        h.release()
+
+    drive(engine)
+    eng = _native.Engine([0])
+    try:
+        eng.set_streams(1)
+        drive(eng)
+    finally:
+        eng.close()
