@@ -33,6 +33,7 @@ from .batch import find_near_matches_batch, resident_batch
 from .multi_batch import find_near_matches_multi_batch
 from .assign import find_best_matches_batch, BestMatches
 from .overlap import find_end_overlaps_batch, EndOverlaps
+from .cuts import find_score_cuts_batch, quality_cuts, poly_tail_cuts, ScoreCuts
 from .records import resident_records, RecordBatch
 from .fasta import resident_fasta, FastaBatch
 from .classes import IUPAC_DNA
@@ -51,6 +52,10 @@ __all__ = [
     'BestMatches',
     'find_end_overlaps_batch',
     'EndOverlaps',
+    'find_score_cuts_batch',
+    'quality_cuts',
+    'poly_tail_cuts',
+    'ScoreCuts',
     'IUPAC_DNA',
     'Match',
     'resident',

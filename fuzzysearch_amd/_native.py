@@ -113,6 +113,9 @@ PROTOTYPES = {
     "fz_batch_end_overlaps": (ci, (vp, vp, u32, bp, u64p, u32, u32, u32, vpp)),
     "fz_debug_end_overlaps": (ci, (u32, bp, u64p, u32, u32, u32, bp, vp, u64, vp)),
     "fz_debug_overlap_ms": (ci, (vp, f64p)),
+    "fz_batch_score_cuts": (ci, (vp, vp, vp, vp, u32, u32, u32, vpp)),
+    "fz_debug_score_cuts": (ci, (vp, vp, u32, u32, u32, bp, vp, u64, vp)),
+    "fz_debug_cuts_ms": (ci, (vp, f64p)),
     "fz_subs_ngrams_multi_cls": _MULTI_CLS,
     "fz_subs_ngrams_multi_best_cls": _MULTI_CLS,
     "fz_batch_search_multi_cls": (ci, (vp, vp, bp, u64p, u32, u32, bp, bp, ci, mpp, u32pp, u64pp)),
@@ -189,6 +192,7 @@ EXPORTED_SYMBOLS = tuple(PROTOTYPES)
 OPTIONAL = frozenset((
     "fz_batch_search_multi", "fz_batch_assign", "fz_debug_assign_fold",
     "fz_batch_end_overlaps", "fz_debug_end_overlaps", "fz_debug_overlap_ms",
+    "fz_batch_score_cuts", "fz_debug_score_cuts", "fz_debug_cuts_ms",
     "fz_subs_ngrams_multi_cls", "fz_subs_ngrams_multi_best_cls", "fz_batch_search_multi_cls", "fz_batch_assign_cls",
     "fz_debug_multi_plan_cls",
     "fz_batch_upload_records", "fz_batch_tables", "fz_debug_batch_bytes", "fz_debug_records_split", "fz_debug_scan_items",
@@ -702,6 +706,45 @@ def end_overlaps_twin(mode, patterns, k, min_overlap, blob, offs):
     return out
 
 
+CUT_STOP3, CUT_STOP5, CUT_RATE = 1, 2, 4          # fz_batch_score_cuts' flags (include/fzhip.h: FZ_CUT_*)
+_CUT_DTYPE = None
+
+
+def cut_dtype():
+    """The numpy dtype of an fz_cut row (include/fzhip.h): start, end."""
+    global _CUT_DTYPE
+    if _CUT_DTYPE is None:
+        import numpy as np
+        _CUT_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4")])
+    return _CUT_DTYPE
+
+
+def _cut_table(w):
+    """A table of 256 scores, or None -> (a contiguous int16 array that stays alive over the call or None, its address or None)"""
+    if w is None:
+        return None, None
+    import numpy as np
+    w = np.ascontiguousarray(w, dtype=np.int16)
+    if w.shape != (256,):
+        raise ValueError("a score table has 256 entries")
+    return w, w.ctypes.data
+
+
+def score_cuts_twin(w3, w5, flags, rate_num, rate_den, blob, offs):
+    """fz_debug_score_cuts (no device): fz_batch_score_cuts on the host, through the functions its kernel's lanes run and with
+    its refusals.  w3 / w5: 256 int16 scores or None; blob: the packed sequences; offs: their n_seqs + 1 offsets -> fz_cut
+    structured array of n_seqs rows."""
+    import numpy as np
+    lib = load_library()
+    w3, a3 = _cut_table(w3)
+    w5, a5 = _cut_table(w5)
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    blob = bytes(blob)
+    out = np.empty(len(offs) - 1, dtype=cut_dtype())
+    _check(_entry(lib, 'fz_debug_score_cuts')(a3, a5, flags, rate_num, rate_den, blob, offs[1:].ctypes.data, len(offs) - 1, out.ctypes.data))
+    return out
+
+
 class OwnedRows(object):
     """A C-ABI result buffer (fz_match rows) that has not been copied anywhere: address, n, and fz_free on release."""
     __slots__ = ('_lib', '_ptr', 'n')
@@ -1106,6 +1149,25 @@ class Engine(object):
         ms = (ctypes.c_double * 4)()
         with self._lock:
             _check(_entry(self._lib, 'fz_debug_overlap_ms')(self._h, ms))
+        return {'tables_h2d': ms[0], 'kernels': ms[1], 'rows_d2h': ms[2], 'call': ms[3]}
+
+    def batch_score_cuts(self, batch, w3, w5, flags, rate_num=0, rate_den=1):
+        """fz_batch_score_cuts: per sequence of the batch where the running sum of the 3' table w3 and / or the 5' table w5 (256
+        int16 scores each, or None) peaks -> a structured array (cut_dtype) of one row per sequence over the library's buffer:
+        start, end.  flags: CUT_STOP3 | CUT_STOP5 | CUT_RATE."""
+        w3, a3 = _cut_table(w3)
+        w5, a5 = _cut_table(w5)
+        fn = _entry(self._lib, "fz_batch_score_cuts")
+        ptr = ctypes.c_void_p()
+        with self._lock:
+            _check(fn(self._h, batch._h, a3, a5, flags, rate_num, rate_den, ctypes.byref(ptr)))
+        return _take_rows(self._lib, ptr.value, batch.n_seqs, cut_dtype())
+
+    def cuts_ms(self):
+        """fz_debug_cuts_ms: {tables_h2d, kernels, rows_d2h, call} milliseconds of this engine's last batch_score_cuts."""
+        ms = (ctypes.c_double * 4)()
+        with self._lock:
+            _check(_entry(self._lib, 'fz_debug_cuts_ms')(self._h, ms))
         return {'tables_h2d': ms[0], 'kernels': ms[1], 'rows_d2h': ms[2], 'call': ms[3]}
 
     # the class calls by their names of old: substitutions mode, tables = (pmask, tmask) of classes.class_tables

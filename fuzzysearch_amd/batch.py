@@ -122,6 +122,10 @@ class BatchSequences(object):
         from .derive import derive_batch
         return derive_batch(self, index, starts, ends, reverse, translate)
 
+    def score_cuts(self, scores=None, scores_5p=None, stop=True, max_miss_rate=None):
+        """find_score_cuts_batch(self, ...): the cut positions of these sequences by a running sum of scores (cuts.py)."""
+        from .cuts import find_score_cuts_batch
+        return find_score_cuts_batch(self, scores, scores_5p, stop, max_miss_rate)
 
     def format(self, format=None, literals=None, out=None):
         """format_records(self, ...): the text of this one column, assembled on the device (egress.py); no format and no

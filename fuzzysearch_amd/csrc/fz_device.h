@@ -1887,17 +1887,20 @@ FZ_HD void fz_bits_column_search(FzBitsCol<1> &c, uint64_t eq, uint64_t hm) {
 // in front of buf_len, so a load ends inside the padding behind the data at the latest.  The up to 3 bytes in front of the
 // tail and behind the read's end belong to a neighbour or to the padding: the accessors below never hand them out.
 struct FzOvlStage { uint64_t wbase; uint32_t sh, ts, nd; };
-FZ_HD FzOvlStage fz_overlap_stage(uint64_t sa, uint64_t se, uint32_t tmax, uint64_t buf_len) {
+// ... of any run of bytes [wlo, whi) of the buffer (fz_cuts_piece stages a read piece by piece through it)
+FZ_HD FzOvlStage fz_stage_range(uint64_t wlo, uint64_t whi, uint64_t buf_len) {
     FzOvlStage s;
-    const uint64_t n = se - sa;
-    s.ts = n < tmax ? (uint32_t)n : tmax;
-    const uint64_t wlo = se - s.ts;
+    s.ts = (uint32_t)(whi - wlo);
     s.wbase = wlo & ~(uint64_t)3;
     s.sh = (uint32_t)(wlo - s.wbase);
-    s.nd = s.ts ? (uint32_t)((se - s.wbase + 3u) >> 2) : 0u;
+    s.nd = s.ts ? (uint32_t)((whi - s.wbase + 3u) >> 2) : 0u;
     const uint64_t resident = buf_len > s.wbase ? (buf_len - s.wbase + 3u) >> 2 : 0u;
     if (s.nd > resident) s.nd = (uint32_t)resident;
     return s;
+}
+FZ_HD FzOvlStage fz_overlap_stage(uint64_t sa, uint64_t se, uint32_t tmax, uint64_t buf_len) {
+    const uint64_t n = se - sa;
+    return fz_stage_range(se - (n < tmax ? n : tmax), se, buf_len);
 }
 FZ_HD uint32_t fz_overlap_load_dword(const uint8_t *buf, uint64_t off) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -1909,13 +1912,20 @@ FZ_HD uint32_t fz_overlap_load_dword(const uint8_t *buf, uint64_t off) {
 #endif
 }
 // The window of one lane: dword d at win[d * stride] (the lane-transposed layout of the verification kernels: stride 64).
-FZ_HD void fz_overlap_stage_copy(const uint8_t *buf, const FzOvlStage &s, uint32_t win_dwords, uint32_t *win, uint32_t stride) {
-    for (uint32_t d0 = 0; d0 < win_dwords; d0 += 4u) {     // (four loads in flight, then their stores)
+// FILL: the dwords of the window behind the staged ones are zeroed; without it only the nd staged dwords are written, and a
+// lane with nothing to stage (nd = 0) touches neither the buffer nor the window.
+template <bool FILL>
+FZ_HD void fz_stage_copy(const uint8_t *buf, const FzOvlStage &s, uint32_t win_dwords, uint32_t *win, uint32_t stride) {
+    const uint32_t nw = FILL || win_dwords < s.nd ? win_dwords : s.nd;
+    for (uint32_t d0 = 0; d0 < nw; d0 += 4u) {             // (four loads in flight, then their stores)
         uint32_t x[4];
         for (uint32_t j = 0; j < 4u; ++j) x[j] = d0 + j < s.nd ? fz_overlap_load_dword(buf, s.wbase + 4u * (d0 + j)) : 0u;
         for (uint32_t j = 0; j < 4u; ++j)
-            if (d0 + j < win_dwords) win[(d0 + j) * stride] = x[j];
+            if (d0 + j < nw) win[(d0 + j) * stride] = x[j];
     }
+}
+FZ_HD void fz_overlap_stage_copy(const uint8_t *buf, const FzOvlStage &s, uint32_t win_dwords, uint32_t *win, uint32_t stride) {
+    fz_stage_copy<true>(buf, s, win_dwords, win, stride);
 }
 struct FzOvlWindow {
     const uint32_t *win;
@@ -2010,4 +2020,107 @@ FZ_HD uint64_t fz_overlap_lane(const FzOvlTabs &tb, const uint32_t *win, uint32_
         if (key > best) best = key;
     }
     return best;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Score cuts (fz_batch_score_cuts; fz_kernels.h: fz_cuts_kernel): where the running sum of a table of scores, taken from a
+// read's end, peaks.  Per read r of n bytes, a table w of 256 signed scores, a flag `stop` and an optional miss rate
+// num / den (a miss: a byte with w < 0):
+//   cut3(r):  s = best = miss = 0; cut = n
+//             for i = n - 1 down to 0:  s += w[r[i]]; miss += w[r[i]] < 0
+//                                       if stop and s < 0: break
+//                                       if s > best and (no rate or miss * den <= num * (n - i)): best = s; cut = i
+//   cut5(r) = n - cut3(reversed r)
+// (strict: of equal peaks the one nearest the end wins).  Quality trimming at cutoff q is w[b] = q - (b - base) with stop,
+// poly-A trimming w['A'] = 1, -2 elsewhere, no stop, rate 1 / 5.  A lane keeps the number of bytes it has walked from its
+// end (3') or its start (5') and `trim` = that number at the peak, so one text serves both sides: cut3 = n - trim, cut5 =
+// trim.  The sums are 32-bit: the call refuses batches with max_seq_len * max|w| >= 2^31.
+#ifndef FZ_CUT_STOP3                   // (include/fzhip.h states the same three)
+#define FZ_CUT_STOP3 1u                // fz_batch_score_cuts' flags: the 3' side stops at the first negative sum
+#define FZ_CUT_STOP5 2u                // ... the 5' side
+#define FZ_CUT_RATE 4u                 // the miss rate is in force on the sides that do not stop
+#endif
+#define FZ_CUT_PIECE_DWORDS 16u        // a read is walked in pieces of 16 dwords of the buffer: 4 KiB of window per wave
+
+struct FzCutRow { uint32_t start, end; };                  // = fz_cut
+// One side's rule.  wmax = the table's largest score; bounded: a lane also ends where no later sum can pass its peak.
+struct FzCutRule { int32_t wmax; uint32_t stop, rate, num, den, bounded; };
+struct FzCutState { int32_t s, best; uint32_t trim, miss, walked, live; };
+
+FZ_HD FzCutRule fz_cuts_rule(uint32_t side, uint32_t flags, uint32_t num, uint32_t den, int32_t wmax, uint32_t bounded) {
+    FzCutRule r;
+    r.wmax = wmax;
+    r.stop = (flags >> side) & 1u;
+    r.rate = (flags & FZ_CUT_RATE) && !r.stop ? 1u : 0u;
+    r.num = num; r.den = den; r.bounded = bounded;
+    return r;
+}
+// A lane is finished when its read is used up, when `stop` fired (fz_cuts_step), or when s + remaining * wmax <= best: every
+// later sum is at most that, and only a sum ABOVE best moves the cut, so the test is exact.  (remaining * wmax < 2^31 by the
+// call's refusal, and |s| <= walked * max|w|: the 32-bit sum cannot wrap.)
+FZ_HD void fz_cuts_check(FzCutState &c, uint32_t n, const FzCutRule &r) {
+    const bool done = c.walked >= n || (r.bounded && c.s + (int32_t)(n - c.walked) * r.wmax <= c.best);
+    c.live = done ? 0u : c.live;
+}
+FZ_HD FzCutState fz_cuts_begin(uint32_t n, const FzCutRule &r) {
+    FzCutState c;
+    c.s = c.best = 0; c.trim = c.miss = c.walked = 0u; c.live = 1u;
+    fz_cuts_check(c, n, r);
+    return c;
+}
+// One byte's score into a lane that is live and `on` (the byte is the piece's own); every field moves by a select, so the
+// state stays in registers whatever is inlined around it.
+FZ_HD void fz_cuts_step(FzCutState &c, int32_t wv, const FzCutRule &r, bool on) {
+    const bool go = on && c.live;
+    c.s += go ? wv : 0;
+    c.miss += go && wv < 0 ? 1u : 0u;
+    c.walked += go ? 1u : 0u;
+    const bool dead = go && r.stop && c.s < 0;
+    bool within = true;
+    if (r.rate) within = (uint64_t)c.miss * r.den <= (uint64_t)r.num * c.walked;   // (uniform)
+    const bool take = go && !dead && c.s > c.best && within;
+    c.best = take ? c.s : c.best;
+    c.trim = take ? c.walked : c.trim;
+    c.live = dead ? 0u : c.live;
+}
+// The next piece of the read [sa, se) for a lane that has walked c.walked bytes from its end (dir 0) or its start (dir 1):
+// the bytes up to the next multiple of FZ_CUT_PIECE_DWORDS dwords of the BUFFER, so that every piece but the first fills its
+// window whole and none needs more than FZ_CUT_PIECE_DWORDS dwords at any alignment.  A finished lane: the empty piece, nd = 0.
+FZ_HD FzOvlStage fz_cuts_piece(const FzCutState &c, uint64_t sa, uint64_t se, uint32_t dir, uint64_t buf_len) {
+    const uint64_t span = 4u * FZ_CUT_PIECE_DWORDS;
+    uint64_t lo = sa, hi = sa;
+    if (c.live && dir) {
+        lo = sa + c.walked;
+        hi = (lo & ~(uint64_t)3) + span;
+        if (hi > se) hi = se;
+    } else if (c.live) {
+        hi = se - c.walked;
+        const uint64_t top = ((hi - 1u) & ~(uint64_t)3) + 4u;   // (live: walked < n, so hi > sa >= 0)
+        lo = top > span ? top - span : 0u;
+        if (lo < sa) lo = sa;
+    }
+    return fz_stage_range(lo, hi, buf_len);
+}
+// One staged piece through one lane: its bytes in the order of the walk, a dword of the window at a time.  Only window bytes
+// [sh, sh + ts) are scored: what else the dwords hold is a neighbour's, the padding's, or this read's outside the piece.
+FZ_HD void fz_cuts_lane(FzCutState &c, const int16_t *w, const uint32_t *win, uint32_t stride, const FzOvlStage &st, uint32_t n,
+                        uint32_t dir, const FzCutRule &r) {
+    const uint32_t lo = st.sh, hi = st.sh + st.ts;
+    for (uint32_t u = 0; u < st.nd && c.live; ++u) {
+        const uint32_t d = dir ? u : st.nd - 1u - u;
+        const uint32_t x = win[d * stride];
+        for (uint32_t v = 0; v < 4u; ++v) {
+            const uint32_t b = dir ? v : 3u - v, o = 4u * d + b;
+            fz_cuts_step(c, (int32_t)w[(x >> (8u * b)) & 0xffu], r, o >= lo && o < hi);
+        }
+        fz_cuts_check(c, n, r);
+    }
+}
+// sides: bit 0 the 3' side was asked for, bit 1 the 5' side.  Both asked for and nothing left between them: the empty read.
+FZ_HD FzCutRow fz_cuts_row(uint32_t n, uint32_t trim3, uint32_t trim5, uint32_t sides) {
+    FzCutRow row;
+    row.start = (sides & 2u) ? trim5 : 0u;
+    row.end = (sides & 1u) ? n - trim3 : n;
+    if (sides == 3u && row.start >= row.end) row.start = row.end = 0u;
+    return row;
 }

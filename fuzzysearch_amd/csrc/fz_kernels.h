@@ -2979,3 +2979,61 @@ __global__ __launch_bounds__(FZ_ASSIGN_THREADS) void fz_overlap_finish_kernel(co
     for (uint64_t j = (uint64_t)blockIdx.x * FZ_ASSIGN_THREADS + threadIdx.x; j < n_seqs; j += stride)
         out[j] = fz_overlap_row(table[j], (uint32_t)(ends[j] - (j ? ends[j - 1u] : 0ull)));
 }
+
+// ---------------------------------------------------------------------------------------------
+// Score cuts (fz_batch_score_cuts; fz_device.h: fz_cuts_*): per read where the running sum of a score table, taken from its
+// 3' end and / or its 5' end, peaks — quality trimming and poly-A trimming are two tables.
+//
+//   fz_cuts_kernel  one lane per read, a workgroup per 256 reads, grid-strided.  LDS: the table of each requested side,
+//       256 x int16 (512 B; thread t brings entry t), then per wave ONE window of FZ_CUT_PIECE_DWORDS x 256 B in the
+//       lane-transposed layout of the overlap and verification kernels (dword d of lane l at win[d * 64 + l]: 32 banks per
+//       half wave, no conflicts at any alignment) — 17 KiB per workgroup.  The read's extent comes from ends[].  Per side the
+//       read is walked in pieces (fz_cuts_piece: from its end for 3', its start for 5'); the piece loop is wave-uniform, it
+//       runs while a ballot says some lane is live, and a finished lane stages nothing (fz_stage_copy<false>: no load, no
+//       LDS store).  Every dword loaded starts in front of buf_len (fz_stage_range).  The lane writes its own 8-byte row: no
+//       atomics, no finish kernel, no memset.
+struct FzCutArgs {
+    FzRagged rag;
+    uint64_t buf_len;
+    const int16_t *w;                                      // the call's tables: side s (0: 3', 1: 5') at w + 256 s
+    uint32_t sides, walk, flags;                           // bit s of sides: side s is asked for (fz_cuts_row); of walk: its table
+                                                           // has a positive score, so it is walked (the others cut nothing)
+    uint32_t num, den;
+    int32_t wmax3, wmax5;                                  // the largest score of each table
+};
+
+// One side of one read: the wave-uniform piece loop -> the number of bytes that side cuts.
+__device__ __forceinline__ uint32_t fz_cuts_side(const uint8_t *__restrict__ buf, const FzCutArgs &a, uint32_t side, int32_t wmax,
+                                                 const int16_t *tab, uint32_t *win, uint64_t sa, uint64_t se, uint32_t n) {
+    const FzCutRule r = fz_cuts_rule(side, a.flags, a.num, a.den, wmax, 1u);
+    FzCutState c = fz_cuts_begin(n, r);
+    while (FZ_WAVE_BALLOT(c.live)) {
+        const FzOvlStage st = fz_cuts_piece(c, sa, se, side, a.buf_len);
+        fz_stage_copy<false>(buf, st, FZ_CUT_PIECE_DWORDS, win, 64u);
+        fz_wave_lds_sync();
+        fz_cuts_lane(c, tab, win, 64u, st, n, side, r);
+        fz_wave_lds_sync();
+    }
+    return c.trim;
+}
+
+__global__ __launch_bounds__(FZ_FILTER_THREADS) void fz_cuts_kernel(const uint8_t *__restrict__ buf, const FzCutArgs a,
+                                                                    FzCutRow *__restrict__ out) {
+    static_assert(FZ_FILTER_THREADS == 256, "thread t brings table entry t");
+    __shared__ int16_t tab[2][256];
+    __shared__ uint32_t wins[FZ_WAVES_PER_BLOCK * FZ_CUT_PIECE_DWORDS * 64u];
+    for (uint32_t side = 0; side < 2u; ++side)
+        if ((a.walk >> side) & 1u) tab[side][threadIdx.x] = a.w[side * 256u + threadIdx.x];
+    __syncthreads();
+    uint32_t *win = wins + (threadIdx.x >> 6) * FZ_CUT_PIECE_DWORDS * 64u + fz_lane();
+    const uint64_t n_seqs = a.rag.n_seqs, groups = (n_seqs + FZ_FILTER_THREADS - 1u) / FZ_FILTER_THREADS;
+    for (uint64_t g = blockIdx.x; g < groups; g += gridDim.x) {
+        const uint64_t j = g * FZ_FILTER_THREADS + threadIdx.x;
+        const bool have = j < n_seqs;
+        const uint64_t sa = have && j ? a.rag.ends[j - 1u] : 0ull, se = have ? a.rag.ends[j] : 0ull;   // (no read: an empty one)
+        const uint32_t n = (uint32_t)(se - sa);
+        const uint32_t trim3 = (a.walk & 1u) ? fz_cuts_side(buf, a, 0u, a.wmax3, tab[0], win, sa, se, n) : 0u;   // (wave-uniform)
+        const uint32_t trim5 = (a.walk & 2u) ? fz_cuts_side(buf, a, 1u, a.wmax5, tab[1], win, sa, se, n) : 0u;
+        if (have) out[j] = fz_cuts_row(n, trim3, trim5, a.sides);
+    }
+}

@@ -430,6 +430,7 @@ struct fz_ctx {
     double drv_ms[5] = {0, 0, 0, 0, 0};          // fz_debug_derive_ms: the last fz_batch_derive
     double fmt_ms[5] = {0, 0, 0, 0, 0};          // fz_debug_format_ms: the last fz_batch_format
     double ovl_ms[4] = {0, 0, 0, 0};             // fz_debug_overlap_ms: the last fz_batch_end_overlaps
+    double cut_ms[4] = {0, 0, 0, 0};             // fz_debug_cuts_ms: the last fz_batch_score_cuts
     bool batch_call = false;                     // inside fz_batch_search: the one caller a batch handle is valid for (validate)
     // sharded searches: where every shard's (rank's) records end in the collected vector, and the shards in ascending
     // order of the index range they own (emit_matches orders shard by shard)
@@ -5230,6 +5231,166 @@ int fz_debug_end_overlaps(uint32_t mode, const uint8_t *pats, const uint64_t *of
     for (uint64_t j = 0; j < n_seqs; ++j) {                   // the finish kernel's lane
         const FzOverlapRow r = fz_overlap_row(table[j], (uint32_t)(ends[j] - (j ? ends[j - 1] : 0ull)));
         memcpy(&out[j], &r, sizeof r);
+    }
+    return FZ_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Score cuts (fz_batch_score_cuts): per read where the running sum of a score table, taken from its 3' and / or its 5' end,
+// peaks.  One launch (fz_kernels.h: fz_cuts_kernel), the lanes write the 8-byte rows, one copy brings them back.
+
+// The call's tables as the kernel takes them: side s (0: 3', 1: 5') at w + 256 s, zeros for a side not asked for.
+struct CutPlan {
+    int16_t w[512];
+    uint32_t sides = 0, walk = 0;                // asked for; asked for with a positive score in the table
+    int32_t wmax[2] = {0, 0};
+    uint32_t wabs = 0;                           // the largest |score| of the tables asked for
+};
+
+// What the call and its host twin refuse first, in this order.
+static int cut_check(const int16_t *w3, const int16_t *w5, uint32_t flags, uint32_t rate_den, CutPlan &p) {
+    if (!w3 && !w5) return fail(FZ_EINVAL, "score cuts: no table, w3 and w5 are both null");
+    if (flags & ~(FZ_CUT_STOP3 | FZ_CUT_STOP5 | FZ_CUT_RATE)) return fail(FZ_EINVAL, "score cuts: flags 0x%x outside FZ_CUT_STOP3 | FZ_CUT_STOP5 | FZ_CUT_RATE", flags);
+    if ((flags & FZ_CUT_RATE) && rate_den == 0) return fail(FZ_EINVAL, "score cuts: rate_den must not be 0 with FZ_CUT_RATE");
+    memset(p.w, 0, sizeof p.w);
+    const int16_t *tabs[2] = {w3, w5};
+    for (uint32_t side = 0; side < 2; ++side) {
+        if (!tabs[side]) continue;
+        memcpy(p.w + 256 * side, tabs[side], 512);
+        int32_t hi = -32768;
+        for (uint32_t c = 0; c < 256; ++c) {
+            const int32_t v = tabs[side][c];
+            hi = std::max(hi, v);
+            p.wabs = std::max(p.wabs, (uint32_t)(v < 0 ? -v : v));
+        }
+        p.wmax[side] = hi;
+        p.sides |= 1u << side;
+        if (hi > 0) p.walk |= 1u << side;
+    }
+    return FZ_OK;
+}
+
+// ... and last: what keeps the lanes' 32-bit sums from wrapping.
+static int cut_check_sums(uint64_t max_seq_len, const CutPlan &p) {
+    if (max_seq_len >= (1ull << 32)) return fail(FZ_EUNSUPPORTED, "score cuts take sequences shorter than 2^32 bytes");
+    if (max_seq_len * p.wabs >= (1ull << 31))
+        return fail(FZ_EUNSUPPORTED, "score cuts: the longest sequence (%llu bytes) times the largest |score| (%u) is not below 2^31",
+                    (unsigned long long)max_seq_len, p.wabs);
+    return FZ_OK;
+}
+
+int fz_batch_score_cuts(fz_ctx *ctx, fz_seq *batch, const int16_t *w3, const int16_t *w5, uint32_t flags, uint32_t rate_num,
+                        uint32_t rate_den, fz_cut **out) {
+    static_assert(sizeof(fz_cut) == sizeof(FzCutRow) && sizeof(fz_cut) == 8, "the kernel writes the C-ABI's rows");
+    const auto t_call = std::chrono::steady_clock::now();
+    auto since = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
+    if (!out) return fail(FZ_EINVAL, "null argument");
+    *out = nullptr;
+    if (!ctx || !batch || batch->ctx != ctx) return fail(FZ_EINVAL, "bad ctx/seq handle");
+    CutPlan p;
+    int rc = cut_check(w3, w5, flags, rate_den, p);
+    if (rc) return rc;
+    if ((rc = batch_single_device(ctx, batch))) return rc;
+    if (!batch->is_batch) return fail(FZ_EUNSUPPORTED, "fz_batch_score_cuts takes a batch handle (fz_batch_upload)");
+    if (ctx->npend || ctx->stream_inflight) return fail(FZ_EINVAL, "a search of this context is in flight");
+    if ((rc = cut_check_sums(batch->max_seq_len, p))) return rc;
+    const uint64_t n_seqs = batch->n_seqs;
+    void *mem = nullptr;
+    if ((rc = alloc_out(n_seqs, sizeof(fz_cut), &mem))) return rc;
+    struct Guard { void *p; ~Guard() { if (p) release_out(p); } } guard{mem};
+    fz_cut *res = static_cast<fz_cut *>(mem);
+    ctx->view = nullptr; ctx->view_n = 0; ctx->rows_ready = false;
+    mp_publish(ctx, MpTotals(), 0, FZ_FORM_NONE);
+    for (double &ms : ctx->cut_ms) ms = 0;
+    if (p.walk == 0 || n_seqs == 0 || batch->n == 0) {        // nothing can be cut: nothing is launched
+        for (uint64_t j = 0; j < n_seqs; ++j) {
+            const FzCutRow r = fz_cuts_row((uint32_t)(batch->ends[j] - (j ? batch->ends[j - 1] : 0ull)), 0u, 0u, p.sides);
+            memcpy(&res[j], &r, sizeof r);
+        }
+        guard.p = nullptr;
+        *out = res;
+        ctx->cut_ms[3] = since(t_call);
+        return FZ_OK;
+    }
+    const Shard &sh = batch->shards[0];
+    DevState &d = ctx->devs[sh.dev];
+    HIP_TRY(hipSetDevice(d.device));
+    // rows | tables (8-, 2-byte alignment)
+    const uint64_t o_tab = n_seqs * sizeof(FzCutRow), need = o_tab + sizeof p.w;
+    if ((rc = grow_device(d, d.d_assign, d.assign_cap, need, need))) return rc;
+    FzCutRow *d_rows = reinterpret_cast<FzCutRow *>(d.d_assign);
+    const auto t_h2d = std::chrono::steady_clock::now();
+    HIP_TRY(hipMemcpyAsync(d.d_assign + o_tab, p.w, sizeof p.w, hipMemcpyHostToDevice, d.stream));
+    HIP_TRY(hipStreamSynchronize(d.stream));               // (p is the call's own: the copy is done before it goes)
+    ctx->cut_ms[0] = since(t_h2d);
+    FzCutArgs a;
+    a.rag = fz_ragged(sh.geom);
+    a.buf_len = sh.geom.buf_len;
+    a.w = reinterpret_cast<const int16_t *>(d.d_assign + o_tab);
+    a.sides = p.sides; a.walk = p.walk; a.flags = flags;
+    a.num = rate_num; a.den = rate_den;
+    a.wmax3 = p.wmax[0]; a.wmax5 = p.wmax[1];
+    MpTotals tot;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((n_seqs + FZ_FILTER_THREADS - 1) / FZ_FILTER_THREADS, (uint64_t)d.n_cus * 8);
+    if (ctx->timing) HIP_TRY(hipEventRecord(d.cur().ev[2], d.stream));
+    hipLaunchKernelGGL(fz_cuts_kernel, dim3(grid), dim3(FZ_FILTER_THREADS), 0, d.stream, sh.d_buf, a, d_rows);
+    HIP_TRY(hipGetLastError());
+    ++tot.launches;
+    if (ctx->timing) HIP_TRY(hipEventRecord(d.cur().ev[3], d.stream));
+    HIP_TRY(hipStreamSynchronize(d.stream));
+    const auto t_d2h = std::chrono::steady_clock::now();
+    HIP_TRY(hipMemcpyAsync(res, d_rows, (size_t)n_seqs * sizeof(fz_cut), hipMemcpyDeviceToHost, d.stream));
+    HIP_TRY(hipStreamSynchronize(d.stream));
+    ctx->cut_ms[2] = since(t_d2h);
+    if (ctx->timing) ctx->cut_ms[1] = span_ms(d.cur().ev[2], d.cur().ev[3]);
+    tot.bytes = sh.geom.buf_len;
+    guard.p = nullptr;
+    *out = res;
+    mp_publish(ctx, tot, 0, FZ_FORM_NONE, ctx->cut_ms[1]);
+    ctx->cut_ms[3] = since(t_call);
+    return FZ_OK;
+}
+
+int fz_debug_cuts_ms(fz_ctx *ctx, double *ms4) {
+    if (!ctx || !ms4) return fail(FZ_EINVAL, "null argument");
+    for (int i = 0; i < 4; ++i) ms4[i] = ctx->cut_ms[i];
+    return FZ_OK;
+}
+
+int fz_debug_score_cuts(const int16_t *w3, const int16_t *w5, uint32_t flags, uint32_t rate_num, uint32_t rate_den,
+                        const uint8_t *bytes, const uint64_t *ends, uint64_t n_seqs, fz_cut *out) {
+    if ((n_seqs && (!ends || !out)) || (n_seqs && ends[n_seqs - 1] && !bytes)) return fail(FZ_EINVAL, "null argument");
+    CutPlan p;
+    if (int rc = cut_check(w3, w5, flags, rate_den, p)) return rc;
+    if (n_seqs >= (1ull << 32)) return fail(FZ_EUNSUPPORTED, "more than 2^32 - 1 sequences in a batch");
+    uint64_t longest = 0;
+    for (uint64_t j = 0; j < n_seqs; ++j) {
+        const uint64_t sa = j ? ends[j - 1] : 0ull;
+        if (ends[j] < sa) return fail(FZ_EINVAL, "sequence offsets must not decrease");
+        longest = std::max(longest, ends[j] - sa);
+    }
+    if (int rc = cut_check_sums(longest, p)) return rc;
+    const uint64_t total = n_seqs ? ends[n_seqs - 1] : 0ull;
+    std::vector<uint8_t> buf((total + 3u) & ~(uint64_t)3, 0);  // the device's buffer: zeros behind the data
+    if (total) memcpy(buf.data(), bytes, (size_t)total);
+    uint32_t win[FZ_CUT_PIECE_DWORDS];
+    for (uint64_t j = 0; j < n_seqs; ++j) {                   // one lane
+        const uint64_t sa = j ? ends[j - 1] : 0ull, se = ends[j];
+        const uint32_t n = (uint32_t)(se - sa);
+        uint32_t trim[2] = {0u, 0u};
+        for (uint32_t side = 0; side < 2u; ++side) {
+            if (!((p.walk >> side) & 1u)) continue;
+            const FzCutRule r = fz_cuts_rule(side, flags, rate_num, rate_den, p.wmax[side], 1u);
+            FzCutState c = fz_cuts_begin(n, r);
+            while (c.live) {                                  // one piece
+                const FzOvlStage st = fz_cuts_piece(c, sa, se, side, total);
+                fz_stage_copy<false>(buf.data(), st, FZ_CUT_PIECE_DWORDS, win, 1u);
+                fz_cuts_lane(c, p.w + 256 * side, win, 1u, st, n, side, r);
+            }
+            trim[side] = c.trim;
+        }
+        const FzCutRow row = fz_cuts_row(n, trim[0], trim[1], p.sides);
+        memcpy(&out[j], &row, sizeof row);
     }
     return FZ_OK;
 }

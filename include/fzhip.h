@@ -344,6 +344,48 @@ int fz_debug_end_overlaps(uint32_t mode, const uint8_t *pats, const uint64_t *of
  * the context's last fz_batch_end_overlaps, in milliseconds. */
 int fz_debug_overlap_ms(fz_ctx *ctx, double *ms4);
 
+/* Score cuts: per sequence of a batch where the running sum of a table of scores, taken from its end, peaks — the cut
+ * position of quality trimming (the running-sum rule of BWA) and of poly-A trimming, which are two tables.  Per sequence r
+ * of n bytes, a table w of 256 signed scores, a flag `stop` and an optional miss rate num / den (a miss: a byte with w < 0):
+ *   cut3(r):  s = best = miss = 0; cut = n
+ *             for i = n - 1 down to 0:  s += w[r[i]]; miss += (w[r[i]] < 0)
+ *                                       if stop and s < 0: break
+ *                                       if s > best and (no rate or miss * den <= num * (n - i)): best = s; cut = i
+ *   cut5(r) = n - cut3(reversed r)
+ * The comparison is strict: of equal peaks the one nearest the end wins.  w3 / w5: the table of the 3' / the 5' side, NULL =
+ * that side is not asked for.  flags: FZ_CUT_STOP3, FZ_CUT_STOP5 = that side stops; FZ_CUT_RATE = rate_num / rate_den is in
+ * force on the sides that do not stop.  Row j of *out (n_seqs rows, released with fz_free): start = cut5 (0 when the 5' side
+ * is not asked for), end = cut3 (n when the 3' side is not); both sides asked for and start >= end: both 0, the empty
+ * sequence.  Quality trimming at cutoff q: w[b] = q - (b - base), stop.  Poly-A: w['A'] = 1, every other byte -2, no stop,
+ * rate 1 / 5.
+ * On the device (fz_kernels.h: fz_cuts_kernel): one lane per sequence walks it in pieces of 64 bytes from the asked end,
+ * with 32-bit sums, and leaves it when the sequence is used up, when `stop` fired, or when s + remaining * wmax <= best
+ * (wmax = the table's largest score: no later sum can pass the peak; exact).  The lane writes its row, ONE copy of
+ * n_seqs * 8 bytes brings the rows back.  A table without a positive score cuts nothing: no side with one, and nothing is
+ * launched.
+ * Refusals, before anything is launched: FZ_EUNSUPPORTED for a plain sequence handle, a context of several devices or in a
+ * communicator, and a batch with max_seq_len * max|w| >= 2^31 (both numbers are named: the sums are 32-bit); FZ_EINVAL for
+ * both tables NULL, flags outside the three, rate_den == 0 with FZ_CUT_RATE, a search of the context still in flight.
+ * fz_stats afterwards: filter_launches = 1 or 0, verify_ms = device_ms = the kernel's span. */
+#define FZ_CUT_STOP3 1u
+#define FZ_CUT_STOP5 2u
+#define FZ_CUT_RATE 4u
+
+typedef struct {
+    uint32_t start, end;
+} fz_cut;
+
+int fz_batch_score_cuts(fz_ctx *ctx, fz_seq *batch, const int16_t *w3, const int16_t *w5, uint32_t flags,
+                        uint32_t rate_num, uint32_t rate_den, fz_cut **out);
+/* Test hook, no device needed: the same call on the host, through the very functions the kernel's lanes run (fz_device.h:
+ * fz_cuts_piece, fz_stage_copy, fz_cuts_lane, fz_cuts_row) and with the same refusals.  bytes = the packed sequences, ends =
+ * their n_seqs cumulative end offsets; out = n_seqs rows. */
+int fz_debug_score_cuts(const int16_t *w3, const int16_t *w5, uint32_t flags, uint32_t rate_num, uint32_t rate_den,
+                        const uint8_t *bytes, const uint64_t *ends, uint64_t n_seqs, fz_cut *out);
+/* ms4 = {tables to the device, kernel (0 for a context that does not time it), rows to the host, the whole call} of the
+ * context's last fz_batch_score_cuts, in milliseconds. */
+int fz_debug_cuts_ms(fz_ctx *ctx, double *ms4);
+
 /* Symbol classes (IUPAC patterns) on the substitutions-only multi-pattern pass.  Two tables of 256 bytes define them:
  *   tmask[t]  the one-hot bit of text byte t among the base symbols (at most 8), 0 when t is no base symbol
  *   pmask[c]  the set of pattern byte c as a mask over those bits, 0 for a plain byte
