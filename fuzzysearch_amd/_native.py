@@ -176,11 +176,14 @@ PROTOTYPES = {
     "fz_debug_scan_regions": (ci, (u64, u64, u32, ci, f64, ci, u32p, vp)),
     "fz_debug_scan_plan": (ci, (cs, u32, u32, u64, u32, ci, u32p, u32p, cip, u32p, vp)),
     "fz_debug_scan_instance": (ci, (u32, cs, u32, u32, u64, u32, u32p, u32p, u32p)),
+    "fz_debug_scan_walk": (ci, (u64, u32, u32, vp, u32, u32, ci, u64p)),
+    "fz_debug_scan_direction": (ci, (vp, vp, cip, u64p)),
     "fz_debug_gather_merge": (ci, (vp, u32, u64, vp, u32, mpp, u64p, u64p)),
     "fz_stats": (ci, (vp, stp)),
     "fz_mem_info": (ci, (vp, u64p, u64p)),
     "fz_set_timing": (ci, (vp, ci)),
     "fz_set_streams": (ci, (vp, ci)),
+    "fz_set_scan_direction": (ci, (vp, ci)),
     "fz_device_ms": (ci, (vp, f64p, ci)),
     "fz_free": (None, (vp,)),
 }
@@ -201,6 +204,7 @@ OPTIONAL = frozenset((
     "fz_batch_derive", "fz_debug_derive_plan", "fz_debug_derive_ms",
     "fz_batch_upload_records_lines", "fz_batch_format", "fz_debug_format_plan", "fz_debug_format_ms",
     "fz_debug_scan_plan", "fz_mem_info", "fz_debug_scan_instance",
+    "fz_debug_scan_walk", "fz_debug_scan_direction", "fz_set_scan_direction",
 ))
 
 _lib = None
@@ -1461,6 +1465,21 @@ class Engine(object):
         """2 (default with one device) or 1 stream per device for the two-deep pipeline of fused searches (fz_set_streams)."""
         with self._lock:
             _check(self._lib.fz_set_streams(self._h, n))
+
+    def set_scan_direction(self, mode):
+        """0 (default): every whole scan of a resident sequence starts where the last one ended, so directions alternate;
+        1: always forward; 2: always reversed (fz_set_scan_direction).  The rows never depend on it."""
+        with self._lock:
+            _check(_entry(self._lib, "fz_set_scan_direction")(self._h, mode))
+
+    def scan_direction(self, seq=None):
+        """(the next eligible scan launch on `seq` would be reversed, reversed launches of this engine so far)
+        (fz_debug_scan_direction)."""
+        nxt, cnt = ci(0), u64(0)
+        with self._lock:
+            _check(_entry(self._lib, "fz_debug_scan_direction")(self._h, seq._h if seq is not None else None,
+                                                                 ctypes.byref(nxt), ctypes.byref(cnt)))
+        return bool(nxt.value), cnt.value
 
     def stats(self):
         st = FzStats()

@@ -231,6 +231,40 @@ struct FzScanArgs {
     uint64_t reg_tile0[FZ_MAX_REGIONS], reg_end[FZ_MAX_REGIONS];
 };
 
+// The tile walk of one scan workgroup.  Logical: first, first + stride, .. below limit — what the regions above say.
+// Physical: the tile whose bytes a step of the walk reads — the logical tile, or (a reversed launch, FZ_FLAG_REVERSE)
+// its mirror ntiles - 1 - logical, so that the workgroups that start first read the END of the buffer first: the next
+// scan of a resident sequence starts where the last one ended, while those lines are still in the Infinity Cache.
+// Everything that orders the work (regions, shares, taper, the limit tests) stays logical; only addresses and
+// positions are physical.  The scan kernel and the host twin (fz_debug_scan_walk) both go through these functions.
+struct FzWalk {
+    uint64_t first, limit;   // logical
+    uint32_t stride;
+    uint64_t phys_first;     // physical tile of iteration 0
+    int32_t phys_stride;     // ... and the step to the next iteration's (negative when reversed)
+};
+FZ_HD uint64_t fz_walk_phys(uint64_t ntiles, uint64_t logical, bool rev) { return rev ? ntiles - 1u - logical : logical; }
+FZ_HD FzWalk fz_scan_walk(uint32_t nreg, const uint32_t *reg_wg0, const uint32_t *reg_nwg, const uint64_t *reg_tile0,
+                          const uint64_t *reg_end, uint32_t grid, uint64_t ntiles, uint32_t wg, bool rev) {
+    uint32_t wg0 = 0, stride = grid;
+    uint64_t tile0 = 0, limit = ntiles;
+#pragma unroll
+    for (uint32_t r = 0; r < FZ_MAX_REGIONS; ++r)
+        if (r < nreg && wg >= reg_wg0[r]) { wg0 = reg_wg0[r]; stride = reg_nwg[r]; tile0 = reg_tile0[r]; limit = reg_end[r]; }
+    FzWalk w;
+    w.first = tile0 + (wg - wg0);
+    w.limit = limit;
+    w.stride = stride;
+    w.phys_first = fz_walk_phys(ntiles, w.first, rev);
+    w.phys_stride = rev ? -(int32_t)stride : (int32_t)stride;
+    return w;
+}
+// Physical tile of iteration `iter` of the walk; ~0 when the walk has no such iteration.
+FZ_HD uint64_t fz_walk_tile(const FzWalk &w, uint32_t iter) {
+    if (w.first + (uint64_t)iter * w.stride >= w.limit) return ~0ull;
+    return (uint64_t)((int64_t)w.phys_first + (int64_t)iter * (int64_t)w.phys_stride);
+}
+
 // A hit: (block g << FZ_IDX_BITS) | global idx (48-bit index: sequences below 256 TiB; 16-bit block number).
 // A record: what verification produced for one hit.
 #define FZ_IDX_BITS 48

@@ -54,17 +54,19 @@
     // DUPH = false (the lean instances): no launch with equal block hashes gets here, the slot-set branch below does not exist
     bool dup_hashes = false;
     if constexpr (DUPH) dup_hashes = (a.flags & FZ_FLAG_DUP_HASHES) != 0;
-    // this workgroup's walk over the tiles: first_tile, first_tile + stride, .. below limit (scalar values); the flushes
-    // decode queue entries with the copy in LDS (fz_code_local)
-    uint32_t wg0 = 0, stride = gridDim.x;
-    uint64_t tile0 = 0, limit = ntiles;
-#pragma unroll
-    for (uint32_t r = 0; r < FZ_MAX_REGIONS; ++r)
-        if (r < a.nreg && blockIdx.x >= a.reg_wg0[r]) { wg0 = a.reg_wg0[r]; stride = a.reg_nwg[r]; tile0 = a.reg_tile0[r]; limit = a.reg_end[r]; }
-    const uint64_t first_tile = tile0 + (blockIdx.x - wg0);
+    // this workgroup's walk over the tiles (fz_device.h: FzWalk): first, first + stride, .. below limit is the logical walk,
+    // kept here as `left` = limit - (the logical tile of this step), so `left > 0` is the walk's `tile < limit`; `ptile` is
+    // the tile whose bytes the step reads — the logical one, or its mirror in a reversed launch — and moves by `pstride`
+    // (four scalar dwords where the logical walk alone kept five: the host keeps a shard below 2^31 tiles, so tile numbers
+    // and their differences are 32-bit values).  The flushes decode queue entries with the physical walk's copy in LDS
+    // (fz_code_local)
+    // (batches and file chunks are never scanned backwards, enqueue_shard: their instances keep the forward walk alone)
+    const FzWalk wk = fz_scan_walk(a.nreg, a.reg_wg0, a.reg_nwg, a.reg_tile0, a.reg_end, gridDim.x, ntiles, blockIdx.x,
+                                   !RAG && !SEG && (a.flags & FZ_FLAG_REVERSE) != 0);
+    const int32_t stride = (int32_t)wk.stride, pstride = wk.phys_stride;
     if (threadIdx.x == 0) {
         uint32_t *walk = reinterpret_cast<uint32_t *>(smem + FZ_WALK_LDS);
-        walk[0] = (uint32_t)first_tile; walk[1] = (uint32_t)(first_tile >> 32); walk[2] = stride;
+        walk[0] = (uint32_t)wk.phys_first; walk[1] = (uint32_t)wk.phys_stride;
     }
     __syncthreads();
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -85,10 +87,11 @@
     uint32_t qf = 0;                                  // PREF: entries [0, qf) have their windows requested
     uint32_t confirmed = 0;                           // wave-uniform statistics
     uint32_t titer = 0;                               // tile iteration of this workgroup
-    uint64_t tile = first_tile;
+    int32_t left = (int32_t)(wk.limit - wk.first);    // <= 0: no tile (left)
+    uint32_t ptile = (uint32_t)wk.phys_first;
     // has_near_match_* (substitutions_only.py:218-233 stops at the first match): a workgroup that starts after a record
     // has been counted skips its tiles (thousands of short workgroups per launch: the ones not yet started are the saving)
-    if ((a.flags & FZ_FLAG_ANY) && __hip_atomic_load(&counters[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0ull) tile = limit;
+    if ((a.flags & FZ_FLAG_ANY) && __hip_atomic_load(&counters[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0ull) left = 0;
     bool slow = false;                                // a tile is being re-scanned by enumeration
     uint32_t slow_pos = 0;
     // Bit-vector form: the queue is worked off in full passes (fz_bits_flush) and filled as far as the tiles' recent yield
@@ -187,7 +190,7 @@
 
     for (;;) {
         if (slow) {
-            // enumerate (row, offset, block) candidates of tile `tile`, 64 lanes at a time
+            // enumerate (row, offset, block) candidates of this step's tile, 64 lanes at a time
             const uint32_t nb = ADAPT ? min(bw, a.nblk - b0) : a.nblk;      // (bit-vector form: the blocks of this pass)
             const uint32_t steps = FZ_FILTER_ROWS * 16u * nb;
             while (slow_pos < steps && qn + 64u <= qcap) {
@@ -200,14 +203,14 @@
             if (slow_pos >= steps) {
                 slow = false;
                 if (ADAPT && b0 + bw < a.nblk) b0 += bw;
-                else { b0 = 0; tile += stride; ++titer; }
+                else { b0 = 0; left -= stride; ptile += (uint32_t)pstride; ++titer; }
             }
-        } else if (tile < limit && (ADAPT ? (qn == 0u || qn + ylast + (ylast >> 2) + 8u <= qcap) : qn <= qcap / 2)) {
+        } else if (left > 0 && (ADAPT ? (qn == 0u || qn + ylast + (ylast >> 2) + 8u <= qcap) : qn <= qcap / 2)) {
             uint4 va[2], vb[2];
             uint2 ha[2], hb[2];
             bool pre;                                 // va / ha hold rows 0-1 of the next tile
             {
-                const uint8_t *tsrc = buf + fz_bcast64(tile * (uint64_t)FZ_TILE_BYTES);
+                const uint8_t *tsrc = buf + fz_bcast64((uint64_t)ptile * FZ_TILE_BYTES);
 #pragma unroll
                 for (int r = 0; r < 2; ++r) {
                     va[r] = *reinterpret_cast<const uint4 *>(tsrc + r * FZ_ROW_BYTES + lane_off);
@@ -215,7 +218,7 @@
                 }
             }
             do {
-                const uint8_t *tsrc = buf + fz_bcast64(tile * (uint64_t)FZ_TILE_BYTES);
+                const uint8_t *tsrc = buf + fz_bcast64((uint64_t)ptile * FZ_TILE_BYTES);
 #pragma unroll
                 for (int r = 0; r < 2; ++r) {
                     vb[r] = *reinterpret_cast<const uint4 *>(tsrc + (r + 2) * FZ_ROW_BYTES + lane_off);
@@ -226,12 +229,14 @@
                 test_row(va[0], ha[0], std::integral_constant<int, 0>{});
                 test_row(va[1], ha[1], std::integral_constant<int, 1>{});
                 const bool same_tile = ADAPT && b0 + bw < a.nblk;       // the next pass is over this tile again (its other blocks)
-                const uint64_t next = same_tile ? tile : tile + stride;
-                if constexpr (ADAPT) pre = next < limit && qn + 3u * (qn - q_tile) + 8u <= qcap;   // this pass's second half + the next pass
-                else pre = next < limit && qn <= qcap / 2;
+                // (wave-uniform: pinned to scalar registers, which `same_tile` alone does not tell the compiler)
+                const int32_t lnext = same_tile ? left : left - stride;
+                const uint32_t pnext = fz_uniform(same_tile ? ptile : ptile + (uint32_t)pstride);
+                if constexpr (ADAPT) pre = lnext > 0 && qn + 3u * (qn - q_tile) + 8u <= qcap;   // this pass's second half + the next pass
+                else pre = lnext > 0 && qn <= qcap / 2;
                 {   // unconditional (a branch here would make the compiler wait for the prefetch at the join):
                     // without a next tile the loads re-read this one (L2 hits, results unused)
-                    const uint8_t *nsrc = buf + fz_bcast64((pre ? next : tile) * (uint64_t)FZ_TILE_BYTES);
+                    const uint8_t *nsrc = buf + fz_bcast64((uint64_t)(pre ? pnext : ptile) * FZ_TILE_BYTES);
 #pragma unroll
                     for (int r = 0; r < 2; ++r) {
                         va[r] = *reinterpret_cast<const uint4 *>(nsrc + r * FZ_ROW_BYTES + lane_off);
@@ -261,8 +266,8 @@
                 }
                 if constexpr (ADAPT) ylast = qn - q_tile;
                 if (PREF && qn > qf) {
-                    if (tile) fz_prefetch_tile(buf, a, w, qf, qn, tile * (uint64_t)FZ_TILE_BYTES);
-                    else fz_prefetch_windows(buf, a, w, qf, qn);          // the first tile: windows clamped at the start
+                    if (ptile) fz_prefetch_tile(buf, a, w, qf, qn, (uint64_t)ptile * FZ_TILE_BYTES);
+                    else fz_prefetch_windows(buf, a, w, qf, qn);          // the buffer's first tile (a reversed walk's last): windows clamped at the start
                     qf = qn;
                 }
                 if constexpr (ADAPT) {
@@ -271,16 +276,18 @@
                     } else {
                         b0 = 0;
                         if (bw < a.nblk && ylast <= (qcap >> 3)) bw <<= 1;   // little queued: twice the blocks per pass from the next tile on
-                        tile = next;
+                        left = lnext;
+                        ptile = pnext;
                         ++titer;
                     }
                 } else {
-                    tile = next;
+                    left = lnext;
+                    ptile = pnext;
                     ++titer;
                 }
             } while (pre);                            // else: the end of the sequence, or a flush is due
         }
-        const bool done = !slow && tile >= limit;
+        const bool done = !slow && left <= 0;
         if (PREF && done) break;                      // what is queued now is verified by the pooled flush below
         if constexpr (WF) {
             // lane-per-cell verification (Levenshtein budgets 5 .. 15): own queue in mid-scan, the workgroup's pool at the end

@@ -59,7 +59,7 @@
 #define FZ_LUT_BYTES (FZ_LUT_SLOTS * 4u)
 #define FZ_TABLE_BYTES (2u * FZ_LUT_BYTES + 32u)           // the hash table + one dword per slot: the block that lives there,
                                                            // four dwords of the pooled flush, the workgroup's tile walk (below)
-#define FZ_WALK_LDS (2u * FZ_LUT_BYTES + 16u)              // LDS address of {first tile lo, hi, tile stride}: the scan kernel's
+#define FZ_WALK_LDS (2u * FZ_LUT_BYTES + 16u)              // LDS address of {first tile, tile stride}: the scan kernel's
                                                            // dynamic LDS starts at address 0
                                                            // + the four waves' final queue fills (pooled last flush)
                                                            // (same byte offset as the hash: no address arithmetic in the rare path)
@@ -68,6 +68,8 @@
                                                            // the device (consolidate_overlapping_matches, common.py:145-189, first stage)
 #define FZ_FLAG_ANY 2u                                     // has_near_match_*: the caller only asks WHETHER a record exists — work that starts
                                                            // after the first record has been counted is skipped
+#define FZ_FLAG_REVERSE 8u                                 // the scan reads the mirror of every tile of its walk (fz_device.h: FzWalk): the
+                                                           // workgroups that start first read the end of the buffer first
 #if FZ_LUT_BITS == 5
 #define FZ_LUT_ADDR_MASK_STR "0x7c"                        // (FZ_LUT_SLOTS - 1) * 4: byte address of a slot
 #else
@@ -480,11 +482,12 @@ __device__ __forceinline__ uint32_t fz_code(uint32_t off, uint32_t blk, uint32_t
 // Queue entry -> (block of this launch, local byte position in the buffer).
 __device__ __forceinline__ uint64_t fz_code_local(uint32_t code, uint32_t &blk) {
     blk = (code >> FZ_TILE_BITS) & (FZ_MAX_BLOCKS_PER_LAUNCH - 1u);
-    // the workgroup's tile walk (first tile, stride) as the scan kernel left it in LDS
+    // the workgroup's physical tile walk (first tile, stride) as the scan kernel left it in LDS.  A shard has fewer than
+    // 2^31 tiles (enqueue_shard), so the walk is 32-bit arithmetic, and the negative stride of a reversed launch is its
+    // two's complement: the sum wraps to the tile
     FzLdsU32 *walk = (FzLdsU32 *)(uintptr_t)FZ_WALK_LDS;
-    const uint64_t first = ((uint64_t)walk[1] << 32) | walk[0];
-    const uint64_t tile = first + (uint64_t)(code >> (FZ_TILE_BITS + FZ_BLK_BITS)) * walk[2];
-    return tile * (uint64_t)FZ_TILE_BYTES + (code & (FZ_TILE_BYTES - 1u));
+    const uint32_t tile = walk[0] + (code >> (FZ_TILE_BITS + FZ_BLK_BITS)) * walk[1];
+    return (uint64_t)tile * FZ_TILE_BYTES + (code & (FZ_TILE_BYTES - 1u));
 }
 
 // Fused in-memory scan: request the sequence windows of the queue entries [qf, qn) — a.win_pieces LDS-DMA

@@ -70,6 +70,10 @@ struct Switches {
     int taper_steps = 4;               // FZ_TAPER_STEPS (0: no regions), FZ_TAPER_MIN, FZ_TAPER_WG_PER_CU: the scan grid's last round
     double taper_min = 0.25;
     int taper_wg_per_cu = 7;
+    int scan_dir = 0;                  // FZ_SCAN_DIR=alt / fwd / rev: a context's default for fz_set_scan_direction (0 alternate, 1 always
+                                       // forward, 2 always reversed)
+    bool scan_rounds = false;          // FZ_SCAN_ROUNDS=1: a scan next to its predecessor lays its first and last resident round down in
+                                       // address order (plan_scan_rounds; measured, not the default: profiles/r25_sweep_direction.txt)
     bool no_rccl = false;              // FZ_NO_RCCL: behave like an install without librccl
     std::string rccl_lib;              // FZ_RCCL_LIB=path: the collective library to dlopen first (tests: tests/libmock_rccl.so)
     std::string rocm_path = "/opt/rocm";   // ROCM_PATH
@@ -95,6 +99,8 @@ Switches read_switches() {
         if (const char *e = getenv("ROCM_PATH")) v.rocm_path = e;
         if (const char *e = getenv("FZ_COMM_TIMEOUT_MS")) v.comm_timeout_ms = std::max(1L, atol(e));
         v.mp_force_pass = flag("FZ_MP_FORCE_PASS");
+        if (const char *e = getenv("FZ_SCAN_DIR")) v.scan_dir = !strcmp(e, "fwd") ? 1 : !strcmp(e, "rev") ? 2 : 0;
+        v.scan_rounds = flag("FZ_SCAN_ROUNDS");
         v.trace = flag("FZ_TRACE"); v.stream_trace = flag("FZ_STREAM_TRACE");
         return v;
 }
@@ -276,6 +282,10 @@ struct Shard {
     uint8_t *d_buf = nullptr;                    // = d_alloc + FZ_PAD_FRONT
     uint64_t alloc_bytes = 0;
     FzGeom geom{};
+    // The last launch over this shard's whole buffer walked forward, i.e. towards the physical end (eligible or not; a
+    // has_near_match_* launch that skipped tiles counts as well: the bit steers, it promises nothing): the next eligible
+    // launch of an alternating context starts at the end and walks back (enqueue_shard).  Launch state, not data: mutable.
+    mutable bool scan_at_end = false;
 };
 
 }  // namespace
@@ -451,6 +461,10 @@ struct fz_ctx {
     // fz_set_streams: 2 = the younger of two fused searches in flight scans on the other stream of its device, next to the
     // older one; 1 = behind it on the same stream.  fz_create sets the default (2 for a context of one device state).
     int streams = 1;
+    // fz_set_scan_direction: 0 = every eligible scan launch starts where the shard's last one ended (alternating
+    // directions), 1 = always forward, 2 = always reversed; and the reversed launches so far (fz_debug_scan_direction)
+    int scan_dir = sw().scan_dir;
+    std::atomic<uint64_t> rev_launches{0};
     double last_gather_ms = 0;                   // host time of the last search's exchange step (all-gather + D2H + parse)
     // multi-device contexts: one host thread per device (enqueue, wait, collect and order its shard), and what the
     // shards of the search being collected left (rows_ready: every shard's rows are ordered, emit_matches only merges)
@@ -934,6 +948,30 @@ void plan_scan_regions(FzScanArgs &fa, uint64_t ntiles, uint64_t grid, uint32_t 
     plan_scan_regions(fa, ntiles, grid, n_cus, steps, fmin, t_per_cu);
 }
 
+// FZ_SCAN_ROUNDS=1, the plan of a scan next to its predecessor: {first resident round | middle | last resident round}.  With
+// nreg = 0 every workgroup strides over the whole buffer, so what a launch reads last is spread over all of it; here the
+// first and the last `n_cus x taper_wg_per_cu` workgroups stride over a range of their own at the start / the end of the
+// buffer (one workgroup's share each, as before), which the chip then sweeps in address order, one resident front (~28 MiB)
+// at a time — what a mirrored successor re-reads first is what this launch read last.  Grids below two fronts keep nreg = 0.
+void plan_scan_rounds(FzScanArgs &fa, uint64_t ntiles, uint64_t grid, uint32_t n_cus) {
+    fa.nreg = 0;
+    const uint64_t W = (uint64_t)n_cus * (uint64_t)std::max(1, sw().taper_wg_per_cu);
+    if (grid < 2 * W || ntiles < 4 * grid) return;
+    const uint64_t edge = ntiles * W / grid, mid = grid - 2 * W;
+    uint64_t at = 0, wg = 0;
+    auto add = [&](uint64_t nwg, uint64_t tiles) {
+        if (!nwg) return;
+        fa.reg_wg0[fa.nreg] = (uint32_t)wg; fa.reg_nwg[fa.nreg] = (uint32_t)nwg;
+        fa.reg_tile0[fa.nreg] = at; fa.reg_end[fa.nreg] = at + tiles;
+        ++fa.nreg; wg += nwg; at += tiles;
+    };
+    add(W, mid ? edge : ntiles - edge);
+    add(mid, ntiles - 2 * edge);
+    add(W, edge);
+    for (uint32_t r = 0; r < fa.nreg; ++r)
+        if ((fa.reg_end[r] - fa.reg_tile0[r] + fa.reg_nwg[r] - 1) / fa.reg_nwg[r] >= FZ_TITER_MAX) { fa.nreg = 0; break; }
+}
+
 // What one scan of a shard runs: the grid, the verification form and the sizes that go with them.  The shape fields of
 // FzScanArgs (regions, fused, vlanes, qcap, win_pieces, win_dwords, band_w) are written into the scan's arguments.
 struct ScanPlan {
@@ -944,6 +982,7 @@ struct ScanPlan {
     uint32_t lds = 0;            // dynamic LDS of a scan workgroup
     VerifyPlan vp;               // the stand-alone verification (with_verify and not fused)
     bool overlapped = false;     // the launch runs next to the scan of the search in flight before it (enqueue_shard)
+    bool partial = false;        // the call scans a piece of the buffer (has_near_match_* in growing pieces)
 };
 
 // Everything that decides what a scan of the shard with geometry `geom` runs: a function of the search, the geometry, the
@@ -958,7 +997,7 @@ ScanPlan plan_scan(const Search &q, const FzGeom &geom, uint32_t n_cus, bool wit
     const uint64_t ntiles_all = (geom.buf_len + FZ_TILE_BYTES - 1) / FZ_TILE_BYTES;
     const uint64_t tile_lo = std::min<uint64_t>(ntiles_all, q.part_lo / FZ_TILE_BYTES);
     const uint64_t tile_hi = q.part_hi == ~0ull ? ntiles_all : std::min<uint64_t>(ntiles_all, (q.part_hi + FZ_TILE_BYTES - 1) / FZ_TILE_BYTES);
-    const bool partial = tile_lo != 0 || tile_hi != ntiles_all;
+    const bool partial = sp.partial = tile_lo != 0 || tile_hi != ntiles_all;
     const uint64_t ntiles = sp.ntiles = tile_hi > tile_lo ? tile_hi - tile_lo : 0;
     const bool force_big = sw().force_big_verify;
     sp.vp = plan_verify(q);
@@ -1124,6 +1163,7 @@ ScanPlan plan_scan(const Search &q, const FzGeom &geom, uint32_t n_cus, bool wit
     // (kTaperSteps groups, down to kTaperMin of a full share) of their own tile range at the end of the buffer, the others
     // correspondingly more.
     if (!sp.overlapped || kTaperOverlapped) plan_scan_regions(fa, ntiles, sp.grid, n_cus);
+    else if (sw().scan_rounds) plan_scan_rounds(fa, ntiles, sp.grid, n_cus);
     else fa.nreg = 0;
     if (partial) {                                               // one region: the call's tiles, no taper
         fa.nreg = 1;
@@ -1160,7 +1200,10 @@ uint32_t fill_launch_blocks(FzScanArgs &fa, const Search &q, uint32_t g0, const 
 
 // Enqueue scan (+ separate verify when it cannot be fused) for one shard on its device stream, as plan_scan decided.
 // No host synchronisation.  `behind`: another search of the context is in flight (fz_*_begin with one search pending).
-int enqueue_shard(fz_ctx *ctx, const Shard &sh, const Search &q, bool with_verify, bool copy_back = true, bool behind = false) {
+// `forward`: the re-run of a search whose results outgrew their buffers — always forward, so that the direction of a
+// launch depends on nothing but the rule below.
+int enqueue_shard(fz_ctx *ctx, const Shard &sh, const Search &q, bool with_verify, bool copy_back = true, bool behind = false,
+                  bool forward = false) {
     DevState &d = lane_dev(ctx, sh.dev);
     HIP_TRY(hipSetDevice(d.device));
     unsigned long long *counters = reinterpret_cast<unsigned long long *>(d.d_out);
@@ -1181,6 +1224,8 @@ int enqueue_shard(fz_ctx *ctx, const Shard &sh, const Search &q, bool with_verif
     const uint32_t L = q.plan.L;
     const uint32_t G = (uint32_t)q.plan.s.size();
     const uint64_t ntiles = sp.ntiles;
+    // (the scan kernel keeps a workgroup's distance to its limit and its signed tile stride in 32 bits: 32 TiB per shard)
+    if ((sh.geom.buf_len + FZ_TILE_BYTES - 1) / FZ_TILE_BYTES >> 31) return fail(FZ_EUNSUPPORTED, "a shard of 2^31 tiles or more");
     const dim3 grid(sp.grid);
     if (q.mode == FZ_MODE_GENERIC && !with_verify) fa.gen_dedup = d.gen_dedup_arg;      // the scan fills the window table (run_generic)
     {
@@ -1233,9 +1278,20 @@ int enqueue_shard(fz_ctx *ctx, const Shard &sh, const Search &q, bool with_verif
     const bool attach = ntiles > 0 && G > 0;
     if (ctx->timing && !attach) HIP_TRY(hipEventRecord(d.cur().ev[0], st));
     uint32_t launches = 0;
+    // Direction (FZ_FLAG_REVERSE).  A resident sequence is scanned again and again, and a sweep that starts where the last
+    // one ended re-reads the lines read last while they are still in the Infinity Cache; two sweeps in the same direction
+    // re-use every line at the distance of the whole buffer.  Every eligible launch — in memory, one sequence, the whole
+    // buffer: each verification form, both streams of the pipeline, the launches of a search of more than 16 blocks among
+    // themselves — therefore takes the direction that starts at the end its shard's last whole scan stopped at.  Batches,
+    // file chunks, the growing pieces of has_near_match_* and overflow re-runs go forward.  Results are ordered on the
+    // host: the direction changes no row, and neither the plan nor the number of launches.
+    const bool may_reverse = sh.geom.seg_stride == 0 && !geom_is_ragged(sh.geom) && !sp.partial && !q.any && !forward;
     for (uint32_t g0 = 0; g0 < G && ntiles > 0;) {
         // Blocks [g0, g0 + nblk) of this launch, the hash multiplier and whether two of the blocks hash alike
         const uint32_t nblk = fill_launch_blocks(fa, q, g0, hgeom);
+        const bool reverse = may_reverse && (ctx->scan_dir == 2 || (ctx->scan_dir == 0 && sh.scan_at_end));
+        if (reverse) { fa.flags |= FZ_FLAG_REVERSE; ctx->rev_launches.fetch_add(1, std::memory_order_relaxed); }
+        if (!sp.partial) sh.scan_at_end = !reverse;
         // the final kernel of the search publishes the counters to the host (direct mode)
         const bool verify_follows = with_verify && !fa.fused;
         fa.host_hdr = (direct && !verify_follows && g0 + nblk >= G) ? reinterpret_cast<uint64_t>(d.cur().h_stage_dev) : 0;
@@ -1622,7 +1678,7 @@ int gather_records(fz_ctx *ctx, fz_seq *seq, std::vector<FzRec> &recs) {
 }
 
 // Launch a search on every shard (no host synchronisation).
-int search_enqueue(fz_ctx *ctx, fz_seq *seq, const Search &q, bool with_verify, bool behind = false) {
+int search_enqueue(fz_ctx *ctx, fz_seq *seq, const Search &q, bool with_verify, bool behind = false, bool forward = false) {
     ctx->view = nullptr;
     ctx->view_n = 0;
     ctx->rows_ready = false;
@@ -1630,8 +1686,8 @@ int search_enqueue(fz_ctx *ctx, fz_seq *seq, const Search &q, bool with_verify, 
     ctx->stats.bytes_scanned = ctx->stats.ngram_hits = ctx->stats.raw_matches = 0;
     ctx->stats.filter_ms = ctx->stats.verify_ms = ctx->stats.device_ms = 0;
     ctx->tref.clear();
-    int rc = for_each_shard(ctx, seq, [ctx, seq, &q, with_verify, behind](size_t si) {
-        return enqueue_shard(ctx, seq->shards[si], q, with_verify, true, behind);
+    int rc = for_each_shard(ctx, seq, [ctx, seq, &q, with_verify, behind, forward](size_t si) {
+        return enqueue_shard(ctx, seq->shards[si], q, with_verify, true, behind, forward);
     });
     if (rc) return rc;
     for (const Shard &sh : seq->shards) {
@@ -1712,7 +1768,7 @@ int search_collect(fz_ctx *ctx, fz_seq *seq, const Search &q, bool with_verify, 
             }
             return FZ_OK;
         }
-        rc = search_enqueue(ctx, seq, q, with_verify);
+        rc = search_enqueue(ctx, seq, q, with_verify, false, /*forward=*/true);
         if (rc) return rc;
     }
     return fail(FZ_EDEVICE, "result buffers kept overflowing");
@@ -1816,7 +1872,7 @@ int run_generic(fz_ctx *ctx, fz_seq *seq, const Search &q, std::vector<FzGenRec>
                 d.dedup_zeroed = false;
                 d.gen_dedup_arg = reinterpret_cast<uint64_t>(d.d_gen_dedup);
             }
-            int rc = enqueue_shard(ctx, sh, q, /*with_verify=*/false, /*copy_back=*/false);
+            int rc = enqueue_shard(ctx, sh, q, /*with_verify=*/false, /*copy_back=*/false, /*behind=*/false, /*forward=*/attempt > 0);   // (a re-run goes forward)
             if (rc) return rc;
             SearchRun &run = d.cur().run;                     // (fresh from enqueue_shard)
             run.dedup_used = dedup;
@@ -5821,6 +5877,26 @@ int fz_debug_scan_plan(const uint8_t *p, uint32_t m, uint32_t k, uint64_t buf_le
     return FZ_OK;
 }
 
+int fz_debug_scan_walk(uint64_t ntiles, uint32_t grid, uint32_t n_regions, const uint64_t *table, uint32_t wg, uint32_t iter,
+                       int reversed, uint64_t *tile) {
+    if (!tile || (n_regions && !table) || n_regions > FZ_MAX_REGIONS || grid == 0 || wg >= grid) return fail(FZ_EINVAL, "bad argument");
+    uint32_t wg0[FZ_MAX_REGIONS] = {0}, nwg[FZ_MAX_REGIONS] = {0};
+    uint64_t tile0[FZ_MAX_REGIONS] = {0}, end[FZ_MAX_REGIONS] = {0};
+    for (uint32_t r = 0; r < n_regions; ++r) {
+        wg0[r] = (uint32_t)table[4 * r]; nwg[r] = (uint32_t)table[4 * r + 1]; tile0[r] = table[4 * r + 2]; end[r] = table[4 * r + 3];
+    }
+    *tile = fz_walk_tile(fz_scan_walk(n_regions, wg0, nwg, tile0, end, grid, ntiles, wg, reversed != 0), iter);
+    return FZ_OK;
+}
+
+int fz_debug_scan_direction(fz_ctx *ctx, fz_seq *seq, int *next_reversed, uint64_t *reversed_launches) {
+    if (!ctx || !next_reversed || !reversed_launches) return fail(FZ_EINVAL, "null argument");
+    const bool at_end = seq && !seq->shards.empty() && seq->shards[0].scan_at_end;       // (every shard has its own bit: the first one's)
+    *next_reversed = (ctx->scan_dir == 2 || (ctx->scan_dir == 0 && at_end)) ? 1 : 0;
+    *reversed_launches = ctx->rev_launches.load(std::memory_order_relaxed);
+    return FZ_OK;
+}
+
 int fz_debug_scan_instance(uint32_t mode, const uint8_t *p, uint32_t m, uint32_t k, uint64_t buf_len, uint32_t n_cus,
                            uint32_t *n_launches, uint32_t *lean_mask, uint32_t *form) {
     if (!p || !n_launches || !lean_mask || !form || m == 0 || m / (k + 1) == 0 || n_cus == 0 || (mode != FZ_MODE_LEV && mode != FZ_MODE_SUBS))
@@ -6301,7 +6377,7 @@ int stream_launch(fz_stream *st, uint64_t j0, uint64_t j1, uint64_t data_hi) {
     if (st->mode != FZ_MODE_GENERIC) {
         memset(&ctx->stats, 0, sizeof ctx->stats); ctx->tref.clear();
         ctx->stats.n_devices = 1;
-        rc = search_enqueue(ctx, st->seq, st->q, st->mode != FZ_MODE_EXACT);
+        rc = search_enqueue(ctx, st->seq, st->q, st->mode != FZ_MODE_EXACT, false, /*forward=*/true);   // a batch of file chunks: read once
         if (rc) return rc;
     }
     st->inflight = true;
@@ -7125,6 +7201,13 @@ int fz_set_timing(fz_ctx *ctx, int on) {
     if (!ctx) return fail(FZ_EINVAL, "null argument");
     if (ctx->npend || ctx->stream_inflight) return fail(FZ_EINVAL, "a search of this context is in flight");
     ctx->timing = on != 0;
+    return FZ_OK;
+}
+
+int fz_set_scan_direction(fz_ctx *ctx, int mode) {
+    if (!ctx || mode < 0 || mode > 2) return fail(FZ_EINVAL, "scan direction must be 0 (alternate), 1 (forward) or 2 (reversed)");
+    if (ctx->npend || ctx->stream_inflight) return fail(FZ_EINVAL, "a search of this context is in flight");
+    ctx->scan_dir = mode;
     return FZ_OK;
 }
 

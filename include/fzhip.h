@@ -738,6 +738,17 @@ int fz_debug_scan_plan(const uint8_t *p, uint32_t m, uint32_t k, uint64_t buf_le
 int fz_debug_scan_instance(uint32_t mode, const uint8_t *p, uint32_t m, uint32_t k, uint64_t buf_len, uint32_t n_cus,
                            uint32_t *n_launches, uint32_t *lean_mask, uint32_t *form);
 
+/* Test hook, no device needed: the host twin of the scan kernel's tile walk (fz_device.h: fz_scan_walk, the function the
+ * kernel itself calls).  `ntiles`, `grid` and the region table as fz_debug_scan_plan returns them (n_regions rows);
+ * *tile = the tile of the buffer that workgroup `wg` reads in its iteration `iter` of a forward (reversed = 0) or a
+ * reversed launch, ~0 when the workgroup has no such iteration. */
+int fz_debug_scan_walk(uint64_t ntiles, uint32_t grid, uint32_t n_regions, const uint64_t *table, uint32_t wg, uint32_t iter,
+                       int reversed, uint64_t *tile);
+
+/* Test hook: *next_reversed = the next eligible scan launch of the context on the FIRST shard of `seq` (every shard keeps
+ * its own direction bit; NULL: on a sequence not scanned yet) would run reversed (fz_set_scan_direction); *reversed_launches = reversed scan launches of the context so far. */
+int fz_debug_scan_direction(fz_ctx *ctx, fz_seq *seq, int *next_reversed, uint64_t *reversed_launches);
+
 /* Test hook (no device needed): the host half of the exchange step of a collective search (what follows the
  * ncclAllGather).  `blocks` = `world` blocks of 1024 + cap * 24 bytes, block r = what rank r contributed: 128 64-bit
  * counters (word 1 = records the rank produced) followed by min(count, cap) device records (see fz_debug_order_records);
@@ -767,6 +778,12 @@ int  fz_set_timing(fz_ctx *ctx, int on);
  * has finished.  Synchronous calls always run on the first stream.  Under overlap a kernel's own hipEvent span (filter_ms,
  * fz_device_ms) includes the time it shares the device with its neighbour, so it no longer measures the kernel alone. */
 int  fz_set_streams(fz_ctx *ctx, int n);
+/* Direction of the whole-buffer scans of a resident sequence.  0 (default; FZ_SCAN_DIR=alt) = every such launch starts at
+ * the end of the buffer its shard's last whole scan stopped at, so consecutive scans alternate between walking forward and
+ * walking back and the second re-reads what the first read last while it is still in the device's last-level cache;
+ * 1 (FZ_SCAN_DIR=fwd) = always forward; 2 (FZ_SCAN_DIR=rev) = always reversed.  Batches, file streams, has_near_match_*
+ * and the re-run of a search whose results outgrew their buffers always go forward.  No row depends on the direction. */
+int  fz_set_scan_direction(fz_ctx *ctx, int mode);
 /* hipEvent span of the filter kernel(s) of the search collected last, per device of the ctx (at most `cap` values
  * are written); returns the number of devices, or a negative FZ_E* code. */
 int  fz_device_ms(fz_ctx *ctx, double *filter_ms, int cap);
